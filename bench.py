@@ -12,9 +12,15 @@ BASELINE.json config 3: 1024 bags x 10 s per GPU (= 10 240 x 0.96 s clips), bf16
 matrix cores, f32 front-end and head. Bags are independent in eval mode, so N GPUs run N
 shards with no data-path collective (weak scaling); timing is max over ranks.
 
-The JSON line also carries `roofline` (dominant kernel, measured live with events on the
-launch stream) and, on rank 0 at N = 1, `cpu_baseline` (the oracle = CPU restatement of the
-reference, timed on this host's cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints the headline line. With --full the
+line also carries `roofline` (dominant kernel, measured live with events on the launch stream),
+the other legs (bf16x3 / f32 modes, host buffers, 1 020-clip batch, training step; the
+data-parallel train step at N > 1) and, on rank 0 at N = 1, `cpu_baseline` (the oracle = CPU
+restatement of the reference, timed on this host's cores on a bounded sample).
+
+--dump-outputs DIR writes what the last timed step returned (the (bags, 10) scores; in --mode
+train the loss and hit counters) as DIR/<name>.npy; inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -46,6 +52,14 @@ PEAK_HBM_GBPS = 8000.0
 CONV_BYTES = {"conv2": lambda e: (48 * 32 * 64 + 24 * 16 * 128) * e, "conv3": lambda e: (24 * 16 * 128 + 24 * 16 * 256) * e,
               "conv4": lambda e: (24 * 16 * 256 + 12 * 8 * 256) * e, "conv5": lambda e: (12 * 8 * 256 + 12 * 8 * 512) * e,
               "conv6": lambda e: (12 * 8 * 512 + 6 * 4 * 512) * e}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: name -> device tensor of the last timed step, written as path/<name>.npy (float32; float64 stays)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def kernel_averages(prof):
@@ -303,7 +317,7 @@ DP_VARIANTS = (("frozen_bf16", False, True), ("frozen_bf16_per_shard_bn", False,
 
 
 def dp_train_leg(world, rank, device, backend, bags=512, steps=5, warmup=2, variants=DP_VARIANTS):
-    """BASELINE config 5 inside the line the driver's scaling run produces (`python bench.py --gpus N`, N > 1): after the
+    """BASELINE config 5 inside the line of `python bench.py --gpus N --full` (N > 1): after the
     inference headline EVERY rank runs the data-parallel train.py step (train.py:119-142: zero_grad -> forward -> CrossEntropyLoss
     -> backward -> Adam) on its own `bags` bags of 96 x 64 log-mel -- global batch N x bags, 4096 at N = 8 -- with SyncBN sums and
     the flat gradient buffer all-reduced over the group (RCCL through mla_allreduce_flat under backend nccl). Same barrier /
@@ -411,13 +425,15 @@ def train_mode(args, world, rank, device):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step(x, y)
+        loss, hits = step(x, y)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:                     # loss and hits are global (all-reduced) values: rank 0 writes them
+        dump_outputs(args.dump_outputs, {"loss": loss, "hits": hits})
     if rank == 0:
         clips = bags * T_BAG
         assert bool(torch.isfinite(loss))
@@ -509,7 +525,8 @@ def dry_run(args, world, rank):
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps({"dry_run": True, "n_gpus": world, "rank_sum": total, "mode": args.mode,
-                          "legs": (["headline"] + ([] if args.no_train_leg else ["train_step", "collective"] if world > 1 else ["train_step"]))
+                          "full": args.full,
+                          "legs": (["headline"] + ([] if args.no_train_leg or not args.full else ["train_step", "collective"] if world > 1 else ["train_step"]))
                                   if args.mode == "infer" else ["train"],
                           "train_bags": args.train_bags, "train_steps": args.train_steps, "train_leg_timeout": args.train_leg_timeout,
                           "dp_variants": [v[0] for v in DP_VARIANTS]}), flush=True)
@@ -526,6 +543,11 @@ def main():
     ap.add_argument("--mode", default="infer", choices=["infer", "train"],
                     help="infer (default, the headline metric) or train: BASELINE configs 4/5, the data-parallel train.py step")
     ap.add_argument("--finetune", action="store_true", help="--mode train: every parameter trainable, train.py:96-97")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel roofline (events in the timed region), the bf16x3 / f32, host-buffer, "
+                         "1 020-clip, CPU-baseline and training-step legs (N = 1), the data-parallel train step (N > 1); the --no-* flags "
+                         "below drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-small-batch", action="store_true", help="skip the 1 020-clip eager / HIP-graph leg")
     ap.add_argument("--no-parity-mode", action="store_true", help="skip the bf16x3 (1e-4-parity arithmetic) leg")
@@ -626,14 +648,16 @@ def infer_mode(args, world, rank, device, ops):
             torch.cuda.synchronize()
         for _ in range(args.warmup):
             out = ens.forward_waveforms(pcm)
-        assert tuple(out.shape) == (args.bags, 10) and bool(torch.isfinite(out).all())
-        # the per-kernel HIP events of the timed region exist before it starts (creating one inside can stall the launching thread)
-        ops.profile = []
-        ens.forward_waveforms(pcm)
-        per_step, ops.profile = len(ops.profile), None
-        ops.reserve_events(2 * per_step * args.steps + 16)
+        if args.warmup:
+            assert tuple(out.shape) == (args.bags, 10) and bool(torch.isfinite(out).all())
+        if args.full:
+            # the per-kernel HIP events of the timed region exist before it starts (creating one inside can stall the launching thread)
+            ops.profile = []
+            ens.forward_waveforms(pcm)
+            per_step, ops.profile = len(ops.profile), None
+            ops.reserve_events(2 * per_step * args.steps + 16)
         barrier()
-        ops.profile = []
+        ops.profile = [] if args.full else None                   # --full: per-kernel events inside the timed region (roofline)
         t0 = time.perf_counter()
         for _ in range(args.steps):
             out = ens.forward_waveforms(pcm)
@@ -641,12 +665,26 @@ def infer_mode(args, world, rank, device, ops):
         elapsed = time.perf_counter() - t0
         prof, ops.profile = ops.profile, None
 
+    if args.dump_outputs:                                         # every rank scores its own shard of bags
+        dump_outputs(args.dump_outputs, {"scores" if world == 1 else "scores_rank%d" % rank: out})
+
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
     if rank == 0:
+        result = {
+            "metric": "0.96 s clips/sec wave->logits (VGGish+attn)", "value": world * clips_per_step * args.steps / elapsed,
+            "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.precision, "data": "synthetic",
+            "config": {"workload": "BASELINE config 3: wave->logits forward, %d bags x 10 s 16 kHz PCM per GPU = %d x 0.96 s clips "
+                                   "per step, VGGish + MLA [2,1], random-init portable-seeded weights; f32 front-end/head, "
+                                   "%s conv+FC" % (args.bags, clips_per_step, args.precision),
+                       "bags_per_gpu": args.bags, "clips_per_step_per_gpu": clips_per_step, "parallelism": "dp%d (no collective: independent bags)" % world},
+        }
+    if rank == 0 and args.full:
         avg = kernel_averages(prof)
         dom = max((k for k in avg if k in CONV_DESC), key=lambda k: avg[k])
         tf = clips_per_step * CONV_MFLOP[dom] * 1e6 / avg[dom] / 1e12
@@ -658,15 +696,7 @@ def infer_mode(args, world, rank, device, ops):
         traffic = load_pmc_traffic()
         t_dom = traffic.get("%s/%s" % (dom, args.precision))
         t_fe = traffic.get("logmel/%s" % ("bf16" if fe_dtype == torch.bfloat16 else "f32"))
-        result = {
-            "metric": "0.96 s clips/sec wave->logits (VGGish+attn)", "value": world * clips_per_step * args.steps / elapsed,
-            "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": "BASELINE config 3: wave->logits forward, %d bags x 10 s 16 kHz PCM per GPU = %d x 0.96 s clips "
-                                   "per step, VGGish + MLA [2,1], random-init portable-seeded weights; f32 front-end/head, "
-                                   "%s conv+FC" % (args.bags, clips_per_step, args.precision),
-                       "bags_per_gpu": args.bags, "clips_per_step_per_gpu": clips_per_step, "parallelism": "dp%d (no collective: independent bags)" % world},
+        result.update({
             "roofline": {"bound": "mfma", "kernel": "conv3x3_kernel %s (%s)" % (dom, CONV_DESC[dom]), "achieved": tf, "peak": peak,
                          "unit": "TFLOP/s", "frac": tf / peak,
                          "traffic": t_dom["bytes_per_clip"] * clips_per_step if t_dom else None,
@@ -683,7 +713,8 @@ def infer_mode(args, world, rank, device, ops):
                                   "traffic": t_fe["bytes_per_clip"] * clips_per_step if t_fe else None,
                                   "issue": frontend_issue_bound(t_fe, clips_per_step, avg["logmel"])},
             "kernel_ms": {k: round(v * 1e3, 4) for k, v in sorted(avg.items())},
-        }
+        })
+
         def leg(name, fn):
             """The additional legs of the N = 1 line never cost the headline line: a failure is reported in place."""
             try:
@@ -720,11 +751,12 @@ def infer_mode(args, world, rank, device, ops):
             del ens, pcm
             torch.cuda.empty_cache()
             leg("train_step", lambda: train_leg(device, bags=args.train_bags))
-        if world == 1 or args.no_train_leg:
-            print(json.dumps(result), flush=True)
+    dp_train = world > 1 and args.full and not args.no_train_leg
+    if rank == 0 and not dp_train:
+        print(json.dumps(result), flush=True)
     if world > 1:
-        if not args.no_train_leg:
-            # BASELINE config 5 in the line the driver's scaling run produces: every rank runs the data-parallel train step
+        if dp_train:
+            # --full at N > 1: BASELINE config 5 after the headline, every rank runs the data-parallel train step
             state = {"printed": False}
             ens = pcm = None
             torch.cuda.empty_cache()

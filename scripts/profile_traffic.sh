@@ -2,25 +2,29 @@
 # HBM traffic per launch of the pipeline's kernels from rocprofv3 PMC counters, collected as MI355X_MICROARCH.md prescribes:
 # FETCH_SIZE and WRITE_SIZE in SEPARATE --pmc passes (TCC has 4 slots: FETCH_SIZE costs 3, WRITE_SIZE 2), --kernel-trace only;
 # corrections for gfx950: FETCH_SIZE (KB) counts 64 B per 128-B request of a wide coalesced read -> x2; WRITE_SIZE (KB) as read.
-# Writes profiles-style JSON (bytes per clip per kernel) to gpurun_out/pmc_traffic.json; copy to profiles/rNN_pmc_traffic.json (bench.py reads the newest).
+# Writes profiles-style JSON (bytes per clip per kernel) to $OUT/pmc_traffic.json; copy to profiles/rNN_pmc_traffic.json (bench.py --full reads the newest).
 set -e
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
+OUT=${OUT:-$R/profile_out}     # results folder (OUT=<dir> to change it)
+export OUT
+mkdir -p "$OUT"
 cd /tmp
 B="python3 $R/bench.py --steps 3 --warmup 1 --prewarm-seconds 0 --no-cpu-baseline --no-small-batch --no-parity-mode --no-h2d --no-train-leg"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/traffic_fetch -- $B > /dev/null 2>$R/gpurun_out/traffic_fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/traffic_write -- $B > /dev/null 2>$R/gpurun_out/traffic_write.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/traffic_fetch" -- $B > /dev/null 2>"$OUT/traffic_fetch.err"
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/traffic_write" -- $B > /dev/null 2>"$OUT/traffic_write.err"
 # third pass: what actually binds the log-mel kernel -- vector instructions issued and LDS-array cycles (bench.py: roofline_frontend.issue)
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $R/gpurun_out/traffic_issue -- $B > /dev/null 2>$R/gpurun_out/traffic_issue.err
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OUT/traffic_issue" -- $B > /dev/null 2>"$OUT/traffic_issue.err"
 cd $R
 python3 - <<'P'
-import collections, csv, glob, json, re
+import collections, csv, glob, json, os, re
+OUT = os.environ["OUT"]
 CLIPS = 10240
 NAMES = {"Cfg<bf16, 64, 128, 48, 32, true, ": "conv2", "Cfg<bf16, 128, 256, 24, 16, false, 4": "conv3", "Cfg<bf16, 256, 256, 24, 16, true, 4": "conv4",
          "Cfg<bf16, 256, 512, 12, 8, false, 4": "conv5", "Cfg<bf16, 512, 512, 12, 8, true, 4": "conv6"}
 def collect(d, counter):
     acc = collections.defaultdict(list)
-    for f in glob.glob("gpurun_out/%s/**/*counter_collection.csv" % d, recursive=True):
+    for f in glob.glob("%s/%s/**/*counter_collection.csv" % (OUT, d), recursive=True):
         for r in csv.DictReader(open(f)):
             if r["Counter_Name"] != counter:
                 continue
@@ -43,7 +47,7 @@ issue = {}
 for name in ("SQ_INSTS_VALU", "SQ_INSTS_LDS", "SQ_LDS_IDX_ACTIVE", "SQ_LDS_BANK_CONFLICT", "SQ_INSTS_SALU", "GRBM_GUI_ACTIVE"):
     issue[name] = collect("traffic_issue", name)
 dur = collections.defaultdict(list)
-for f in glob.glob("gpurun_out/traffic_issue/**/*kernel_trace.csv", recursive=True):
+for f in glob.glob(OUT + "/traffic_issue/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         if "logmel" in r["Kernel_Name"]:
             dur["logmel"].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
@@ -58,7 +62,7 @@ for k in [k for k in out if k.startswith("logmel/")]:
                            "launch_us_while_profiled": us,
                            "source": "rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU GRBM_GUI_ACTIVE "
                                      "(one pass, --kernel-trace only), scripts/profile_traffic.sh; wave-instructions / LDS-array cycles summed over the chip"}
-json.dump(out, open("gpurun_out/pmc_traffic.json", "w"), indent=1)
+json.dump(out, open(OUT + "/pmc_traffic.json", "w"), indent=1)
 for k, v in out.items():
     print(k, "read %.4g B write %.4g B per launch -> %.0f B per clip" % (v["read_bytes_per_launch"], v["write_bytes_per_launch"], v["bytes_per_clip"]))
 P

@@ -1,6 +1,6 @@
 """GPU test of the bench contract: `python bench.py` at a reduced batch prints ONE JSON line with the fields the driver parses
-(metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling / dtype / config.workload, `roofline` and `cpu_baseline`),
-with internally consistent numbers. The full-size numbers live in profiles/; this checks the plumbing, including the self-launched
+(metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling / dtype / config.workload; with --full also `roofline`
+and `cpu_baseline`), with internally consistent numbers, and --dump-outputs writes what the last timed step computed. The full-size numbers live in profiles/; this checks the plumbing, including the self-launched
 two-rank path (gloo rehearsal on one GPU: the N > 1 branch of the timing code)."""
 
 import json
@@ -26,7 +26,8 @@ def run_bench(*args):
 
 
 def test_one_gpu_line_has_the_contract_fields_and_consistent_numbers():
-    d = run_bench("--bags", "64", "--steps", "3", "--warmup", "1", "--prewarm-seconds", "0.2", "--no-small-batch", "--no-h2d", "--no-train-leg")
+    d = run_bench("--full", "--bags", "64", "--steps", "3", "--warmup", "1", "--prewarm-seconds", "0.2", "--no-small-batch", "--no-h2d",
+                  "--no-train-leg")
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "clips/s" and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["dtype"] == "bf16" and d["data"] == "synthetic" and d["vs_baseline"] is None
     assert "workload" in d["config"] and "model" not in d["config"]
@@ -49,10 +50,35 @@ def test_one_gpu_line_has_the_contract_fields_and_consistent_numbers():
     assert abs(i["valu_bound_ms"] - i["valu_insts_per_clip"] * clips * 2 / (1024 * 2.4e9) * 1e3) < 1e-9
 
 
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline fields only; --dump-outputs writes the scores of the last timed step, the
+    same numbers this process gets from the same seeded weights and waveforms."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    d = run_bench("--bags", "16", "--steps", "2", "--warmup", "1", "--prewarm-seconds", "0.2", "--dump-outputs", str(out))
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "clips/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["config"]["clips_per_step_per_gpu"] == 160
+    assert abs(d["value"] - 160 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "roofline_conv_stack", "roofline_frontend", "kernel_ms", "parity_mode", "h2d", "small_batch", "cpu_baseline",
+              "value_at_tolerance", "train_step"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["scores.npy"]
+    got = np.load(out / "scores.npy")
+    assert got.shape == (16, 10) and got.dtype == np.float32 and np.isfinite(got).all()
+    dev = torch.device("cuda", 0)
+    ens, _ = bench.build_model("bf16", dev)
+    with torch.no_grad():
+        ref = ens.forward_waveforms(bench.synth_pcm(16, 0, dev)).float().cpu().numpy()
+    assert np.array_equal(got, ref)                 # the forward is deterministic (tests/test_model_gpu.py)
+
+
 def test_two_self_launched_ranks_report_the_aggregate_and_the_data_parallel_train_step():
-    """`python bench.py --gpus 2` (the driver's scaling invocation; gloo here, two ranks sharing the test GPU): the inference
-    headline AND BASELINE config 5's data-parallel train step with the evidence of its collectives."""
-    d = run_bench("--gpus", "2", "--backend", "gloo", "--bags", "32", "--steps", "2", "--warmup", "1", "--prewarm-seconds", "0.2",
+    """`python bench.py --gpus 2 --full` (gloo here, two ranks sharing the test GPU): the inference headline AND BASELINE
+    config 5's data-parallel train step with the evidence of its collectives."""
+    d = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--bags", "32", "--steps", "2", "--warmup", "1", "--prewarm-seconds", "0.2",
                   "--train-bags", "32", "--train-steps", "2")
     assert d["n_gpus"] == 2 and d["config"]["clips_per_step_per_gpu"] == 320
     assert abs(d["value"] - 2 * 320 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]       # whole-job rate over max-over-ranks time

@@ -31,21 +31,29 @@ def test_self_launch_two_ranks_prints_one_line():
     assert d["n_gpus"] == 2 and d["rank_sum"] == 1.0          # ranks 0 + 1 took part in the all-reduce
 
 
-def test_default_line_at_n_gt_1_carries_the_data_parallel_train_step():
-    """The driver's scaling run is `python bench.py --gpus N` with no mode flag: at N > 1 that line must hold the inference headline
-    AND the data-parallel train step (BASELINE config 5) with its collective section; flags reach the ranks."""
+def test_full_line_at_n_gt_1_carries_the_data_parallel_train_step():
+    """`python bench.py --gpus N --full` with no mode flag: at N > 1 that line must hold the inference headline AND the
+    data-parallel train step (BASELINE config 5) with its collective section; flags reach the ranks. A plain run (no --full)
+    is the headline alone, at any N."""
     rc, lines, err = _run("--gpus", "2", "--dry-run", "--backend", "gloo")
     assert rc == 0, err
     d = json.loads(lines[0])
-    assert d["legs"] == ["headline", "train_step", "collective"] and d["train_bags"] == 512
+    assert d["legs"] == ["headline"] and d["full"] is False
+    rc, lines, err = _run("--gpus", "2", "--dry-run", "--backend", "gloo", "--full")
+    assert rc == 0, err
+    d = json.loads(lines[0])
+    assert d["legs"] == ["headline", "train_step", "collective"] and d["train_bags"] == 512 and d["full"] is True
     assert d["dp_variants"] == ["frozen_bf16", "frozen_bf16_per_shard_bn", "finetune_bf16"]
-    rc, lines, err = _run("--gpus", "2", "--dry-run", "--backend", "gloo", "--train-bags", "32", "--train-steps", "3", "--train-leg-timeout", "99")
+    rc, lines, err = _run("--gpus", "2", "--dry-run", "--backend", "gloo", "--full", "--train-bags", "32", "--train-steps", "3",
+                          "--train-leg-timeout", "99")
     d = json.loads(lines[0])
     assert (d["train_bags"], d["train_steps"], d["train_leg_timeout"]) == (32, 3, 99)
-    rc, lines, err = _run("--gpus", "2", "--dry-run", "--backend", "gloo", "--no-train-leg")
+    rc, lines, err = _run("--gpus", "2", "--dry-run", "--backend", "gloo", "--full", "--no-train-leg")
     assert json.loads(lines[0])["legs"] == ["headline"]
-    rc, lines, err = _run("--dry-run")
+    rc, lines, err = _run("--dry-run", "--full")
     assert json.loads(lines[0])["legs"] == ["headline", "train_step"]
+    rc, lines, err = _run("--dry-run")
+    assert json.loads(lines[0])["legs"] == ["headline"]
 
 
 def test_watchdog_prints_what_it_has_and_leaves(tmp_path):
