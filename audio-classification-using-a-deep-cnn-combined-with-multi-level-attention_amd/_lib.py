@@ -124,6 +124,16 @@ def lib():
         L.mla_comm_count.argtypes = [vp, ctypes.POINTER(ci)]
         L.mla_comm_library_origin.restype = ctypes.c_char_p
         L.mla_allreduce_flat.argtypes = [vp, i64, ci, vp, vp]
+        L.mla_rn_repack.argtypes = [vp, i64, i64, i64, vp, ci, vp]
+        L.mla_rn_stem.argtypes = [vp, i64, i64, i64, ci, vp, vp, vp, ci, vp, ci, vp]
+        L.mla_rn_conv.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, ci, vp, ci, vp]
+        L.mla_rn_bn_workspace_bytes.restype = i64
+        L.mla_rn_bn_workspace_bytes.argtypes = [i64]
+        L.mla_rn_bn_stats.argtypes = [vp, i64, i64, ci, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, vp]
+        L.mla_rn_bn_eval_coeffs.argtypes = [vp, vp, vp, vp, cf, i64, vp, vp, vp]
+        L.mla_rn_bn_apply.argtypes = [vp, i64, i64, vp, vp, vp, ci, vp, ci, vp]
+        L.mla_rn_maxpool.argtypes = [vp, i64, i64, i64, i64, vp, ci, vp]
+        L.mla_rn_avgpool.argtypes = [vp, i64, i64, i64, vp, ci, vp]
         _lib = L
     return _lib
 

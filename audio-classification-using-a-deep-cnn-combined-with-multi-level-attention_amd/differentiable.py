@@ -87,6 +87,25 @@ class EmbeddingsFn(torch.autograd.Function):
         return (None, None, d) + tuple(grads.get(n) for n, _ in ctx.names)
 
 
+class FcFn(torch.autograd.Function):
+    """apply(feats, w, b): ResNet.fc (model.py:148-149) on f32 (N, 2048) features of the frozen trunk -> (N, num_classes); the
+    backward returns the weight / bias gradients (the trunk below takes none)."""
+
+    @staticmethod
+    def forward(ctx, feats, w, b):
+        feats = feats.detach().contiguous()
+        ctx.save_for_backward(feats, w, b)
+        return ops.linear_small(feats, w.detach().contiguous(), b.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, dz):
+        feats, w, b = ctx.saved_tensors
+        dw = torch.empty(w.shape, dtype=torch.float32, device=dz.device)
+        db = torch.empty(b.shape, dtype=torch.float32, device=dz.device)
+        ops.linear_small_bwd(feats, w.detach().contiguous(), dz.float().contiguous(), dw, db)
+        return None, (dw if ctx.needs_input_grad[1] else None), (db if ctx.needs_input_grad[2] else None)
+
+
 class CastFn(torch.autograd.Function):
     """bf16 bottlenecks (just_bottlenecks=True) -> the float32 features the head takes; the gradient goes back in bf16."""
 

@@ -39,7 +39,10 @@ def embedded_mapping_forward(em, x, ctx=None):
     if ctx.tape is not None:
         ctx.tape.append(("norm0", em, rows, mean, var))
     for j in range(em.n_fc):
-        z = ops.linear(h, em.fc[j].weight.detach(), em.fc[j].bias.detach())
+        if h.shape[1] % 4:      # narrow input (ResNet fc width, e.g. 10): rows are not 16-byte aligned for the MFMA GEMM
+            z = ops.linear_small(h, em.fc[j].weight.detach().contiguous(), em.fc[j].bias.detach().contiguous())
+        else:
+            z = ops.linear(h, em.fc[j].weight.detach(), em.fc[j].bias.detach())
         mean, var = _bn_stats(em.norms[j], z, 0, T, train, ctx)
         if train and ctx.counter is not None:
             d = em.dropouts[j]
@@ -102,6 +105,11 @@ def mla_apply(mla, x):
 def _linear_backward(x_in, weight, dz, g_w, g_b, want_dx):
     """out = x_in W^T + b: dW = dz^T x_in, db = column sums, dx = dz W -- MFMA GEMMs on transposed,
     K-contiguous copies (reduction over rows for dW, over out-features for dx). g_w / g_b None: that gradient is not wanted."""
+    if x_in.shape[1] % 4:                                      # narrow input (see embedded_mapping_forward): the small-Linear backward
+        g_w = g_w if g_w is not None else torch.empty(weight.shape, dtype=torch.float32, device=dz.device)
+        g_b = g_b if g_b is not None else torch.empty(weight.shape[0], dtype=torch.float32, device=dz.device)
+        dx = ops.linear_small_bwd(x_in.contiguous(), weight.contiguous(), dz.contiguous(), g_w, g_b)
+        return dx if want_dx else None
     if g_w is not None:
         dzT = ops.transpose_padded(dz)                         # (N, M~)
         xT = ops.transpose_padded(x_in)                        # (Kin, M~)

@@ -6,8 +6,8 @@ keys (model.py:14, :68, :107, :179, :202, :228, :248, :272), executed by HIP ker
 Reproduced on purpose (SURVEY.md section 7 "quirks"): ``fcv`` feeds both attention branches
 and ``fcf`` is a dead parameter (model.py:230-238); BatchNorm1d(T) treats the time slot as
 channel; the outputs are sigmoids that train.py feeds to CrossEntropyLoss; ``Input`` is a
-reshape, never a transpose (model.py:98-99). The ``resnet`` branches are outside the hot path
- and raise.
+reshape, never a transpose (model.py:98-99). The ``resnet`` branch (model.py:128-149) runs a frozen
+ResNet-50 trunk on HIP kernels (``resnet.py``); its BatchNorm layers follow train / eval mode.
 """
 
 from typing import Dict, List, Union
@@ -15,7 +15,7 @@ from typing import Dict, List, Union
 import torch
 from torch import nn
 
-from . import differentiable, mla_train, ops
+from . import differentiable, mla_train, ops, resnet
 from .params import *  # noqa: F401,F403  (T, H, K, DR, M_VGGISH, M_VGGISH_JB, S_VGGISH_SHAPE: model.py:9)
 from .torchvggish.vggish import Linear, VGGish
 
@@ -81,8 +81,10 @@ class Ensemble(nn.Module):
             self.emb_input_size = M_VGGISH_JB
         elif self.cnn_type == "vggish" and not self.just_bottlenecks:
             self.emb_input_size = M_VGGISH
-        elif self.cnn_type == "resnet":
-            raise Exception("cnn_type 'resnet' is outside the MI355X hot path (torchvision ResNet-50); use 'vggish'.")
+        elif self.cnn_type == "resnet" and self.just_bottlenecks:
+            self.emb_input_size = M_RESNET
+        elif self.cnn_type == "resnet" and not self.just_bottlenecks:
+            self.emb_input_size = self.num_classes
         else:
             raise Exception("CNN type is not valid.")
         self.input = Input(input_conf=input_conf, cnn_type=self.cnn_type, device=device)
@@ -99,10 +101,16 @@ class Ensemble(nn.Module):
         out = self.mla(features.reshape(-1, T, self.emb_input_size))
         return out
 
+    def _waveforms_only_vggish(self):
+        if self.cnn_type != "vggish":
+            raise NotImplementedError("the waveform paths feed VGGish log-mel examples; cnn_type 'resnet' takes 224 x 224 "
+                                      "spectrogram images (dataset.py:175-178 of the reference) through forward()")
+
     def forward_waveforms(self, pcm):
         """Fused online path of the north star: (B, n_samples) 16 kHz PCM on the device (float32
         or int16), one bag per row with exactly T examples -> (B, K) scores. The front-end writes
         the examples directly in the CNN's compute dtype."""
+        self._waveforms_only_vggish()
         from . import frontend
         dtype = torch.bfloat16 if self.cnn.precision == "bf16" else torch.float32
         ex = frontend.waveforms_to_examples(pcm, out_dtype=dtype)
@@ -115,6 +123,7 @@ class Ensemble(nn.Module):
         (B, K) scores of each. The copy of batch i+1 runs on its own HIP stream while batch i computes (two device
         buffers), so a steady stream is bound by max(copy, compute), not their sum. Scores are yielded after the batch's
         compute has been enqueued; they are ordinary tensors on the current stream."""
+        self._waveforms_only_vggish()
         dev = next(self.parameters()).device
         cur = torch.cuda.current_stream(dev)
         copy = torch.cuda.Stream(device=dev)
@@ -143,6 +152,7 @@ class Ensemble(nn.Module):
         """Capture forward_waveforms for inputs shaped like `pcm` into a HIP graph (eval mode only) and return a
         callable that replays it: ~45 kernel launches per step become one graph launch, which is what small
         batches (about 1 000 clips, where a step is ~1.5 ms of GPU work) need."""
+        self._waveforms_only_vggish()
         return GraphedWaveforms(self, pcm)
 
 
@@ -182,7 +192,16 @@ class Input(nn.Module):
         if self.cnn_type == "vggish":
             return x.reshape((-1, 1, S_VGGISH_SHAPE[0], S_VGGISH_SHAPE[1]))
         elif self.cnn_type == "resnet":
-            raise Exception("cnn_type 'resnet' is outside the MI355X hot path.")
+            # model.py:84-99: repeat / single channels, ImageNet normalisation and the (-1, 3, 224, 224) reshape all happen in
+            # the stem kernel, which needs the raw planes (the conv's zero padding applies to the normalised channels)
+            if self.conf not in ("repeat", "single"):
+                raise Exception("Invalid input type")
+            if x.dim() != 5 or x.shape[2] != 1 or tuple(x.shape[3:]) != S_RESNET_SHAPE:
+                raise ValueError("cnn_type 'resnet' takes (B, T, 1, %d, %d) inputs, got %s" % (S_RESNET_SHAPE + (tuple(x.shape),)))
+            planes = x.detach().reshape(-1, S_RESNET_SHAPE[0], S_RESNET_SHAPE[1])
+            if planes.dtype != torch.float32 or not planes.is_contiguous():
+                planes = planes.float().contiguous()
+            return resnet.StemInput(planes, self.conf == "single")
         else:
             raise Exception("CNN type is not valid.")
 
@@ -201,11 +220,31 @@ class CNN(nn.Module):
             if just_bottlenecks:
                 self.cnn_model = nn.Sequential(list(self.cnn_model.children())[0], CnnFlatten(cnn_type))
         elif cnn_type == "resnet":
-            raise Exception("cnn_type 'resnet' is outside the MI355X hot path (torchvision ResNet-50); use 'vggish'.")
+            if precision not in ("f32", "bf16"):
+                raise NotImplementedError("cnn_type 'resnet' runs in precision 'f32' or 'bf16', not %r" % precision)
+            self.cnn_model = resnet.resnet50(pretrained=use_pretrained)
+            if not cnn_trainable:
+                set_requires_grad(self.cnn_model, False)
+            if first_cnn_layer_trainable:
+                if in_channels == 3:
+                    set_requires_grad(self.cnn_model.conv1, True)
+                else:
+                    self.cnn_model.conv1 = resnet.Conv2d(in_channels, 64, 7, stride=2, padding=3)
+            if just_bottlenecks:
+                modules = list(self.cnn_model.children())[:-1]       # model.py:142-146: drop fc, flatten
+                modules.append(CnnFlatten(cnn_type))
+                self.cnn_model = nn.Sequential(*modules)
+            else:
+                self.cnn_model.fc = resnet.Linear(self.cnn_model.fc.in_features, num_classes)   # after the freeze: trainable
+            self._rn_cache = resnet.new_cache()
         else:
             raise Exception("Invalid CNN model name specified.")
+        self.cnn_type = cnn_type
+        self.just_bottlenecks = just_bottlenecks
 
     def set_precision(self, precision):
+        if self.cnn_type == "resnet" and precision not in ("f32", "bf16"):
+            raise NotImplementedError("cnn_type 'resnet' runs in precision 'f32' or 'bf16', not %r" % precision)
         self.precision = precision
         for m in self.cnn_model.modules():
             if hasattr(m, "precision"):
@@ -213,6 +252,9 @@ class CNN(nn.Module):
         return self
 
     def forward(self, x):
+        if self.cnn_type == "resnet":
+            feats = resnet.trunk_forward(self.cnn_model, x, self.precision, self.training, self._rn_cache)
+            return feats if self.just_bottlenecks else resnet.fc_forward(self.cnn_model.fc, feats)
         x = self.cnn_model(x)
         if x.dtype == torch.bfloat16:      # bf16 bottlenecks (just_bottlenecks=True) feed the f32 head
             if x.requires_grad:
@@ -227,7 +269,9 @@ class CnnFlatten(nn.Module):
         self.cnn_type = cnn_type
 
     def forward(self, x):
-        if self.cnn_type == "vggish":
+        if self.cnn_type == "resnet":
+            x = torch.flatten(x, 1)
+        elif self.cnn_type == "vggish":
             x = torch.transpose(x, 1, 3)
             x = torch.transpose(x, 1, 2)
             x = x.contiguous()           # no copy: VGGFeatures returns an NCHW view of NHWC memory

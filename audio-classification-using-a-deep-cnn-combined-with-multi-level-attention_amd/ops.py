@@ -704,3 +704,108 @@ def conv1_bwd(x, w, b, d_pooled, dw, db):
     ws = torch.empty(int(_lib.lib().mla_conv1_bwd_workspace_floats()), dtype=torch.float32, device=x.device)
     fn = _lib.lib().mla_conv1_bwd_bf16 if d_pooled.dtype == torch.bfloat16 else _lib.lib().mla_conv1_bwd
     _lib.check(_timed("conv1_bwd", fn, _p(x), _p(w), _p(b), _p(d_pooled), n, _p(ws), _p(dw), _p(db), _lib.stream_ptr()))
+
+
+# ---- ResNet-50 trunk (cnn_type="resnet"): NHWC activations in f32 / bf16, see include/mla_hip.h "ResNet-50 v1.5 trunk" ----
+
+def rn_repack(w, dtype):
+    """Conv2d weight (O, I, k, k) f32 -> (O, k, k, I) in `dtype`."""
+    _chk(w, torch.float32)
+    cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
+    out = torch.empty((cout, ks, ks, cin), dtype=dtype, device=w.device)
+    _lib.check(_lib.lib().mla_rn_repack(_p(w), cout, cin, ks, _p(out), DT[dtype], _lib.stream_ptr()))
+    return out
+
+
+def rn_stem(planes, single, w, dtype, scale=None, shift=None, relu=False):
+    """(N, 224, 224) f32 planes -> NHWC (N, 112, 112, 64): Input normalisation + conv1 [+ eval bn1 + ReLU]."""
+    _chk(planes, torch.float32); _chk(w, torch.float32)
+    assert planes.dim() == 3, planes.shape
+    n, H, W_ = planes.shape
+    out = torch.empty((n, 112, 112, 64), dtype=dtype, device=planes.device)
+    _lib.check(_timed("rn_stem", _lib.lib().mla_rn_stem, _p(planes), n, H, W_, int(single), _p(w), _p(scale), _p(shift), int(relu), _p(out),
+                      DT[dtype], _lib.stream_ptr()))
+    return out
+
+
+def rn_conv(x, w_packed, stride, scale=None, shift=None, residual=None, relu=False):
+    """NHWC x (N, H, W, Cin), packed weight (Cout, k, k, Cin) -> (N, Ho, Wo, Cout) [* scale + shift] [+ residual] [ReLU]."""
+    _chk(x); _chk(w_packed, x.dtype)
+    n, H, W_, cin = x.shape
+    cout, ks = w_packed.shape[0], w_packed.shape[1]
+    pad = ks // 2
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W_ + 2 * pad - ks) // stride + 1
+    out = torch.empty((n, Ho, Wo, cout), dtype=x.dtype, device=x.device)
+    if residual is not None:
+        _chk(residual, x.dtype)
+        assert residual.shape == out.shape, (residual.shape, out.shape)
+    _lib.check(_timed("rn_conv%dx%d" % (ks, ks), _lib.lib().mla_rn_conv, _p(x), n, H, W_, cin, _p(w_packed), cout, ks, stride,
+                      _p(scale), _p(shift), _p(residual), int(relu), _p(out), DT[x.dtype], _lib.stream_ptr()))
+    return out
+
+
+def _rn_workspace(device, channels):
+    key = ("rn_bn", str(device))
+    need = int(_lib.lib().mla_rn_bn_workspace_bytes(channels)) // 8
+    if key not in _ws or _ws[key].numel() < need:
+        _ws[key] = torch.empty(need, dtype=torch.float64, device=device)
+    return _ws[key]
+
+
+def rn_bn_stats(x, bn, running=True, want_stats=False):
+    """Train-mode BatchNorm2d statistics of NHWC x: returns (scale, shift[, mean, var_biased]); updates bn's running
+    statistics (and num_batches_tracked) when `running`."""
+    _chk(x)
+    C = x.shape[-1]
+    rows = x.numel() // C
+    dev = x.device
+    scale = torch.empty(C, dtype=torch.float32, device=dev)
+    shift = torch.empty(C, dtype=torch.float32, device=dev)
+    mean = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
+    var = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
+    rm, rv = (bn.running_mean, bn.running_var) if running else (None, None)
+    _lib.check(_timed("rn_bn_stats", _lib.lib().mla_rn_bn_stats, _p(x), rows, C, DT[x.dtype], _p(_rn_workspace(dev, C)),
+                      _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps), float(bn.momentum), _p(rm), _p(rv),
+                      _p(mean), _p(var), _p(scale), _p(shift), _lib.stream_ptr()))
+    if running:
+        _lib.check(_lib.lib().mla_counter_add(_p(bn.num_batches_tracked), 1, _lib.stream_ptr()))
+    return (scale, shift, mean, var) if want_stats else (scale, shift)
+
+
+def rn_bn_eval_coeffs(bn):
+    C = bn.num_features
+    dev = bn.weight.device
+    scale = torch.empty(C, dtype=torch.float32, device=dev)
+    shift = torch.empty(C, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().mla_rn_bn_eval_coeffs(_p(bn.weight.detach()), _p(bn.bias.detach()), _p(bn.running_mean), _p(bn.running_var),
+                                                float(bn.eps), C, _p(scale), _p(shift), _lib.stream_ptr()))
+    return scale, shift
+
+
+def rn_bn_apply(x, scale, shift, residual=None, relu=False, out=None):
+    _chk(x)
+    C = x.shape[-1]
+    out = x if out is None else out
+    if residual is not None:
+        _chk(residual, x.dtype)
+        assert residual.shape == x.shape
+    _lib.check(_timed("rn_bn_apply", _lib.lib().mla_rn_bn_apply, _p(x), x.numel() // C, C, _p(scale), _p(shift), _p(residual), int(relu),
+                      _p(out), DT[x.dtype], _lib.stream_ptr()))
+    return out
+
+
+def rn_maxpool(x):
+    _chk(x)
+    n, H, W_, C = x.shape
+    out = torch.empty((n, (H - 1) // 2 + 1, (W_ - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
+    _lib.check(_timed("rn_maxpool", _lib.lib().mla_rn_maxpool, _p(x), n, H, W_, C, _p(out), DT[x.dtype], _lib.stream_ptr()))
+    return out
+
+
+def rn_avgpool(x):
+    """NHWC (N, H, W, C) -> f32 (N, C)."""
+    _chk(x)
+    n, H, W_, C = x.shape
+    out = torch.empty((n, C), dtype=torch.float32, device=x.device)
+    _lib.check(_timed("rn_avgpool", _lib.lib().mla_rn_avgpool, _p(x), n, H * W_, C, _p(out), DT[x.dtype], _lib.stream_ptr()))
+    return out

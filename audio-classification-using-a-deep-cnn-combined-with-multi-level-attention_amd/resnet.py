@@ -1,0 +1,220 @@
+"""ResNet-50 v1.5 (torchvision ``resnet50``, as the reference builds it in ``model.py:128-149``) with torchvision's
+attribute names, child order and parameter shapes, so that the reference's ``state_dict`` keys -- both the
+``nn.Sequential(*children()[:-1], CnnFlatten)`` numbering of ``just_bottlenecks=True`` and the named keys of
+``just_bottlenecks=False`` -- load unchanged.
+
+The modules are parameter holders; ``trunk_forward`` runs the whole trunk as HIP kernels (``csrc/resnet.hip``) on NHWC
+activations in the compute dtype: eval mode with the BatchNorm folded into the conv epilogues as an f32 scale/shift from
+the running statistics, train mode (the frozen trunk stays in train mode, ``set_requires_grad`` does not call ``eval``)
+with batch statistics and the running-statistics update. Gradients into the trunk are not built and raise; the ``fc``
+of ``just_bottlenecks=False`` (trainable in the reference) is differentiable (``fc_forward``).
+"""
+
+import math
+
+import torch
+from torch import nn
+
+from . import ops
+from .params import S_RESNET_SHAPE
+from .torchvggish.vggish import _Cache
+
+_DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
+
+
+class Conv2d(nn.Module):
+    """Parameter holder with nn.Conv2d's names and default initialisation (bias=False, as every conv of ResNet-50)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=False):
+        super().__init__()
+        assert not bias
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride, self.padding = (kernel_size, kernel_size), (stride, stride), (padding, padding)
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+
+    def forward(self, x):
+        raise RuntimeError("Conv2d is executed by the HIP ResNet trunk of its parent module")
+
+
+class BatchNorm2d(nn.Module):
+    """Parameter / buffer holder with torch.nn.BatchNorm2d's names, eps 1e-5, momentum 0.1."""
+
+    def __init__(self, num_features):
+        super().__init__()
+        self.num_features, self.eps, self.momentum = num_features, 1e-5, 0.1
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+
+    def forward(self, x):
+        raise RuntimeError("BatchNorm2d is executed by the HIP ResNet trunk of its parent module")
+
+
+class _Fused(nn.Module):
+    """Parameterless torchvision child (ReLU, MaxPool2d, AdaptiveAvgPool2d): it only holds its place in the child order."""
+
+    def forward(self, x):
+        raise RuntimeError("%s is fused into the HIP ResNet trunk" % type(self).__name__)
+
+
+class ReLU(_Fused):
+    pass
+
+
+class MaxPool2d(_Fused):
+    pass
+
+
+class AdaptiveAvgPool2d(_Fused):
+    pass
+
+
+class Linear(nn.Module):
+    """nn.Linear parameter holder (ResNet.fc)."""
+
+    def __init__(self, in_features, out_features):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.empty(out_features, in_features))
+        self.bias = nn.Parameter(torch.empty(out_features))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(in_features)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x):
+        raise RuntimeError("Linear is executed by its container")
+
+
+class Bottleneck(nn.Module):
+    """torchvision v1.5 Bottleneck: the stride sits on the 3x3 conv2."""
+
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = Conv2d(inplanes, planes, 1)
+        self.bn1 = BatchNorm2d(planes)
+        self.conv2 = Conv2d(planes, planes, 3, stride=stride, padding=1)
+        self.bn2 = BatchNorm2d(planes)
+        self.conv3 = Conv2d(planes, planes * 4, 1)
+        self.bn3 = BatchNorm2d(planes * 4)
+        self.relu = ReLU()
+        self.downsample = downsample
+        self.stride = stride
+
+
+class ResNet(nn.Module):
+    """torchvision ResNet-50: children conv1, bn1, relu, maxpool, layer1..layer4, avgpool, fc (in that order)."""
+
+    def __init__(self, layers=(3, 4, 6, 3), num_classes=1000):
+        super().__init__()
+        self.conv1 = Conv2d(3, 64, 7, stride=2, padding=3)
+        self.bn1 = BatchNorm2d(64)
+        self.relu = ReLU()
+        self.maxpool = MaxPool2d()
+        inplanes = 64
+        for i, (planes, n, stride) in enumerate(zip((64, 128, 256, 512), layers, (1, 2, 2, 2))):
+            ds = nn.Sequential(Conv2d(inplanes, planes * 4, 1, stride=stride), BatchNorm2d(planes * 4))
+            blocks = [Bottleneck(inplanes, planes, stride, ds)] + [Bottleneck(planes * 4, planes) for _ in range(n - 1)]
+            inplanes = planes * 4
+            setattr(self, "layer%d" % (i + 1), nn.Sequential(*blocks))
+        self.avgpool = AdaptiveAvgPool2d()
+        self.fc = Linear(2048, num_classes)
+
+
+def resnet50(pretrained=False, **kwargs):
+    """torchvision.models.resnet50 stand-in: weights arrive through load_state_dict (no download here)."""
+    if pretrained:
+        raise Exception("pretrained ResNet-50 weights are not downloaded here: use pretrained=False and load_state_dict instead")
+    return ResNet(**kwargs)
+
+
+class StemInput:
+    """What ``Input.forward`` hands to the ResNet trunk: the raw (N, 224, 224) f32 planes and the channel configuration
+    (``single``: x in channel 0 only). The normalisation happens inside the stem kernel (model.py:84-94)."""
+
+    def __init__(self, planes, single):
+        self.planes, self.single = planes, single
+
+
+def parts(cnn_model):
+    """(conv1, bn1, [layer1..layer4], fc or None) of a ResNet or of the just_bottlenecks Sequential of its children."""
+    if isinstance(cnn_model, ResNet):
+        m = cnn_model
+        return m.conv1, m.bn1, [m.layer1, m.layer2, m.layer3, m.layer4], m.fc
+    kids = list(cnn_model.children())
+    return kids[0], kids[1], kids[4:8], None
+
+
+def _check_frozen(cnn_model):
+    if not torch.is_grad_enabled():
+        return
+    for name, p in cnn_model.named_parameters():
+        if p.requires_grad and not name.startswith("fc."):      # fc (just_bottlenecks=False) is trained: fc_forward
+            raise NotImplementedError("gradients into the ResNet trunk are not built (parameter cnn.cnn_model.%s requires grad); "
+                                      "train with cnn_trainable=False / first_cnn_layer_trainable=False" % name)
+
+
+def trunk_forward(cnn_model, x, precision, training, cache):
+    """StemInput -> f32 (N, 2048) bottleneck features (avgpool + flatten) of the HIP trunk."""
+    if not isinstance(x, StemInput):
+        raise TypeError("the ResNet trunk takes the output of model.Input (raw 224 x 224 planes)")
+    if precision not in _DTYPES:
+        raise NotImplementedError("the ResNet trunk is built for precision 'f32' and 'bf16', not %r" % precision)
+    conv1, bn1, layers, _ = parts(cnn_model)
+    if conv1.weight.shape != (64, 3, 7, 7):
+        raise NotImplementedError("the ResNet stem kernel takes the 3-channel conv1 (in_channels=3)")
+    planes = x.planes
+    assert planes.dim() == 3 and tuple(planes.shape[1:]) == S_RESNET_SHAPE
+    _check_frozen(cnn_model)
+    dtype = _DTYPES[precision]
+    blocks = [b for layer in layers for b in layer]
+    convs = [c for b in blocks for c in ([b.conv1, b.conv2, b.conv3] + ([b.downsample[0]] if b.downsample is not None else []))]
+    packed = cache["w"].get([c.weight for c in convs], dtype,
+                            lambda: {id(c): ops.rn_repack(c.weight.detach().contiguous(), dtype) for c in convs})
+    w1 = conv1.weight.detach().contiguous()
+    if training:
+        cache["bn"].key = None                    # the running statistics change below, behind torch's version counters
+        h = ops.rn_stem(planes, x.single, w1, dtype)
+        ops.rn_bn_apply(h, *ops.rn_bn_stats(h, bn1), relu=True)
+        h = ops.rn_maxpool(h)
+        for b in blocks:
+            o = ops.rn_conv(h, packed[id(b.conv1)], 1)
+            ops.rn_bn_apply(o, *ops.rn_bn_stats(o, b.bn1), relu=True)
+            o = ops.rn_conv(o, packed[id(b.conv2)], b.stride)
+            ops.rn_bn_apply(o, *ops.rn_bn_stats(o, b.bn2), relu=True)
+            if b.downsample is not None:
+                idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride)
+                ops.rn_bn_apply(idn, *ops.rn_bn_stats(idn, b.downsample[1]))
+            else:
+                idn = h
+            o = ops.rn_conv(o, packed[id(b.conv3)], 1)
+            h = ops.rn_bn_apply(o, *ops.rn_bn_stats(o, b.bn3), residual=idn, relu=True)
+        return ops.rn_avgpool(h)
+    bns = [bn1] + [n for b in blocks for n in ([b.bn1, b.bn2, b.bn3] + ([b.downsample[1]] if b.downsample is not None else []))]
+    tensors = [t for n in bns for t in (n.weight, n.bias, n.running_mean, n.running_var)]
+    coef = cache["bn"].get(tensors, None, lambda: {id(n): ops.rn_bn_eval_coeffs(n) for n in bns})
+    h = ops.rn_stem(planes, x.single, w1, dtype, *coef[id(bn1)], relu=True)
+    h = ops.rn_maxpool(h)
+    for b in blocks:
+        o = ops.rn_conv(h, packed[id(b.conv1)], 1, *coef[id(b.bn1)], relu=True)
+        o = ops.rn_conv(o, packed[id(b.conv2)], b.stride, *coef[id(b.bn2)], relu=True)
+        idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride, *coef[id(b.downsample[1])]) if b.downsample is not None else h
+        h = ops.rn_conv(o, packed[id(b.conv3)], 1, *coef[id(b.bn3)], residual=idn, relu=True)
+    return ops.rn_avgpool(h)
+
+
+def fc_forward(fc, feats):
+    """ResNet.fc (model.py:148-149: Linear(2048, num_classes), assigned after the freeze, so it trains) on the f32 (N, 2048)
+    features; through autograd when its parameters require grad."""
+    from . import differentiable
+    if torch.is_grad_enabled() and (fc.weight.requires_grad or fc.bias.requires_grad):
+        return differentiable.FcFn.apply(feats, fc.weight, fc.bias)
+    return ops.linear_small(feats, fc.weight.detach().contiguous(), fc.bias.detach().contiguous())
+
+
+def new_cache():
+    return {"w": _Cache(), "bn": _Cache()}

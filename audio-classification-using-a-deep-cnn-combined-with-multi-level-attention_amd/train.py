@@ -85,9 +85,20 @@ class TrainStep:
                  if p.requires_grad and ".fcf." not in n and (held is None or id(p) in held)]
         if not named:
             raise ValueError("no trainable parameter to update")
+        self.resnet = getattr(clf, "cnn_type", "vggish") == "resnet"
+        self.rn_fc = False
+        if self.resnet:
+            # the ResNet trunk runs its train-mode forward inside the step (batch statistics, running-statistics update) with
+            # no tape; trained are the head and, with just_bottlenecks=False, cnn.cnn_model.fc (model.py:148-149)
+            self.rn_fc = any(n.startswith(self.RN_FC) for n, _ in named)
+            trunk = [n for n, _ in named if n.startswith("cnn.") and not n.startswith(self.RN_FC)]
+            if trunk:
+                raise NotImplementedError("gradients into the ResNet trunk are not built (parameter %s is in the update set)" % trunk[0])
+            if self.dist.active:
+                raise NotImplementedError("train mode of cnn_type 'resnet' runs in a single process (no data parallel)")
         # CNN gradients are needed iff the update set holds a CNN parameter; any subset of the CNN is fine (the backward
         # pass stops at the lowest layer that needs a gradient and skips the weight gradients nobody asked for)
-        self.finetune = any(n.startswith("cnn.") for n, _ in named)
+        self.finetune = not self.resnet and any(n.startswith("cnn.") for n, _ in named)
         if self.finetune and clf.cnn.precision not in ("f32", "bf16"):
             raise NotImplementedError("CNN gradients are built for precision 'f32' (exact) and 'bf16' (bf16 arithmetic, f32 "
                                       "master weights), not %r" % clf.cnn.precision)
@@ -134,9 +145,11 @@ class TrainStep:
     # layer position (cnn_train.backward's `pos`: 0..5 conv1..conv6, 6..8 the three Linear layers) at which a bucket is final
     BUCKET_TRIGGER = {"fc12": 7, "fc0": 6, "conv56": 4, "conv14": 0}
 
+    RN_FC = "cnn.cnn_model.fc."
+
     @staticmethod
     def _bucket_of(name):
-        if not name.startswith("cnn."):
+        if not name.startswith("cnn.") or name.startswith(TrainStep.RN_FC):
             return "mla"
         key = name.split(".")[-3:-1]                      # (..., "features" | "embeddings" | "0", index, "weight" | "bias")
         idx = int(key[1])
@@ -229,6 +242,9 @@ class TrainStep:
         self._dev_t = self.t
         for d in drops:
             d.calls += 1
+        rn = getattr(self.clf.cnn, "_rn_cache", None)
+        if rn is not None:                         # the replay moved the ResNet running statistics on the device: eval coefficients are stale
+            rn["bn"].key = None
         if self.finetune:                          # the graph re-derives its own weight copies; anything cached outside it is stale
             for m in self.clf.cnn.modules():
                 if hasattr(m, "_cache"):
@@ -241,14 +257,27 @@ class TrainStep:
         clf = self.clf
         B_global = inputs.shape[0] * self.dist.world
         x = clf.input(inputs)
+        rn_feats = None
         if self.finetune:
             feats, cnn_tape = cnn_train.forward(clf.cnn.cnn_model, x, clf.cnn.precision)
+        elif self.rn_fc:                       # ResNet fc (just_bottlenecks=False): trunk features kept for the fc weight gradient
+            from . import resnet
+            m = clf.cnn.cnn_model
+            rn_feats = resnet.trunk_forward(m, x, clf.cnn.precision, True, clf.cnn._rn_cache)
+            feats = ops.linear_small(rn_feats, m.fc.weight.detach(), m.fc.bias.detach())
         else:
             feats = clf.cnn(x)
         ctx = mla_train.Ctx(tape=True, dist=self.dist, counter=self.step_dev if captured else None, bases=bases)
         out = mla_train.mla_forward(clf.mla, feats.reshape(-1, T, clf.emb_input_size), ctx)
         loss, dout, hits = ops.cross_entropy(out, labels, 1.0 / B_global)
-        d_feats = mla_train.mla_backward(clf.mla, ctx, dout, self.mla_grads, need_input_grad=self.finetune)
+        d_feats = mla_train.mla_backward(clf.mla, ctx, dout, self.mla_grads, need_input_grad=self.finetune or self.rn_fc)
+        if self.rn_fc:
+            fc = clf.cnn.cnn_model.fc
+            gw = self.grads.get(self.RN_FC + "weight")
+            gb = self.grads.get(self.RN_FC + "bias")
+            ops.linear_small_bwd(rn_feats, fc.weight.detach(), d_feats.contiguous(),
+                                 gw if gw is not None else torch.empty_like(fc.weight, dtype=torch.float32),
+                                 gb if gb is not None else torch.empty_like(fc.bias, dtype=torch.float32))
         bucketed = self.dist.active and self.finetune and self.overlap
         if bucketed:
             # the head's gradients are final: reduce them while the CNN backward runs; each CNN bucket follows as soon as

@@ -14,6 +14,7 @@ SURVEY.md section 5 "Checkpoint / resume".
 """
 
 import math
+import re
 import zlib
 
 import numpy as np
@@ -118,8 +119,44 @@ def mla_shapes(model_conf, emb_input_size, prefix="mla.", T=10, H=600, K=10):
     return shapes
 
 
-def ensemble_shapes(model_conf=(2, 1), just_bottlenecks=False):
-    """Ordered {key: shape} of Ensemble.state_dict() for cnn_type='vggish' (model.py:54-56)."""
+RESNET_STAGES = [(64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)]   # (width, blocks, stride of block 0)
+
+
+def resnet50_shapes(prefix="cnn.cnn_model.", just_bottlenecks=True, num_classes=1000):
+    """Ordered {key: shape} of torchvision's ResNet-50 as CNN.cnn_model (model.py:128-149). just_bottlenecks=True:
+    nn.Sequential(*children()[:-1], CnnFlatten) numbers the children conv1 0, bn1 1, relu 2, maxpool 3, layer1..4 4..7
+    (318 entries); otherwise the named keys with fc = Linear(2048, num_classes) (320 entries)."""
+    names = ["0", "1"] + [str(4 + i) for i in range(4)] if just_bottlenecks else ["conv1", "bn1"] + ["layer%d" % (i + 1) for i in range(4)]
+    shapes = {prefix + names[0] + ".weight": (64, 3, 7, 7)}
+    _bn_shapes(shapes, prefix + names[1], 64)
+    inplanes = 64
+    for (planes, n, _), stage in zip(RESNET_STAGES, names[2:]):
+        for b in range(n):
+            p = "%s%s.%d." % (prefix, stage, b)
+            cin = inplanes if b == 0 else planes * 4
+            shapes[p + "conv1.weight"] = (planes, cin, 1, 1)
+            _bn_shapes(shapes, p + "bn1", planes)
+            shapes[p + "conv2.weight"] = (planes, planes, 3, 3)
+            _bn_shapes(shapes, p + "bn2", planes)
+            shapes[p + "conv3.weight"] = (planes * 4, planes, 1, 1)
+            _bn_shapes(shapes, p + "bn3", planes * 4)
+            if b == 0:
+                shapes[p + "downsample.0.weight"] = (planes * 4, inplanes, 1, 1)
+                _bn_shapes(shapes, p + "downsample.1", planes * 4)
+        inplanes = planes * 4
+    if not just_bottlenecks:
+        shapes[prefix + "fc.weight"] = (num_classes, 2048)
+        shapes[prefix + "fc.bias"] = (num_classes,)
+    return shapes
+
+
+def ensemble_shapes(model_conf=(2, 1), just_bottlenecks=False, cnn_type="vggish", num_classes=10):
+    """Ordered {key: shape} of Ensemble.state_dict() (model.py:54-56); num_classes: the ResNet fc width when
+    just_bottlenecks=False (= the head's input width, model.py:49-50)."""
+    if cnn_type == "resnet":
+        shapes = mla_shapes(list(model_conf), 2048 if just_bottlenecks else num_classes)
+        shapes.update(resnet50_shapes("cnn.cnn_model.", just_bottlenecks, num_classes))
+        return shapes
     emb = 12288 if just_bottlenecks else 128
     shapes = mla_shapes(list(model_conf), emb)
     if just_bottlenecks:
@@ -132,6 +169,9 @@ def ensemble_shapes(model_conf=(2, 1), just_bottlenecks=False):
     return shapes
 
 
+_RESNET_BN = re.compile(r"^cnn\.cnn_model\.(1|bn1)\.|\.bn[123]\.|\.downsample\.1\.")
+
+
 def make_tensor(seed, key, shape):
     """One synthetic tensor for a state_dict key (float32, or int64 for counters).
 
@@ -139,7 +179,9 @@ def make_tensor(seed, key, shape):
     activations keep O(1) scale through the ReLU stack (a parity test on vanishing
     activations would not see kernel errors); biases use 1/sqrt(fan_in).
     BatchNorm affine / running statistics get non-trivial values so that
-    eval-mode normalisation is exercised.
+    eval-mode normalisation is exercised. ResNet-50 BatchNorm2d affine parameters (``bn1``, ``bnK``,
+    ``downsample.1``; the names hold no "norm") get the same BatchNorm values, except ``bn3.weight`` at a
+    fifth of that scale, so that the residual stream stays O(1) through the 16 blocks in eval mode.
     """
     sid = stream_id(key)
     n = int(np.prod(shape)) if len(shape) else 1
@@ -151,6 +193,10 @@ def make_tensor(seed, key, shape):
         v = 0.1 * u
     elif leaf == "running_var":
         v = 1.0 + 0.5 * u
+    elif len(shape) == 1 and _RESNET_BN.search(key):
+        v = (1.0 + 0.1 * u) if leaf == "weight" else 0.1 * u
+        if leaf == "weight" and ".bn3." in key:
+            v = 0.2 * v
     elif len(shape) == 1 and ("norm" in key):
         v = (1.0 + 0.1 * u) if leaf == "weight" else 0.1 * u
     elif leaf == "weight":

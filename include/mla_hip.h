@@ -407,6 +407,55 @@ int mla_dropout_mask(uint8_t* mask, int64_t n, uint64_t seed, uint64_t stream_id
 int mla_dropout_mask_dev(uint8_t* mask, int64_t n, uint64_t seed, uint64_t stream_base, const int64_t* counter_dev,
                          uint64_t offset, float p_drop, mla_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * ResNet-50 v1.5 trunk, cnn_type="resnet" (model.py:128-149, torchvision resnet50 as the reference
+ * builds it). Activations NHWC in MLA_F32 or MLA_BF16, accumulation f32; images exactly 224 x 224.
+ * ---------------------------------------------------------------------------------- */
+
+/* Conv2d weight OIHW f32 (cout, cin, ks, ks) -> [cout][ks][ks][cin] in `dtype` (the layout mla_rn_conv reads): the
+ * weights of the convs torchvision's resnet50 builds at model.py:129 (loaded through load_model, train.py:278-281). */
+int mla_rn_repack(const float* w_oihw, int64_t cout, int64_t cin, int64_t ks, void* out, int dtype, mla_stream_t stream);
+
+/* Input.forward (model.py:84-101) + resnet.conv1 (7x7 stride 2 pad 3, 3 -> 64, no bias; model.py:129): x (n, H, W) f32
+ * planes with H = W = 224 (S_RESNET_SHAPE, params.py:23; anything else is MLA_E_SHAPE); single = 0
+ * "repeat" (x in all three channels), 1 "single" (x in channel 0, zeros in 1-2); channels normalised with the ImageNet
+ * mean/std, zero padding applied to the NORMALISED channels (a tap outside the image adds nothing). w (64, 3, 7, 7) f32.
+ * out NHWC (n, 112, 112, 64) in dtype; scale/shift (64 each, or NULL for the raw conv) then ReLU if relu != 0. */
+int mla_rn_stem(const float* x, int64_t n, int64_t H, int64_t W, int single, const float* w, const float* scale, const float* shift, int relu,
+                void* out, int dtype, mla_stream_t stream);
+
+/* Bottleneck convs of resnet.layer1..layer4 (model.py:129, applied by CNN.forward at model.py:172-173; conv1x1 / conv3x3 /
+ * downsample, bias=False): NHWC in (n, H, W, cin) -> out (n, Ho, Wo, cout)
+ * with ks 1 or 3, pad ks/2, stride 1 or 2; cin and cout multiples of 64. w_packed from mla_rn_repack in the same dtype.
+ * Epilogue: v = acc; if scale: v = v * scale[c] + shift[c] (eval BatchNorm2d); if residual (same shape as out): v += r;
+ * if relu: v = max(v, 0). Deterministic: an output element's reduction order does not depend on n. */
+int mla_rn_conv(const void* in, int64_t n, int64_t H, int64_t W, int64_t cin, const void* w_packed, int64_t cout, int64_t ks,
+                int64_t stride, const float* scale, const float* shift, const void* residual, int relu, void* out, int dtype,
+                mla_stream_t stream);
+
+/* BatchNorm2d in train mode (bn1..bn3 / downsample.1 of model.py:129; the frozen trunk stays in train mode, model.py:132
+ * + train.py:111 clf.train()): batch statistics of x (rows = n*H*W, channels),
+ * NHWC, channels a multiple of 64. Writes scale = gamma / sqrt(var_b + eps) and shift = beta - mean * scale (for
+ * mla_rn_bn_apply), optionally mean / var_biased (NULL to skip), and updates running_mean / running_var (unbiased variance,
+ * count = rows; NULL to skip). Sums in double with a fixed reduction order: bit-identical runs.
+ * workspace: mla_rn_bn_workspace_bytes(channels) bytes. */
+int64_t mla_rn_bn_workspace_bytes(int64_t channels);
+int mla_rn_bn_stats(const void* x, int64_t rows, int64_t channels, int dtype, void* workspace, const float* gamma,
+                    const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* mean,
+                    float* var_biased, float* scale, float* shift, mla_stream_t stream);
+/* BatchNorm2d in eval mode (model.py:129 under clf.eval(), train.py:113 and :201): scale / shift from the running statistics, for the mla_rn_conv / mla_rn_stem epilogue. */
+int mla_rn_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                          float eps, int64_t channels, float* scale, float* shift, mla_stream_t stream);
+/* out = x * scale[c] + shift[c] (+ residual) (ReLU if relu), rows x channels NHWC (channels a multiple of 8): the train-mode
+ * bn1/bn2/bn3/downsample.1 of a Bottleneck followed by `out += identity; relu(out)`. out may alias x. */
+int mla_rn_bn_apply(const void* x, int64_t rows, int64_t channels, const float* scale, const float* shift, const void* residual,
+                    int relu, void* out, int dtype, mla_stream_t stream);
+
+/* resnet.maxpool (model.py:129, child 3 of the model.py:142-146 Sequential): MaxPool2d(3, stride 2, padding 1), NHWC (n, H, W, channels) -> (n, (H-1)/2+1, (W-1)/2+1, channels). */
+int mla_rn_maxpool(const void* in, int64_t n, int64_t H, int64_t W, int64_t channels, void* out, int dtype, mla_stream_t stream);
+/* resnet.avgpool + CnnFlatten (model.py:188): AdaptiveAvgPool2d(1) of NHWC (n, hw, channels) -> f32 (n, channels). */
+int mla_rn_avgpool(const void* in, int64_t n, int64_t hw, int64_t channels, float* out, int dtype, mla_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

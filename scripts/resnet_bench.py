@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Throughput of the HIP ResNet-50 trunk (cnn_type="resnet", just_bottlenecks=True): eval trunk in bf16 / f32 at 80 and
+5 120 images, the frozen training step (TrainStep) at 8 and 64 bags, and -- as a yardstick only -- the same network built
+from torch.nn.functional.conv2d in channels-last bf16 (MIOpen). Prints one JSON line.
+
+    python scripts/resnet_bench.py [--quick] [--per-conv]
+
+--per-conv: instead, each distinct bf16 conv (and the stem) timed alone at 80 images against its own roofline.
+"""
+
+import importlib
+import json
+import os
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "audio-classification-using-a-deep-cnn-combined-with-multi-level-attention_amd"
+M = importlib.import_module(PKG + ".model")
+W = importlib.import_module(PKG + ".weights")
+TR = importlib.import_module(PKG + ".train")
+RN = importlib.import_module(PKG + ".resnet")
+
+CONF = dict(cnn_type="resnet", num_classes=10, use_pretrained=False, just_bottlenecks=True, cnn_trainable=False,
+            first_cnn_layer_trainable=False, in_channels=3)
+
+
+def timeit(fn, warmup, iters):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters
+
+
+def miopen_trunk(ens, x):
+    """Yardstick: the same trunk from F.conv2d / F.batch_norm in channels-last bf16 (eval mode)."""
+    conv1, bn1, layers, _ = RN.parts(ens.cnn.cnn_model)
+    cache = {}
+
+    def w(c):
+        if id(c) not in cache:
+            cache[id(c)] = c.weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        return cache[id(c)]
+
+    def bn(t, m, relu):
+        t = F.batch_norm(t, m.running_mean, m.running_var, m.weight.detach(), m.bias.detach(), False, 0.0, m.eps)
+        return F.relu(t) if relu else t
+
+    mean = torch.tensor([0.485, 0.456, 0.406], device=x.device).view(1, 3, 1, 1)
+    std = torch.tensor([0.229, 0.224, 0.225], device=x.device).view(1, 3, 1, 1)
+
+    def run():
+        h = ((x.reshape(-1, 1, 224, 224).expand(-1, 3, -1, -1) - mean) / std).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        h = F.max_pool2d(bn(F.conv2d(h, w(conv1), stride=2, padding=3), bn1, True), 3, 2, 1)
+        for layer in layers:
+            for b in layer:
+                o = bn(F.conv2d(h, w(b.conv1)), b.bn1, True)
+                o = bn(F.conv2d(o, w(b.conv2), stride=b.stride, padding=1), b.bn2, True)
+                o = bn(F.conv2d(o, w(b.conv3)), b.bn3, False)
+                idn = bn(F.conv2d(h, w(b.downsample[0]), stride=b.stride), b.downsample[1], False) if b.downsample is not None else h
+                h = F.relu(o + idn)
+        return F.adaptive_avg_pool2d(h, 1).flatten(1).float()
+    return run
+
+
+def conv_rooflines(ens, n_img=80):
+    """Each distinct bf16 conv of the trunk timed alone at n_img images, against max(FLOP / 2.5 PF, bytes / 8 TB/s)
+    (bytes = input + weights + output once each); the stem against its own bound."""
+    OPS = importlib.import_module(PKG + ".ops")
+    dev = torch.device("cuda")
+    conv1, bn1, layers, _ = RN.parts(ens.cnn.cnn_model)
+    shapes, H = {}, 56
+    for layer in layers:
+        for b in layer:
+            cin = b.conv1.in_channels
+            for c, h, st in ((b.conv1, H, 1), (b.conv2, H, b.stride), (b.conv3, H // b.stride, 1)) + \
+                    (((b.downsample[0], H, b.stride),) if b.downsample is not None else ()):
+                key = (c.kernel_size[0], st, c.in_channels, c.out_channels, h)
+                shapes[key] = shapes.get(key, 0) + 1
+            H //= b.stride
+    rows = []
+    for (k, st, cin, cout, h), count in shapes.items():
+        x = torch.randn(n_img, h, h, cin, device=dev).to(torch.bfloat16)
+        w = OPS.rn_repack(torch.randn(cout, cin, k, k, device=dev) * 0.05, torch.bfloat16)
+        ho = (h + 2 * (k // 2) - k) // st + 1
+        t = timeit(lambda: OPS.rn_conv(x, w, st), 3, 20)
+        flop = 2.0 * n_img * ho * ho * cout * k * k * cin
+        byts = 2.0 * (n_img * h * h * cin + cout * k * k * cin + n_img * ho * ho * cout)
+        bound = max(flop / 2.5e15, byts / 8e12)
+        rows.append({"conv": "k%d s%d %d->%d @%d" % (k, st, cin, cout, h), "count": count, "us": round(t * 1e6, 1),
+                     "roofline_us": round(bound * 1e6, 1), "fraction": round(bound / t, 3)})
+    planes = torch.rand(n_img, 224, 224, device=dev)
+    w1 = torch.randn(64, 3, 7, 7, device=dev) * 0.05
+    t = timeit(lambda: OPS.rn_stem(planes, False, w1, torch.bfloat16), 3, 20)
+    flop, byts = 2.0 * n_img * 112 * 112 * 64 * 147, 4.0 * n_img * 224 * 224 + 2.0 * n_img * 112 * 112 * 64
+    bound = max(flop / 157e12, byts / 8e12)              # the stem runs on the f32 vector/FMA path: f32 MFMA peak as its bound
+    rows.append({"conv": "stem k7 s2 3->64 @224", "count": 1, "us": round(t * 1e6, 1), "roofline_us": round(bound * 1e6, 1),
+                 "fraction": round(bound / t, 3)})
+    return rows
+
+
+def main():
+    quick = "--quick" in sys.argv
+    dev = torch.device("cuda")
+    sd = {k: torch.as_tensor(v) for k, v in W.make_state_dict(21, W.ensemble_shapes((2, 1), True, cnn_type="resnet")).items()}
+    if "--per-conv" in sys.argv:
+        ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
+        ens.load_state_dict(sd)
+        for r in conv_rooflines(ens.cuda().eval()):
+            print(json.dumps(r))
+        return
+    res = {"metric": "resnet50_trunk", "device": torch.cuda.get_device_name(0)}
+    for prec in ("bf16", "f32"):
+        ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision=prec)
+        ens.load_state_dict(sd)
+        ens.cuda().eval()
+        for n_img in ((80,) if quick else (80, 5120)):
+            x = torch.rand(n_img // 10, 10, 1, 224, 224, device=dev)
+            with torch.no_grad():
+                t = timeit(lambda: ens.cnn(ens.input(x)), 2, 5 if n_img > 1000 else 20)
+            res["eval_%s_%d_img_per_s" % (prec, n_img)] = round(n_img / t, 1)
+            res["eval_%s_%d_bags_per_s" % (prec, n_img)] = round(n_img / 10 / t, 1)
+            if prec == "bf16":
+                with torch.no_grad():
+                    t = timeit(miopen_trunk(ens, x), 2, 5 if n_img > 1000 else 20)
+                res["miopen_bf16_%d_img_per_s" % n_img] = round(n_img / t, 1)
+        del ens
+    ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
+    ens.load_state_dict(sd)
+    ens.cuda()
+    step = TR.TrainStep(ens, lr=1e-3)
+    for bags in ((8,) if quick else (8, 64)):
+        x = torch.rand(bags, 10, 1, 224, 224, device=dev)
+        y = torch.arange(bags, device=dev) % 10
+        t = timeit(lambda: step(x, y), 2, 5)
+        res["train_step_bf16_%d_bags_ms" % bags] = round(t * 1e3, 2)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
