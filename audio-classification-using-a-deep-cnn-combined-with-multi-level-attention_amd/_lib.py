@@ -130,6 +130,8 @@ def lib():
         L.mla_rn_bn_workspace_bytes.restype = i64
         L.mla_rn_bn_workspace_bytes.argtypes = [i64]
         L.mla_rn_bn_stats.argtypes = [vp, i64, i64, ci, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, vp]
+        L.mla_rn_bn_sums.argtypes = [vp, i64, i64, ci, vp, vp, vp]
+        L.mla_rn_bn_finish.argtypes = [vp, i64, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, vp]
         L.mla_rn_bn_eval_coeffs.argtypes = [vp, vp, vp, vp, cf, i64, vp, vp, vp]
         L.mla_rn_bn_apply.argtypes = [vp, i64, i64, vp, vp, vp, ci, vp, ci, vp]
         L.mla_rn_maxpool.argtypes = [vp, i64, i64, i64, i64, vp, ci, vp]

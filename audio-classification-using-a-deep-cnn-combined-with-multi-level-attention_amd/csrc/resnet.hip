@@ -7,7 +7,8 @@
 //                     epilogue: raw store (train mode) or per-channel scale/shift [+ residual] [+ ReLU] (eval BN)
 //   rn_bn_partial_kernel / rn_bn_finish_kernel
 //                     BatchNorm2d batch statistics over NHWC rows (fixed reduction order: bit-identical runs), running-stat
-//                     update and the scale/shift of the normalisation
+//                     update and the scale/shift of the normalisation; rn_bn_sums_kernel / rn_bn_finish_sums_kernel split
+//                     the finish around an all-reduce of [sum x, sum x^2, rows] (SyncBN across data-parallel ranks)
 //   rn_bn_apply_kernel  y = x * scale + shift [+ residual] [ReLU] (train mode)
 //   rn_maxpool_kernel   MaxPool2d(3, 2, 1);  rn_avgpool_kernel  AdaptiveAvgPool2d(1) -> f32 (N, C)
 #include "common.h"
@@ -248,15 +249,20 @@ __global__ __launch_bounds__(256) void rn_bn_partial_kernel(const T* __restrict_
     }
 }
 
-__global__ void rn_bn_finish_kernel(const double* __restrict__ part, int P, int C, int64_t rows, const float* __restrict__ gamma,
-                                    const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
-                                    float* __restrict__ running_var, float* __restrict__ mean_out, float* __restrict__ var_out,
-                                    float* __restrict__ scale, float* __restrict__ shift) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0, s2 = 0.0;
+// The P slices of one channel, added in slice order: the fixed order that rn_bn_finish_kernel and rn_bn_sums_kernel share.
+__device__ __forceinline__ void bn_sum_slices(const double* __restrict__ part, int P, int C, int c, double& s, double& s2) {
+    s = 0.0;
+    s2 = 0.0;
     for (int p = 0; p < P; ++p) { s += part[int64_t(p) * C + c]; s2 += part[int64_t(P + p) * C + c]; }
-    const double n = double(rows), mean = s / n;
+}
+
+// One channel's statistics from its sums over n rows: one expression sequence for the single-process and the two-stage path.
+__device__ __forceinline__ void bn_finish_channel(int c, double s, double s2, double n, const float* __restrict__ gamma,
+                                                  const float* __restrict__ beta, float eps, float momentum,
+                                                  float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                  float* __restrict__ mean_out, float* __restrict__ var_out,
+                                                  float* __restrict__ scale, float* __restrict__ shift) {
+    const double mean = s / n;
     double var = s2 / n - mean * mean;
     if (var < 0.0) var = 0.0;
     const double sc = double(gamma[c]) / sqrt(var + double(eps));
@@ -265,10 +271,43 @@ __global__ void rn_bn_finish_kernel(const double* __restrict__ part, int P, int 
     if (mean_out) mean_out[c] = float(mean);
     if (var_out) var_out[c] = float(var);
     if (running_mean) {
-        const double unbiased = rows > 1 ? var * n / (n - 1.0) : var;
+        const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
         running_mean[c] = float((1.0 - momentum) * running_mean[c] + momentum * mean);
         running_var[c] = float((1.0 - momentum) * running_var[c] + momentum * unbiased);
     }
+}
+
+__global__ void rn_bn_finish_kernel(const double* __restrict__ part, int P, int C, int64_t rows, const float* __restrict__ gamma,
+                                    const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
+                                    float* __restrict__ running_var, float* __restrict__ mean_out, float* __restrict__ var_out,
+                                    float* __restrict__ scale, float* __restrict__ shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double s, s2;
+    bn_sum_slices(part, P, C, c, s, s2);
+    bn_finish_channel(c, s, s2, double(rows), gamma, beta, eps, momentum, running_mean, running_var, mean_out, var_out, scale, shift);
+}
+
+// Stage 1 of the data-parallel statistics: sums = [sum x (C), sum x^2 (C), rows], the message the ranks add up.
+__global__ void rn_bn_sums_kernel(const double* __restrict__ part, int P, int C, int64_t rows, double* __restrict__ sums) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double s, s2;
+    bn_sum_slices(part, P, C, c, s, s2);
+    sums[c] = s;
+    sums[C + c] = s2;
+    if (c == 0) sums[2 * int64_t(C)] = double(rows);
+}
+
+// Stage 2: the statistics of the (all-reduced) sums; the row count is the message's last element.
+__global__ void rn_bn_finish_sums_kernel(const double* __restrict__ sums, int C, const float* __restrict__ gamma,
+                                         const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
+                                         float* __restrict__ running_var, float* __restrict__ mean_out, float* __restrict__ var_out,
+                                         float* __restrict__ scale, float* __restrict__ shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    bn_finish_channel(c, sums[c], sums[C + c], sums[2 * int64_t(C)], gamma, beta, eps, momentum, running_mean, running_var, mean_out,
+                      var_out, scale, shift);
 }
 
 __global__ void rn_bn_eval_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ rm,
@@ -417,15 +456,15 @@ extern "C" int mla_rn_conv(const void* in, int64_t n, int64_t H, int64_t W, int6
 
 extern "C" int64_t mla_rn_bn_workspace_bytes(int64_t channels) { return 2 * int64_t(kMaxSlices) * channels * int64_t(sizeof(double)); }
 
-extern "C" int mla_rn_bn_stats(const void* x, int64_t rows, int64_t channels, int dtype, void* workspace, const float* gamma,
-                               const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* mean,
-                               float* var_biased, float* scale, float* shift, mla_stream_t stream) {
+// Checks the arguments of the statistics pass over x and launches rn_bn_partial_kernel into the workspace; returns the slice count P
+// through *slices (0 on an error, which is then in mla_last_error).
+static int rn_bn_partials(const void* x, int64_t rows, int64_t channels, int dtype, void* workspace, hipStream_t s, int* slices) {
+    *slices = 0;
     MLA_REQUIRE(rows > 0 && channels > 0 && channels % 64 == 0 && channels <= 65536 * 64, MLA_E_SHAPE,
                 "rn_bn_stats rows %lld channels %lld (channels: multiple of 64)", (long long)rows, (long long)channels);
-    MLA_REQUIRE(x && workspace && gamma && beta && scale && shift && (!running_mean == !running_var), MLA_E_ARG, "null rn_bn_stats buffers");
+    MLA_REQUIRE(x && workspace, MLA_E_ARG, "null rn_bn_stats buffers");
     MLA_REQUIRE(mla::aligned(x, 16) && mla::aligned(workspace, 8), MLA_E_ARG, "rn_bn_stats buffers must be 16-byte aligned");
     MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_bn_stats dtype %d", dtype);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = bn_slices(rows);
     double* part = static_cast<double*>(workspace);
     const dim3 grid(unsigned(channels / 64), unsigned(P));
@@ -434,9 +473,48 @@ extern "C" int mla_rn_bn_stats(const void* x, int64_t rows, int64_t channels, in
     else
         hipLaunchKernelGGL(rn_bn_partial_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(x), rows, int(channels), part);
     MLA_LAUNCH_OK("rn_bn_partial_kernel");
-    hipLaunchKernelGGL(rn_bn_finish_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, part, P, int(channels), rows, gamma,
-                       beta, eps, momentum, running_mean, running_var, mean, var_biased, scale, shift);
+    *slices = P;
+    return MLA_OK;
+}
+
+extern "C" int mla_rn_bn_stats(const void* x, int64_t rows, int64_t channels, int dtype, void* workspace, const float* gamma,
+                               const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* mean,
+                               float* var_biased, float* scale, float* shift, mla_stream_t stream) {
+    MLA_REQUIRE(rows > 0 && channels > 0 && channels % 64 == 0 && channels <= 65536 * 64, MLA_E_SHAPE,
+                "rn_bn_stats rows %lld channels %lld (channels: multiple of 64)", (long long)rows, (long long)channels);
+    MLA_REQUIRE(x && workspace && gamma && beta && scale && shift && (!running_mean == !running_var), MLA_E_ARG, "null rn_bn_stats buffers");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int P = 0;
+    const int rc = rn_bn_partials(x, rows, channels, dtype, workspace, s, &P);
+    if (rc != MLA_OK) return rc;
+    hipLaunchKernelGGL(rn_bn_finish_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, static_cast<const double*>(workspace),
+                       P, int(channels), rows, gamma, beta, eps, momentum, running_mean, running_var, mean, var_biased, scale, shift);
     MLA_LAUNCH_OK("rn_bn_finish_kernel");
+    return MLA_OK;
+}
+
+extern "C" int mla_rn_bn_sums(const void* x, int64_t rows, int64_t channels, int dtype, void* workspace, double* sums,
+                              mla_stream_t stream) {
+    MLA_REQUIRE(sums && mla::aligned(sums, 8), MLA_E_ARG, "rn_bn_sums: sums must be a non-null, 8-byte aligned buffer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int P = 0;
+    const int rc = rn_bn_partials(x, rows, channels, dtype, workspace, s, &P);
+    if (rc != MLA_OK) return rc;
+    hipLaunchKernelGGL(rn_bn_sums_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, static_cast<const double*>(workspace), P,
+                       int(channels), rows, sums);
+    MLA_LAUNCH_OK("rn_bn_sums_kernel");
+    return MLA_OK;
+}
+
+extern "C" int mla_rn_bn_finish(const double* sums, int64_t channels, const float* gamma, const float* beta, float eps, float momentum,
+                                float* running_mean, float* running_var, float* mean, float* var_biased, float* scale, float* shift,
+                                mla_stream_t stream) {
+    MLA_REQUIRE(channels > 0 && channels <= 65536 * 64, MLA_E_SHAPE, "rn_bn_finish channels %lld", (long long)channels);
+    MLA_REQUIRE(sums && gamma && beta && scale && shift && (!running_mean == !running_var), MLA_E_ARG, "null rn_bn_finish buffers");
+    MLA_REQUIRE(mla::aligned(sums, 8), MLA_E_ARG, "rn_bn_finish: sums must be 8-byte aligned");
+    hipLaunchKernelGGL(rn_bn_finish_sums_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), sums,
+                       int(channels), gamma, beta, eps, momentum, running_mean, running_var, mean, var_biased, scale, shift);
+    MLA_LAUNCH_OK("rn_bn_finish_sums_kernel");
     return MLA_OK;
 }
 

@@ -772,6 +772,33 @@ def rn_bn_stats(x, bn, running=True, want_stats=False):
     return (scale, shift, mean, var) if want_stats else (scale, shift)
 
 
+def rn_bn_stats_sync(x, bn, dist, running=True, want_stats=False):
+    """rn_bn_stats with the statistics of the data-parallel group's global batch (SyncBN): [sum x, sum x^2, rows] of the local
+    shard, all-reduced (tag "syncbn_rn"), then finished on every rank. The row count travels in the message, so shards may
+    differ in size. Without an active SyncBN group (no group, or sync_bn=False) this is rn_bn_stats itself, bit for bit."""
+    if not dist.bn_active:
+        return rn_bn_stats(x, bn, running, want_stats)
+    _chk(x)
+    C = x.shape[-1]
+    rows = x.numel() // C
+    dev = x.device
+    L = _lib.lib()
+    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+    _lib.check(_timed("rn_bn_sums", L.mla_rn_bn_sums, _p(x), rows, C, DT[x.dtype], _p(_rn_workspace(dev, C)), _p(sums),
+                      _lib.stream_ptr()))
+    dist.all_reduce_sum(sums, "syncbn_rn")
+    scale = torch.empty(C, dtype=torch.float32, device=dev)
+    shift = torch.empty(C, dtype=torch.float32, device=dev)
+    mean = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
+    var = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
+    rm, rv = (bn.running_mean, bn.running_var) if running else (None, None)
+    _lib.check(_timed("rn_bn_finish", L.mla_rn_bn_finish, _p(sums), C, _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps),
+                      float(bn.momentum), _p(rm), _p(rv), _p(mean), _p(var), _p(scale), _p(shift), _lib.stream_ptr()))
+    if running:
+        _lib.check(L.mla_counter_add(_p(bn.num_batches_tracked), 1, _lib.stream_ptr()))
+    return (scale, shift, mean, var) if want_stats else (scale, shift)
+
+
 def rn_bn_eval_coeffs(bn):
     C = bn.num_features
     dev = bn.weight.device

@@ -158,8 +158,10 @@ def _check_frozen(cnn_model):
                                       "train with cnn_trainable=False / first_cnn_layer_trainable=False" % name)
 
 
-def trunk_forward(cnn_model, x, precision, training, cache):
-    """StemInput -> f32 (N, 2048) bottleneck features (avgpool + flatten) of the HIP trunk."""
+def trunk_forward(cnn_model, x, precision, training, cache, dist=None):
+    """StemInput -> f32 (N, 2048) bottleneck features (avgpool + flatten) of the HIP trunk. dist: the ``ops.Dist`` of a
+    data-parallel training step; in train mode its SyncBN setting decides whether the 53 BatchNorm2d statistics are those of
+    the global batch (one all-reduce per layer) or of this rank's shard."""
     if not isinstance(x, StemInput):
         raise TypeError("the ResNet trunk takes the output of model.Input (raw 224 x 224 planes)")
     if precision not in _DTYPES:
@@ -178,21 +180,23 @@ def trunk_forward(cnn_model, x, precision, training, cache):
     w1 = conv1.weight.detach().contiguous()
     if training:
         cache["bn"].key = None                    # the running statistics change below, behind torch's version counters
+        dist = dist or ops._local()
+        stats = lambda t, bn: ops.rn_bn_stats_sync(t, bn, dist)     # noqa: E731
         h = ops.rn_stem(planes, x.single, w1, dtype)
-        ops.rn_bn_apply(h, *ops.rn_bn_stats(h, bn1), relu=True)
+        ops.rn_bn_apply(h, *stats(h, bn1), relu=True)
         h = ops.rn_maxpool(h)
         for b in blocks:
             o = ops.rn_conv(h, packed[id(b.conv1)], 1)
-            ops.rn_bn_apply(o, *ops.rn_bn_stats(o, b.bn1), relu=True)
+            ops.rn_bn_apply(o, *stats(o, b.bn1), relu=True)
             o = ops.rn_conv(o, packed[id(b.conv2)], b.stride)
-            ops.rn_bn_apply(o, *ops.rn_bn_stats(o, b.bn2), relu=True)
+            ops.rn_bn_apply(o, *stats(o, b.bn2), relu=True)
             if b.downsample is not None:
                 idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride)
-                ops.rn_bn_apply(idn, *ops.rn_bn_stats(idn, b.downsample[1]))
+                ops.rn_bn_apply(idn, *stats(idn, b.downsample[1]))
             else:
                 idn = h
             o = ops.rn_conv(o, packed[id(b.conv3)], 1)
-            h = ops.rn_bn_apply(o, *ops.rn_bn_stats(o, b.bn3), residual=idn, relu=True)
+            h = ops.rn_bn_apply(o, *stats(o, b.bn3), residual=idn, relu=True)
         return ops.rn_avgpool(h)
     bns = [bn1] + [n for b in blocks for n in ([b.bn1, b.bn2, b.bn3] + ([b.downsample[1]] if b.downsample is not None else []))]
     tensors = [t for n in bns for t in (n.weight, n.bias, n.running_mean, n.running_var)]

@@ -94,8 +94,6 @@ class TrainStep:
             trunk = [n for n, _ in named if n.startswith("cnn.") and not n.startswith(self.RN_FC)]
             if trunk:
                 raise NotImplementedError("gradients into the ResNet trunk are not built (parameter %s is in the update set)" % trunk[0])
-            if self.dist.active:
-                raise NotImplementedError("train mode of cnn_type 'resnet' runs in a single process (no data parallel)")
         # CNN gradients are needed iff the update set holds a CNN parameter; any subset of the CNN is fine (the backward
         # pass stops at the lowest layer that needs a gradient and skips the weight gradients nobody asked for)
         self.finetune = not self.resnet and any(n.startswith("cnn.") for n, _ in named)
@@ -260,11 +258,15 @@ class TrainStep:
         rn_feats = None
         if self.finetune:
             feats, cnn_tape = cnn_train.forward(clf.cnn.cnn_model, x, clf.cnn.precision)
-        elif self.rn_fc:                       # ResNet fc (just_bottlenecks=False): trunk features kept for the fc weight gradient
+        elif self.resnet:                      # trunk in train mode; its SyncBN statistics go through self.dist
             from . import resnet
             m = clf.cnn.cnn_model
-            rn_feats = resnet.trunk_forward(m, x, clf.cnn.precision, True, clf.cnn._rn_cache)
-            feats = ops.linear_small(rn_feats, m.fc.weight.detach(), m.fc.bias.detach())
+            feats = resnet.trunk_forward(m, x, clf.cnn.precision, True, clf.cnn._rn_cache, dist=self.dist)
+            if self.rn_fc:                     # ResNet fc (just_bottlenecks=False): trunk features kept for the fc weight gradient
+                rn_feats = feats
+                feats = ops.linear_small(rn_feats, m.fc.weight.detach(), m.fc.bias.detach())
+            elif not clf.cnn.just_bottlenecks:
+                feats = resnet.fc_forward(m.fc, feats)
         else:
             feats = clf.cnn(x)
         ctx = mla_train.Ctx(tape=True, dist=self.dist, counter=self.step_dev if captured else None, bases=bases)

@@ -443,6 +443,17 @@ int64_t mla_rn_bn_workspace_bytes(int64_t channels);
 int mla_rn_bn_stats(const void* x, int64_t rows, int64_t channels, int dtype, void* workspace, const float* gamma,
                     const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* mean,
                     float* var_biased, float* scale, float* shift, mla_stream_t stream);
+/* mla_rn_bn_stats in two stages, so that an all-reduce over the data-parallel ranks fits between them (SyncBN of the
+ * trunk: the statistics of the global batch). Stage 1 writes sums = [sum x (channels), sum x^2 (channels), rows] in double
+ * (2*channels + 1 elements): the row count travels with the message, so ranks may hold different numbers of rows. Stage 2
+ * computes mean, biased variance, scale / shift and the running-statistics update (unbiased variance with the count
+ * sums[2*channels], which must be > 0) from the sums; NULL conventions as mla_rn_bn_stats. For one rank, stage 1 followed
+ * by stage 2 gives the bits of mla_rn_bn_stats (same partial kernel, slices added in the same order, same finishing
+ * arithmetic). workspace: mla_rn_bn_workspace_bytes(channels) bytes, consumed by stage 1. */
+int mla_rn_bn_sums(const void* x, int64_t rows, int64_t channels, int dtype, void* workspace, double* sums, mla_stream_t stream);
+int mla_rn_bn_finish(const double* sums, int64_t channels, const float* gamma, const float* beta, float eps, float momentum,
+                     float* running_mean, float* running_var, float* mean, float* var_biased, float* scale, float* shift,
+                     mla_stream_t stream);
 /* BatchNorm2d in eval mode (model.py:129 under clf.eval(), train.py:113 and :201): scale / shift from the running statistics, for the mla_rn_conv / mla_rn_stem epilogue. */
 int mla_rn_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                           float eps, int64_t channels, float* scale, float* shift, mla_stream_t stream);

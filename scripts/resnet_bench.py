@@ -3,9 +3,12 @@
 5 120 images, the frozen training step (TrainStep) at 8 and 64 bags, and -- as a yardstick only -- the same network built
 from torch.nn.functional.conv2d in channels-last bf16 (MIOpen). Prints one JSON line.
 
-    python scripts/resnet_bench.py [--quick] [--per-conv]
+    python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank]
 
 --per-conv: instead, each distinct bf16 conv (and the stem) timed alone at 80 images against its own roofline.
+--dp-one-rank: instead, the cost of the trunk's SyncBN on one GPU: the frozen bf16 step (eager) at 8 and 64 bags without a
+process group and on a one-rank RCCL group with the collectives forced on (ops.Dist(always=True)), where each of the 53
+BatchNorm2d layers runs sums -> all-reduce -> finish; the all-reduces are counted and timed from ops.Dist.trace.
 """
 
 import importlib
@@ -107,10 +110,52 @@ def conv_rooflines(ens, n_img=80):
     return rows
 
 
+def dp_one_rank(sd):
+    """See --dp-one-rank in the module docstring."""
+    import torch.distributed as dist
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29517")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
+    ens.load_state_dict(sd)
+    ens.cuda()
+    res = {"metric": "resnet50_frozen_step_dp_one_rank", "device": torch.cuda.get_device_name(0), "precision": "bf16",
+           "just_bottlenecks": True}
+    for bags in (8, 64):
+        x = torch.rand(bags, 10, 1, 224, 224, device=dev)
+        y = torch.arange(bags, device=dev) % 10
+        for name, always in (("no_dist", "0"), ("dist_one_rank", "1")):
+            os.environ["MLA_DIST_ALWAYS"] = always
+            step = TR.TrainStep(ens, lr=1e-3, graph=False)
+            assert step.dist.active == (always == "1")
+            res["train_step_%d_bags_ms_%s" % (bags, name)] = round(timeit(lambda: step(x, y), 3, 10) * 1e3, 2)
+            if always == "1":
+                step.dist.trace, n = [], 5
+                for _ in range(n):
+                    step(x, y)
+                torch.cuda.synchronize()
+                rn = [t for t in step.dist.trace if t[0] == "syncbn_rn"]
+                res["trunk_allreduces_per_step"] = len(rn) // n
+                res["trunk_allreduce_bytes_per_step"] = sum(t[1] for t in rn) // n
+                res["trunk_allreduce_ms_per_step_%d_bags" % bags] = round(sum(t[2].elapsed_time(t[3]) for t in rn) / n, 3)
+                res["other_allreduces_per_step"] = (len(step.dist.trace) - len(rn)) // n
+                step.dist.trace = None
+                step.dist.close()
+        res["dist_overhead_ms_%d_bags" % bags] = round(res["train_step_%d_bags_ms_dist_one_rank" % bags] -
+                                                      res["train_step_%d_bags_ms_no_dist" % bags], 2)
+    os.environ.pop("MLA_DIST_ALWAYS", None)
+    print(json.dumps(res))
+    dist.destroy_process_group()
+
+
 def main():
     quick = "--quick" in sys.argv
     dev = torch.device("cuda")
     sd = {k: torch.as_tensor(v) for k, v in W.make_state_dict(21, W.ensemble_shapes((2, 1), True, cnn_type="resnet")).items()}
+    if "--dp-one-rank" in sys.argv:
+        return dp_one_rank(sd)
     if "--per-conv" in sys.argv:
         ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
         ens.load_state_dict(sd)
