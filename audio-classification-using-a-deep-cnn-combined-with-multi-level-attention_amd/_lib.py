@@ -136,6 +136,19 @@ def lib():
         L.mla_rn_bn_apply.argtypes = [vp, i64, i64, vp, vp, vp, ci, vp, ci, vp]
         L.mla_rn_maxpool.argtypes = [vp, i64, i64, i64, i64, vp, ci, vp]
         L.mla_rn_avgpool.argtypes = [vp, i64, i64, i64, vp, ci, vp]
+        L.mla_rn_repack_dgrad.argtypes = [vp, i64, i64, i64, vp, ci, vp]
+        L.mla_rn_conv_dgrad.argtypes = [vp, i64, i64, i64, i64, vp, i64, i64, i64, i64, i64, vp, vp, ci, vp]
+        L.mla_rn_conv_wgrad_workspace_floats.restype = i64
+        L.mla_rn_conv_wgrad_workspace_floats.argtypes = [i64, i64, i64, i64, i64, i64, ci]
+        L.mla_rn_conv_wgrad.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, i64, vp, i64, vp, ci, vp]
+        L.mla_rn_stem_wgrad_workspace_floats.restype = i64
+        L.mla_rn_stem_wgrad_workspace_floats.argtypes = [i64]
+        L.mla_rn_stem_wgrad.argtypes = [vp, i64, ci, vp, vp, i64, vp, ci, vp]
+        L.mla_rn_bn_bwd_workspace_bytes.restype = i64
+        L.mla_rn_bn_bwd_workspace_bytes.argtypes = [i64]
+        L.mla_rn_bn_bwd.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, cf, vp, vp, vp, vp, vp, ci, vp]
+        L.mla_rn_maxpool_bwd.argtypes = [vp, vp, i64, i64, i64, i64, vp, ci, vp]
+        L.mla_rn_avgpool_bwd.argtypes = [vp, i64, i64, i64, vp, ci, vp]
         _lib = L
     return _lib
 

@@ -14,6 +14,7 @@ Three stages, one Function each, chained by ordinary autograd (reshapes / transp
 * ``FeaturesFn``   -- the conv stack (vggish.py:108-118): ``VGGFeatures.forward``
 * ``EmbeddingsFn`` -- the three Linear + ReLU layers (vggish.py:13-19): ``VGGEmbeddings.forward``
 * ``HeadFn``       -- the whole multi-level-attention head (model.py:258-269): ``MultiLevelAttention.forward``
+* ``TrunkFn`` / ``FcFn`` -- the ResNet-50 trunk (train mode, when its trunk backward is on) and its fc (model.py:128-149)
 
 ``TrainStep`` (train.py of this package) stays the fast path: one flat gradient buffer, fused Adam, SyncBN and bucketed
 all-reduce. This module trades that for the reference's calling convention.
@@ -88,8 +89,8 @@ class EmbeddingsFn(torch.autograd.Function):
 
 
 class FcFn(torch.autograd.Function):
-    """apply(feats, w, b): ResNet.fc (model.py:148-149) on f32 (N, 2048) features of the frozen trunk -> (N, num_classes); the
-    backward returns the weight / bias gradients (the trunk below takes none)."""
+    """apply(feats, w, b): ResNet.fc (model.py:148-149) on f32 (N, 2048) trunk features -> (N, num_classes); the backward returns
+    the weight / bias gradients and, when the trunk below is being trained (TrunkFn), the features' gradient."""
 
     @staticmethod
     def forward(ctx, feats, w, b):
@@ -102,8 +103,33 @@ class FcFn(torch.autograd.Function):
         feats, w, b = ctx.saved_tensors
         dw = torch.empty(w.shape, dtype=torch.float32, device=dz.device)
         db = torch.empty(b.shape, dtype=torch.float32, device=dz.device)
-        ops.linear_small_bwd(feats, w.detach().contiguous(), dz.float().contiguous(), dw, db)
-        return None, (dw if ctx.needs_input_grad[1] else None), (db if ctx.needs_input_grad[2] else None)
+        da = ops.linear_small_bwd(feats, w.detach().contiguous(), dz.float().contiguous(), dw, db)
+        return (da if ctx.needs_input_grad[0] else None), (dw if ctx.needs_input_grad[1] else None), (db if ctx.needs_input_grad[2] else None)
+
+
+class TrunkFn(torch.autograd.Function):
+    """apply(cnn_model, x, precision, cache, *trunk parameters): the train-mode HIP ResNet-50 trunk (resnet.trunk_forward with a
+    tape) on the StemInput x -> f32 (N, 2048) features. The backward (resnet.trunk_backward) returns one f32 gradient per
+    parameter that requires one and None for the frozen ones, so ``p.grad`` behaves as for the torch modules."""
+
+    @staticmethod
+    def forward(ctx, cnn_model, x, precision, cache, *params):
+        from . import resnet
+        tape = {}
+        out = resnet.trunk_forward(cnn_model, x, precision, True, cache, tape=tape)
+        ctx.model, ctx.tape, ctx.params, ctx.device = cnn_model, tape, params, out.device
+        return out
+
+    @staticmethod
+    def backward(ctx, d_feats):
+        from . import resnet
+        tape, ctx.tape = ctx.tape, None
+        if tape is None:
+            raise RuntimeError("the ResNet trunk's tape has been consumed: backward through it a second time needs a second forward")
+        grads = {id(p): torch.empty(p.shape, dtype=torch.float32, device=ctx.device)
+                 for i, p in enumerate(ctx.params) if ctx.needs_input_grad[4 + i]}
+        resnet.trunk_backward(ctx.model, tape, d_feats.float().contiguous(), grads)
+        return (None, None, None, None) + tuple(grads.get(id(p)) for p in ctx.params)
 
 
 class CastFn(torch.autograd.Function):

@@ -72,7 +72,7 @@ class Dropout(nn.Module):
 
 class Ensemble(nn.Module):
     def __init__(self, input_conf: str, cnn_conf: Dict[str, Union[str, int]], model_conf: List[int], device,
-                 precision: str = "f32"):
+                 precision: str = "f32", trunk_backward: bool = False):
         super().__init__()
         self.cnn_type = cnn_conf["cnn_type"]
         self.just_bottlenecks = cnn_conf["just_bottlenecks"]
@@ -89,10 +89,14 @@ class Ensemble(nn.Module):
             raise Exception("CNN type is not valid.")
         self.input = Input(input_conf=input_conf, cnn_type=self.cnn_type, device=device)
         self.mla = MultiLevelAttention(model_conf, self.emb_input_size)
-        self.cnn = CNN(**cnn_conf, precision=precision)
+        self.cnn = CNN(**cnn_conf, precision=precision, trunk_backward=trunk_backward)
 
     def set_precision(self, precision):
         self.cnn.set_precision(precision)
+        return self
+
+    def set_trunk_backward(self, flag):
+        self.cnn.set_trunk_backward(flag)
         return self
 
     def forward(self, x):
@@ -208,9 +212,12 @@ class Input(nn.Module):
 
 class CNN(nn.Module):
     def __init__(self, cnn_type="vggish", num_classes=10, use_pretrained=True, just_bottlenecks=False,
-                 cnn_trainable=False, first_cnn_layer_trainable=False, in_channels=3, precision="f32"):
+                 cnn_trainable=False, first_cnn_layer_trainable=False, in_channels=3, precision="f32", trunk_backward=False):
         super().__init__()
         self.precision = precision
+        # cnn_type="resnet": gradients into the trunk (cnn_trainable / first_cnn_layer_trainable, model.py:131-136) run on the
+        # HIP trunk backward only when this is on; while off, a trunk parameter that requires grad raises. No-op for VGGish.
+        self.trunk_backward = bool(trunk_backward)
         if cnn_type == "vggish":
             model_urls = {"vggish": "https://github.com/harritaylor/torchvggish/releases/download/v0.1/vggish-10086976.pth"}
             self.cnn_model = VGGish(urls=model_urls, pretrained=use_pretrained, preprocess=False, postprocess=False,
@@ -251,8 +258,21 @@ class CNN(nn.Module):
                 m.precision = precision
         return self
 
+    def set_trunk_backward(self, flag):
+        """Turn the HIP backward of the ResNet-50 trunk on or off (models built by the reference's own constructor call or by
+        load_model); returns self. No effect for cnn_type="vggish", whose finetuning always runs."""
+        self.trunk_backward = bool(flag)
+        return self
+
     def forward(self, x):
         if self.cnn_type == "resnet":
+            if self.trunk_backward and torch.is_grad_enabled() and resnet.trunk_requires_grad(self.cnn_model):
+                if not self.training:
+                    raise NotImplementedError("the ResNet trunk backward differentiates the train-mode forward (batch statistics); "
+                                              "run eval-mode forwards under torch.no_grad() as _evaluate / test_model do")
+                params = [p for _, p in resnet.trunk_params(self.cnn_model)]
+                feats = differentiable.TrunkFn.apply(self.cnn_model, x, self.precision, self._rn_cache, *params)
+                return feats if self.just_bottlenecks else resnet.fc_forward(self.cnn_model.fc, feats)
             feats = resnet.trunk_forward(self.cnn_model, x, self.precision, self.training, self._rn_cache)
             return feats if self.just_bottlenecks else resnet.fc_forward(self.cnn_model.fc, feats)
         x = self.cnn_model(x)

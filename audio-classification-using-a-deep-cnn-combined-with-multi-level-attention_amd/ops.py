@@ -836,3 +836,90 @@ def rn_avgpool(x):
     out = torch.empty((n, C), dtype=torch.float32, device=x.device)
     _lib.check(_timed("rn_avgpool", _lib.lib().mla_rn_avgpool, _p(x), n, H * W_, C, _p(out), DT[x.dtype], _lib.stream_ptr()))
     return out
+
+
+# ---- backward of the ResNet-50 trunk (csrc/resnet_bwd.hip): gradients NHWC in the activations' dtype, weight gradients f32 ----
+# Workspaces are allocated per call from torch's caching allocator: inside a graph capture they belong to the graph's pool,
+# so no later eager call of another size can free memory a captured step still uses.
+
+def rn_repack_dgrad(w, dtype):
+    """Conv2d weight (O, I, k, k) f32 -> (I, k, k, O) in `dtype` with the taps flipped (data-gradient weights)."""
+    _chk(w, torch.float32)
+    cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
+    out = torch.empty((cin, ks, ks, cout), dtype=dtype, device=w.device)
+    _lib.check(_lib.lib().mla_rn_repack_dgrad(_p(w), cout, cin, ks, _p(out), DT[dtype], _lib.stream_ptr()))
+    return out
+
+
+def rn_conv_dgrad(dy, w_dgrad, stride, in_hw, residual=None):
+    """dy (N, Ho, Wo, Cout), dgrad weights (Cin, k, k, Cout) -> dx (N, H, W, Cin) [+ residual]; in_hw = (H, W)."""
+    _chk(dy); _chk(w_dgrad, dy.dtype)
+    n, Ho, Wo, cout = dy.shape
+    cin, ks = w_dgrad.shape[0], w_dgrad.shape[1]
+    H, W_ = in_hw
+    out = torch.empty((n, H, W_, cin), dtype=dy.dtype, device=dy.device)
+    if residual is not None:
+        _chk(residual, dy.dtype)
+        assert residual.shape == out.shape, (residual.shape, out.shape)
+    _lib.check(_timed("rn_dgrad%dx%d_s%d" % (ks, ks, stride), _lib.lib().mla_rn_conv_dgrad, _p(dy), n, Ho, Wo, cout, _p(w_dgrad), cin, ks,
+                      stride, H, W_, _p(residual), _p(out), DT[dy.dtype], _lib.stream_ptr()))
+    return out
+
+
+def rn_conv_wgrad(x, dy, stride, dw):
+    """x (N, H, W, Cin), dy (N, Ho, Wo, Cout) in one dtype -> dw (Cout, Cin, k, k) f32, written."""
+    _chk(x); _chk(dy, x.dtype); _chk(dw, torch.float32)
+    n, H, W_, cin = x.shape
+    cout, ks = dw.shape[0], dw.shape[2]
+    assert tuple(dw.shape) == (cout, cin, ks, ks) and dy.shape[3] == cout
+    L = _lib.lib()
+    need = int(L.mla_rn_conv_wgrad_workspace_floats(n, dy.shape[1], dy.shape[2], cin, cout, ks, DT[x.dtype]))
+    ws = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+    _lib.check(_timed("rn_wgrad%dx%d" % (ks, ks), L.mla_rn_conv_wgrad, _p(x), _p(dy), n, H, W_, cin, cout, ks, stride, _p(ws), ws.numel(),
+                      _p(dw), DT[x.dtype], _lib.stream_ptr()))
+
+
+def rn_stem_wgrad(planes, single, dy, dw):
+    """Raw (N, 224, 224) f32 planes and dy (N, 112, 112, 64) -> dw (64, 3, 7, 7) f32 of the stem conv (normalisation folded in)."""
+    _chk(planes, torch.float32); _chk(dy); _chk(dw, torch.float32)
+    n = planes.shape[0]
+    L = _lib.lib()
+    ws = torch.empty(int(L.mla_rn_stem_wgrad_workspace_floats(n)), dtype=torch.float32, device=planes.device)
+    _lib.check(_timed("rn_stem_wgrad", L.mla_rn_stem_wgrad, _p(planes), n, int(single), _p(dy), _p(ws), ws.numel(), _p(dw), DT[dy.dtype],
+                      _lib.stream_ptr()))
+
+
+def rn_bn_bwd(x, dy, mean, var, bn, y=None, want_dres=False, dgamma=None, dbeta=None):
+    """Train-mode BatchNorm2d backward: x the BatchNorm input, mean / var its (biased) batch statistics, y the kept ReLU output
+    (mask y > 0) or None. Returns (dx, dres): dres = the masked incoming gradient (residual path) when want_dres, else None.
+    dgamma / dbeta: f32 tensors to write, or None."""
+    _chk(x); _chk(dy, x.dtype)
+    if y is not None:
+        _chk(y, x.dtype)
+    C = x.shape[-1]
+    rows = x.numel() // C
+    L = _lib.lib()
+    ws = torch.empty(int(L.mla_rn_bn_bwd_workspace_bytes(C)) // 8, dtype=torch.float64, device=x.device)
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if want_dres else None
+    _lib.check(_timed("rn_bn_bwd", L.mla_rn_bn_bwd, _p(x), _p(dy), _p(y), rows, C, _p(mean), _p(var), _p(bn.weight.detach()), float(bn.eps),
+                      _p(ws), _p(dgamma), _p(dbeta), _p(dx), _p(dres), DT[x.dtype], _lib.stream_ptr()))
+    return dx, dres
+
+
+def rn_maxpool_bwd(x, dy):
+    """MaxPool2d(3, 2, 1) backward: x the pooled input (N, H, W, C), dy (N, Ho, Wo, C) -> dx like x."""
+    _chk(x); _chk(dy, x.dtype)
+    n, H, W_, C = x.shape
+    dx = torch.empty_like(x)
+    _lib.check(_timed("rn_maxpool_bwd", _lib.lib().mla_rn_maxpool_bwd, _p(x), _p(dy), n, H, W_, C, _p(dx), DT[x.dtype], _lib.stream_ptr()))
+    return dx
+
+
+def rn_avgpool_bwd(d, shape, dtype):
+    """AdaptiveAvgPool2d(1) backward: d (N, C) f32 -> (N, H, W, C) = d / (H W) in `dtype`; shape = (N, H, W, C)."""
+    _chk(d, torch.float32)
+    n, H, W_, C = shape
+    dx = torch.empty((n, H, W_, C), dtype=dtype, device=d.device)
+    _lib.check(_timed("rn_avgpool_bwd", _lib.lib().mla_rn_avgpool_bwd, _p(d), n, H * W_, C, _p(dx), DT[dtype], _lib.stream_ptr()))
+    return dx

@@ -6,8 +6,9 @@ attribute names, child order and parameter shapes, so that the reference's ``sta
 The modules are parameter holders; ``trunk_forward`` runs the whole trunk as HIP kernels (``csrc/resnet.hip``) on NHWC
 activations in the compute dtype: eval mode with the BatchNorm folded into the conv epilogues as an f32 scale/shift from
 the running statistics, train mode (the frozen trunk stays in train mode, ``set_requires_grad`` does not call ``eval``)
-with batch statistics and the running-statistics update. Gradients into the trunk are not built and raise; the ``fc``
-of ``just_bottlenecks=False`` (trainable in the reference) is differentiable (``fc_forward``).
+with batch statistics and the running-statistics update. Gradients into the trunk (``trunk_backward``, csrc/resnet_bwd.hip)
+are opt-in per model (``CNN.set_trunk_backward``) and raise while off; the ``fc`` of ``just_bottlenecks=False`` (trainable in
+the reference) is differentiable (``fc_forward``).
 """
 
 import math
@@ -149,19 +150,31 @@ def parts(cnn_model):
     return kids[0], kids[1], kids[4:8], None
 
 
+def trunk_params(cnn_model):
+    """(name, parameter) of the trunk: everything but the fc of just_bottlenecks=False."""
+    return [(n, p) for n, p in cnn_model.named_parameters() if not n.startswith("fc.")]
+
+
+def trunk_requires_grad(cnn_model):
+    return any(p.requires_grad for _, p in trunk_params(cnn_model))
+
+
 def _check_frozen(cnn_model):
     if not torch.is_grad_enabled():
         return
-    for name, p in cnn_model.named_parameters():
-        if p.requires_grad and not name.startswith("fc."):      # fc (just_bottlenecks=False) is trained: fc_forward
-            raise NotImplementedError("gradients into the ResNet trunk are not built (parameter cnn.cnn_model.%s requires grad); "
-                                      "train with cnn_trainable=False / first_cnn_layer_trainable=False" % name)
+    for name, p in trunk_params(cnn_model):
+        if p.requires_grad:               # fc (just_bottlenecks=False) is trained: fc_forward
+            raise NotImplementedError("gradients into the ResNet trunk are off (parameter cnn.cnn_model.%s requires grad); train with "
+                                      "cnn_trainable=False / first_cnn_layer_trainable=False, or turn the HIP trunk backward on with "
+                                      "CNN.set_trunk_backward(True) / Ensemble(..., trunk_backward=True)" % name)
 
 
-def trunk_forward(cnn_model, x, precision, training, cache, dist=None):
+def trunk_forward(cnn_model, x, precision, training, cache, dist=None, tape=None):
     """StemInput -> f32 (N, 2048) bottleneck features (avgpool + flatten) of the HIP trunk. dist: the ``ops.Dist`` of a
     data-parallel training step; in train mode its SyncBN setting decides whether the 53 BatchNorm2d statistics are those of
-    the global batch (one all-reduce per layer) or of this rank's shard."""
+    the global batch (one all-reduce per layer) or of this rank's shard. tape: a dict that receives what ``trunk_backward``
+    needs (train mode only): every BatchNorm's input (the raw conv output), batch statistics and output, and every block's
+    input; the BatchNorm outputs then go to new tensors instead of overwriting their inputs. Same results either way."""
     if not isinstance(x, StemInput):
         raise TypeError("the ResNet trunk takes the output of model.Input (raw 224 x 224 planes)")
     if precision not in _DTYPES:
@@ -172,6 +185,7 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None):
     planes = x.planes
     assert planes.dim() == 3 and tuple(planes.shape[1:]) == S_RESNET_SHAPE
     _check_frozen(cnn_model)
+    assert tape is None or training, "the trunk backward differentiates the train-mode forward"
     dtype = _DTYPES[precision]
     blocks = [b for layer in layers for b in layer]
     convs = [c for b in blocks for c in ([b.conv1, b.conv2, b.conv3] + ([b.downsample[0]] if b.downsample is not None else []))]
@@ -182,21 +196,36 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None):
         cache["bn"].key = None                    # the running statistics change below, behind torch's version counters
         dist = dist or ops._local()
         stats = lambda t, bn: ops.rn_bn_stats_sync(t, bn, dist)     # noqa: E731
+        if tape is not None:
+            tape.update(dtype=dtype, planes=planes, single=x.single, bn={}, block_in={})
+
+            def bn_apply(t, bn, residual=None, relu=False):
+                scale, shift, mean, var = ops.rn_bn_stats_sync(t, bn, dist, want_stats=True)
+                y = ops.rn_bn_apply(t, scale, shift, residual=residual, relu=relu, out=torch.empty_like(t))
+                tape["bn"][id(bn)] = (t, mean, var, y if relu else None)
+                return y
+        else:
+            def bn_apply(t, bn, residual=None, relu=False):
+                return ops.rn_bn_apply(t, *stats(t, bn), residual=residual, relu=relu)
         h = ops.rn_stem(planes, x.single, w1, dtype)
-        ops.rn_bn_apply(h, *stats(h, bn1), relu=True)
+        h = bn_apply(h, bn1, relu=True)
         h = ops.rn_maxpool(h)
         for b in blocks:
+            if tape is not None:
+                tape["block_in"][id(b)] = h
             o = ops.rn_conv(h, packed[id(b.conv1)], 1)
-            ops.rn_bn_apply(o, *stats(o, b.bn1), relu=True)
+            o = bn_apply(o, b.bn1, relu=True)
             o = ops.rn_conv(o, packed[id(b.conv2)], b.stride)
-            ops.rn_bn_apply(o, *stats(o, b.bn2), relu=True)
+            o = bn_apply(o, b.bn2, relu=True)
             if b.downsample is not None:
                 idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride)
-                ops.rn_bn_apply(idn, *stats(idn, b.downsample[1]))
+                idn = bn_apply(idn, b.downsample[1])
             else:
                 idn = h
             o = ops.rn_conv(o, packed[id(b.conv3)], 1)
-            h = ops.rn_bn_apply(o, *stats(o, b.bn3), residual=idn, relu=True)
+            h = bn_apply(o, b.bn3, residual=idn, relu=True)
+        if tape is not None:
+            tape["last_shape"] = tuple(h.shape)
         return ops.rn_avgpool(h)
     bns = [bn1] + [n for b in blocks for n in ([b.bn1, b.bn2, b.bn3] + ([b.downsample[1]] if b.downsample is not None else []))]
     tensors = [t for n in bns for t in (n.weight, n.bias, n.running_mean, n.running_var)]
@@ -209,6 +238,72 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None):
         idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride, *coef[id(b.downsample[1])]) if b.downsample is not None else h
         h = ops.rn_conv(o, packed[id(b.conv3)], 1, *coef[id(b.bn3)], residual=idn, relu=True)
     return ops.rn_avgpool(h)
+
+
+def trunk_backward(cnn_model, tape, d_feats, grads):
+    """Backward of the train-mode trunk forward recorded in `tape`: d_feats (N, 2048) f32, the gradient of the features ->
+    the f32 gradients of the trunk parameters in `grads` ({id(parameter): tensor to write}); only those are computed. The
+    blocks are walked in reverse (at a block input the main-path and skip-path gradients are summed by the conv epilogue)
+    down to the lowest unit holding a requested parameter; weight gradients nobody asked for are skipped. The tape is
+    consumed (its tensors are released as the walk passes them)."""
+    conv1, bn1, layers, _ = parts(cnn_model)
+    blocks = [b for layer in layers for b in layer]
+    units = [[conv1, bn1]] + [[b] for b in blocks]                 # unit 0: stem; unit k: blocks[k - 1]
+    wanted = [any(id(p) in grads for m in u for p in m.parameters()) for u in units]
+    if not any(wanted):
+        return
+    lowest = wanted.index(True)
+    dtype, bns = tape["dtype"], tape["bn"]
+    g = grads.get
+    d = ops.rn_avgpool_bwd(d_feats, tape["last_shape"], dtype)
+
+    def dgrad(dy, conv, in_hw, residual=None):
+        return ops.rn_conv_dgrad(dy, ops.rn_repack_dgrad(conv.weight.detach().contiguous(), dtype), conv.stride[0], in_hw, residual)
+
+    def wgrad(x, dy, conv):
+        if id(conv.weight) in grads:
+            ops.rn_conv_wgrad(x, dy, conv.stride[0], grads[id(conv.weight)])
+
+    def bn_bwd(bn, dy, want_dres=False):
+        x, mean, var, y = bns.pop(id(bn))
+        return ops.rn_bn_bwd(x, dy, mean, var, bn, y=y, want_dres=want_dres, dgamma=g(id(bn.weight)), dbeta=g(id(bn.bias)))
+
+    for k in range(len(blocks), max(lowest, 1) - 1, -1):
+        b = blocks[k - 1]
+        h_in = tape["block_in"].pop(id(b))
+        a2 = bns[id(b.bn2)][3]
+        do3, g3 = bn_bwd(b.bn3, d, want_dres=True)
+        wgrad(a2, do3, b.conv3)
+        da2 = dgrad(do3, b.conv3, a2.shape[1:3])
+        del do3
+        a1 = bns[id(b.bn1)][3]
+        do2, _ = bn_bwd(b.bn2, da2)
+        del da2
+        wgrad(a1, do2, b.conv2)
+        da1 = dgrad(do2, b.conv2, a1.shape[1:3])
+        del do2
+        do1, _ = bn_bwd(b.bn1, da1)
+        del da1
+        wgrad(h_in, do1, b.conv1)
+        below = lowest < k                                        # a unit under this block wants a gradient
+        if b.downsample is not None:
+            dds, _ = bn_bwd(b.downsample[1], g3)
+            wgrad(h_in, dds, b.downsample[0])
+            skip = dgrad(dds, b.downsample[0], h_in.shape[1:3]) if below else None
+            del dds
+        else:
+            skip = g3
+        del g3
+        d = dgrad(do1, b.conv1, h_in.shape[1:3], residual=skip) if below else None
+        del do1, skip, h_in
+    if lowest == 0:                                               # d: gradient of the maxpool output
+        a0 = bns[id(bn1)][3]
+        da0 = ops.rn_maxpool_bwd(a0, d)
+        dh0, _ = bn_bwd(bn1, da0)
+        del da0
+        if id(conv1.weight) in grads:
+            ops.rn_stem_wgrad(tape["planes"], tape["single"], dh0, grads[id(conv1.weight)])
+    tape.clear()
 
 
 def fc_forward(fc, feats):

@@ -87,13 +87,22 @@ class TrainStep:
             raise ValueError("no trainable parameter to update")
         self.resnet = getattr(clf, "cnn_type", "vggish") == "resnet"
         self.rn_fc = False
+        self.rn_trunk = {}                                # id(trunk parameter) -> its gradient view (trunk backward on)
+        trunk_names = set()
         if self.resnet:
-            # the ResNet trunk runs its train-mode forward inside the step (batch statistics, running-statistics update) with
-            # no tape; trained are the head and, with just_bottlenecks=False, cnn.cnn_model.fc (model.py:148-149)
+            # the ResNet trunk runs its train-mode forward inside the step (batch statistics, running-statistics update); trained
+            # are the head, with just_bottlenecks=False cnn.cnn_model.fc (model.py:148-149), and -- with the trunk backward on
+            # (CNN.set_trunk_backward) -- the trunk parameters in the update set, through a tape of the forward
             self.rn_fc = any(n.startswith(self.RN_FC) for n, _ in named)
             trunk = [n for n, _ in named if n.startswith("cnn.") and not n.startswith(self.RN_FC)]
-            if trunk:
-                raise NotImplementedError("gradients into the ResNet trunk are not built (parameter %s is in the update set)" % trunk[0])
+            trunk_names = set(trunk)
+            if trunk and not getattr(clf.cnn, "trunk_backward", False):
+                raise NotImplementedError("gradients into the ResNet trunk are off (parameter %s is in the update set); turn the HIP "
+                                          "trunk backward on with clf.set_trunk_backward(True)" % trunk[0])
+            if trunk and (self.dist.active or self.dist.backend is not None):       # under a torch.distributed process group
+                raise NotImplementedError("data-parallel training of the ResNet trunk is not built: its SyncBN backward needs sum(dy) "
+                                          "and sum(dy * xhat) all-reduced per BatchNorm2d layer (parameter %s is in the update set); "
+                                          "frozen-trunk data parallelism is supported" % trunk[0])
         # CNN gradients are needed iff the update set holds a CNN parameter; any subset of the CNN is fine (the backward
         # pass stops at the lowest layer that needs a gradient and skips the weight gradients nobody asked for)
         self.finetune = not self.resnet and any(n.startswith("cnn.") for n, _ in named)
@@ -119,7 +128,9 @@ class TrainStep:
             p.data = self.flat_p[off:off + k].view(p.shape)
             self.grads[n] = self.flat_g[off:off + k].view(p.shape)
             self._seated.append((n, p, self.flat_p.data_ptr() + 4 * off))
-            b = self._bucket_of(n)
+            if n in trunk_names:
+                self.rn_trunk[id(p)] = self.grads[n]
+            b = "rn_trunk" if n in trunk_names else self._bucket_of(n)        # the ResNet trunk: one range (no overlap bucketing)
             spans[b] = [min(spans.get(b, [off, 0])[0], off), off + pad4(k)]
             off += pad4(k)
         # Gradient buckets of the data-parallel exchange: contiguous ranges of the flat gradient buffer that become final
@@ -243,6 +254,8 @@ class TrainStep:
         rn = getattr(self.clf.cnn, "_rn_cache", None)
         if rn is not None:                         # the replay moved the ResNet running statistics on the device: eval coefficients are stale
             rn["bn"].key = None
+            if self.rn_trunk:                      # and Adam the trunk weights, behind torch's version counters: so are the repacks
+                rn["w"].key = None
         if self.finetune:                          # the graph re-derives its own weight copies; anything cached outside it is stale
             for m in self.clf.cnn.modules():
                 if hasattr(m, "_cache"):
@@ -261,7 +274,8 @@ class TrainStep:
         elif self.resnet:                      # trunk in train mode; its SyncBN statistics go through self.dist
             from . import resnet
             m = clf.cnn.cnn_model
-            feats = resnet.trunk_forward(m, x, clf.cnn.precision, True, clf.cnn._rn_cache, dist=self.dist)
+            rn_tape = {} if self.rn_trunk else None
+            feats = resnet.trunk_forward(m, x, clf.cnn.precision, True, clf.cnn._rn_cache, dist=self.dist, tape=rn_tape)
             if self.rn_fc:                     # ResNet fc (just_bottlenecks=False): trunk features kept for the fc weight gradient
                 rn_feats = feats
                 feats = ops.linear_small(rn_feats, m.fc.weight.detach(), m.fc.bias.detach())
@@ -272,14 +286,18 @@ class TrainStep:
         ctx = mla_train.Ctx(tape=True, dist=self.dist, counter=self.step_dev if captured else None, bases=bases)
         out = mla_train.mla_forward(clf.mla, feats.reshape(-1, T, clf.emb_input_size), ctx)
         loss, dout, hits = ops.cross_entropy(out, labels, 1.0 / B_global)
-        d_feats = mla_train.mla_backward(clf.mla, ctx, dout, self.mla_grads, need_input_grad=self.finetune or self.rn_fc)
+        d_feats = mla_train.mla_backward(clf.mla, ctx, dout, self.mla_grads,
+                                         need_input_grad=self.finetune or self.rn_fc or bool(self.rn_trunk))
         if self.rn_fc:
             fc = clf.cnn.cnn_model.fc
             gw = self.grads.get(self.RN_FC + "weight")
             gb = self.grads.get(self.RN_FC + "bias")
-            ops.linear_small_bwd(rn_feats, fc.weight.detach(), d_feats.contiguous(),
-                                 gw if gw is not None else torch.empty_like(fc.weight, dtype=torch.float32),
-                                 gb if gb is not None else torch.empty_like(fc.bias, dtype=torch.float32))
+            d_feats = ops.linear_small_bwd(rn_feats, fc.weight.detach(), d_feats.contiguous(),
+                                           gw if gw is not None else torch.empty_like(fc.weight, dtype=torch.float32),
+                                           gb if gb is not None else torch.empty_like(fc.bias, dtype=torch.float32))
+        if self.rn_trunk:                      # head -> fc -> trunk: the trunk's gradients land in the flat buffer
+            from . import resnet
+            resnet.trunk_backward(clf.cnn.cnn_model, rn_tape, d_feats.reshape(-1, 2048).contiguous(), self.rn_trunk)
         bucketed = self.dist.active and self.finetune and self.overlap
         if bucketed:
             # the head's gradients are final: reduce them while the CNN backward runs; each CNN bucket follows as soon as
@@ -320,6 +338,8 @@ class TrainStep:
                 for m in clf.cnn.modules():
                     if hasattr(m, "_cache"):
                         m._cache.key = None
+            if self.rn_trunk:                      # so are the ResNet trunk's repacked weights (Adam writes behind the version counters)
+                clf.cnn._rn_cache["w"].key = None
         return loss, hits, out
 
 

@@ -467,6 +467,47 @@ int mla_rn_maxpool(const void* in, int64_t n, int64_t H, int64_t W, int64_t chan
 /* resnet.avgpool + CnnFlatten (model.py:188): AdaptiveAvgPool2d(1) of NHWC (n, hw, channels) -> f32 (n, channels). */
 int mla_rn_avgpool(const void* in, int64_t n, int64_t hw, int64_t channels, float* out, int dtype, mla_stream_t stream);
 
+/* --- backward of the trunk: cnn_trainable / first_cnn_layer_trainable finetuning (model.py:131-136, loss.backward()
+ *     train.py:137). Activations and gradients NHWC in MLA_F32 or MLA_BF16 (f32 accumulation), weight gradients f32 OIHW,
+ *     written (not accumulated). No float atomics; every reduction runs in a fixed order (bit-identical runs). --- */
+
+/* Conv2d weight OIHW f32 (cout, cin, ks, ks) -> [cin][ks][ks][cout] in `dtype` with the taps flipped: the weights of the
+ * data gradient (a stride-1 data gradient is mla_rn_conv on them). */
+int mla_rn_repack_dgrad(const float* w_oihw, int64_t cout, int64_t cin, int64_t ks, void* out, int dtype, mla_stream_t stream);
+/* Data gradient of a Bottleneck / downsample conv (model.py:129): dy (n, Ho, Wo, cout) and w_dgrad from mla_rn_repack_dgrad ->
+ * dx (n, H, W, cin) [+ residual, same shape as dx: the other branch's gradient]. stride 1: H == Ho; stride 2: H == 2 Ho (four
+ * parity classes of input pixel, each with its own tap subset; positions no tap reaches receive the residual alone). */
+int mla_rn_conv_dgrad(const void* dy, int64_t n, int64_t Ho, int64_t Wo, int64_t cout, const void* w_dgrad, int64_t cin, int64_t ks,
+                      int64_t stride, int64_t H, int64_t W, const void* residual, void* dx, int dtype, mla_stream_t stream);
+/* Weight gradient dw (cout, cin, ks, ks) f32 of the conv of mla_rn_conv from its input x (n, H, W, cin) and dy (n, Ho, Wo, cout):
+ * a GEMM over the n*Ho*Wo output pixels, split into a shape-determined number of ranges whose f32 partials are added in range
+ * order. workspace: mla_rn_conv_wgrad_workspace_floats(n, Ho, Wo, cin, cout, ks, dtype) floats. */
+int64_t mla_rn_conv_wgrad_workspace_floats(int64_t n, int64_t Ho, int64_t Wo, int64_t cin, int64_t cout, int64_t ks, int dtype);
+int mla_rn_conv_wgrad(const void* x, const void* dy, int64_t n, int64_t H, int64_t W, int64_t cin, int64_t cout, int64_t ks,
+                      int64_t stride, float* workspace, int64_t workspace_floats, float* dw_oihw, int dtype, mla_stream_t stream);
+/* Weight gradient of the stem (Input.forward model.py:84-101 + resnet.conv1): dw (64, 3, 7, 7) f32 from the raw planes x (n, 224, 224)
+ * f32 and dy (n, 112, 112, 64) in dtype. The normalisation is folded in: per (o, tap) S1 = sum dy x and S0 = sum dy over the
+ * taps inside the image, dw[o][c][tap] = inv_c ([c carries x] S1 - mean_c S0) (single: x in channel 0 only).
+ * workspace: mla_rn_stem_wgrad_workspace_floats(n) floats. */
+int64_t mla_rn_stem_wgrad_workspace_floats(int64_t n);
+int mla_rn_stem_wgrad(const float* x, int64_t n, int single, const void* dy, float* workspace, int64_t workspace_floats, float* dw,
+                      int dtype, mla_stream_t stream);
+/* BatchNorm2d train-mode backward (bn1..bn3 / downsample.1 / resnet.bn1): x = the BatchNorm input (raw conv output), mean /
+ * var_biased its batch statistics (mla_rn_bn_stats), g = dy masked by y > 0 when y (the kept ReLU output) is non-NULL.
+ * dx = gamma invstd (g - mean(g) - xhat mean(g xhat)); dres (or NULL) receives g itself (the residual-path gradient of
+ * `relu(bn3 + identity)`); dgamma = sum g xhat, dbeta = sum g (each NULL to skip). Sums in double in the row-slice order
+ * of the statistics kernels. workspace: mla_rn_bn_bwd_workspace_bytes(channels) bytes. */
+int64_t mla_rn_bn_bwd_workspace_bytes(int64_t channels);
+int mla_rn_bn_bwd(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean, const float* var_biased,
+                  const float* gamma, float eps, void* workspace, float* dgamma, float* dbeta, void* dx, void* dres, int dtype,
+                  mla_stream_t stream);
+/* Backward of mla_rn_maxpool (resnet.maxpool, model.py:129): in (n, H, W, channels) the pooled input, dy the pooled gradient ->
+ * dx (n, H, W, channels). Gradient routed to the FIRST maximum of each window in torch's scan order (ky-major, strict >). */
+int mla_rn_maxpool_bwd(const void* in, const void* dy, int64_t n, int64_t H, int64_t W, int64_t channels, void* dx, int dtype,
+                       mla_stream_t stream);
+/* Backward of mla_rn_avgpool (resnet.avgpool + CnnFlatten, model.py:188): d (n, channels) f32 -> dx (n, hw, channels) = d / hw. */
+int mla_rn_avgpool_bwd(const float* d, int64_t n, int64_t hw, int64_t channels, void* dx, int dtype, mla_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

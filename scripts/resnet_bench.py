@@ -3,12 +3,15 @@
 5 120 images, the frozen training step (TrainStep) at 8 and 64 bags, and -- as a yardstick only -- the same network built
 from torch.nn.functional.conv2d in channels-last bf16 (MIOpen). Prints one JSON line.
 
-    python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank]
+    python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank] [--finetune]
 
 --per-conv: instead, each distinct bf16 conv (and the stem) timed alone at 80 images against its own roofline.
 --dp-one-rank: instead, the cost of the trunk's SyncBN on one GPU: the frozen bf16 step (eager) at 8 and 64 bags without a
 process group and on a one-rank RCCL group with the collectives forced on (ops.Dist(always=True)), where each of the 53
 BatchNorm2d layers runs sums -> all-reduce -> finish; the all-reduces are counted and timed from ops.Dist.trace.
+--finetune: instead, the trunk-finetuning step (cnn_trainable=True with the HIP trunk backward on, TrainStep, default graph
+mode) in bf16 and f32 at 8 and 64 bags next to the frozen bf16 step, and torch autograd's forward + backward of the restated
+ResNet-50 trunk (channels-last bf16, MIOpen, train mode) as the yardstick; writes profiles/resnet_finetune.json.
 """
 
 import importlib
@@ -150,12 +153,54 @@ def dp_one_rank(sd):
     dist.destroy_process_group()
 
 
+def finetune(sd):
+    """See --finetune in the module docstring."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import resnet50_restated as R
+    dev = torch.device("cuda")
+    res = {"metric": "resnet50_finetune_step", "device": torch.cuda.get_device_name(0), "just_bottlenecks": True, "optimizer": "adam lr 1e-4"}
+    for bags in (8, 64):
+        x = torch.rand(bags, 10, 1, 224, 224, device=dev)
+        y = torch.arange(bags, device=dev) % 10
+        for prec, trainable in (("bf16", False), ("bf16", True), ("f32", True)):
+            ens = M.Ensemble("repeat", dict(CONF, cnn_trainable=trainable), [2, 1], dev, precision=prec, trunk_backward=True)
+            ens.load_state_dict(sd)
+            ens.cuda()
+            step = TR.TrainStep(ens, lr=1e-4)
+            torch.cuda.reset_peak_memory_stats()
+            t = timeit(lambda: step(x, y), 3, 5)
+            key = "%s_%s_%d_bags" % ("finetune" if trainable else "frozen", prec, bags)
+            res[key + "_ms"] = round(t * 1e3, 2)
+            res[key + "_peak_gb"] = round(torch.cuda.max_memory_allocated() / 1e9, 2)
+            del ens, step
+            torch.cuda.empty_cache()
+        m = R.CNN(True).cuda().to(torch.bfloat16).to(memory_format=torch.channels_last).train()
+        for p in m.parameters():
+            p.requires_grad_(True)
+        xin = R.normalize_input(x, "repeat").to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+        def torch_step():
+            for p in m.parameters():
+                p.grad = None
+            m(xin).float().sum().backward()
+        res["torch_autograd_trunk_fwd_bwd_bf16_%d_bags_ms" % bags] = round(timeit(torch_step, 3, 5) * 1e3, 2)
+        del m, xin
+        torch.cuda.empty_cache()
+        res["finetune_over_frozen_bf16_%d_bags" % bags] = round(res["finetune_bf16_%d_bags_ms" % bags] / res["frozen_bf16_%d_bags_ms" % bags], 2)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "resnet_finetune.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     quick = "--quick" in sys.argv
     dev = torch.device("cuda")
     sd = {k: torch.as_tensor(v) for k, v in W.make_state_dict(21, W.ensemble_shapes((2, 1), True, cnn_type="resnet")).items()}
     if "--dp-one-rank" in sys.argv:
         return dp_one_rank(sd)
+    if "--finetune" in sys.argv:
+        return finetune(sd)
     if "--per-conv" in sys.argv:
         ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
         ens.load_state_dict(sd)
