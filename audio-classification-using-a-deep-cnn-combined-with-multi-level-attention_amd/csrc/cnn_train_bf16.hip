@@ -29,23 +29,6 @@ using namespace mma;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-// eight consecutive channels as floats, from bf16 (one 16-byte load) or f32 (two)
-template <typename T> __device__ __forceinline__ void load8(const T* p, float* v);
-template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* p, float* v) {
-    const u32x4 u = *reinterpret_cast<const u32x4*>(p);
-    _Pragma("unroll") for (int k = 0; k < 4; ++k) {
-        v[2 * k] = __builtin_bit_cast(float, u[k] << 16);
-        v[2 * k + 1] = __builtin_bit_cast(float, u[k] & 0xffff0000u);
-    }
-}
-template <> __device__ __forceinline__ void load8<float>(const float* p, float* v) {
-    const f32x4 a = reinterpret_cast<const f32x4*>(p)[0], b = reinterpret_cast<const f32x4*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void store8(bf16_t* p, const float* v) {
-    *reinterpret_cast<u32x4*>(p) = u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-}
-
 __global__ __launch_bounds__(256) void maxpool_bf16_kernel(const bf16_t* __restrict__ a, bf16_t* __restrict__ out, int64_t n_out,
                                                            int H, int W, int C) {
     const int c8 = C / 8, WO = W / 2, HO = H / 2;

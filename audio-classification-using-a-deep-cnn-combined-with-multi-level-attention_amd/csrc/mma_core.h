@@ -1,4 +1,4 @@
-// mma_core.h -- shared device pieces of the MFMA kernels (conv.hip, gemm.hip).
+// mma_core.h -- shared device pieces of the MFMA kernels (conv.hip, gemm.hip, cnn_train*.hip, resnet.hip, resnet_bwd.hip).
 //
 // Geometry shared by the bf16 and the f32 ("parity") modes: every LDS tile row is 128 bytes
 // = 8 chunks of 16 B (64 bf16 or 32 f32 channels of one pixel / one weight row). One "k-step"
@@ -59,6 +59,36 @@ template <> __device__ __forceinline__ void store_elem<bf16_t>(bf16_t* p, float 
 template <typename T> __device__ __forceinline__ float load_elem(const T* p);
 template <> __device__ __forceinline__ float load_elem<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float load_elem<bf16_t>(const bf16_t* p) { return bf2f(p->bits); }
+
+// eight consecutive channels as floats, from / to bf16 (one 16-byte access) or f32 (two)
+template <typename T>
+__device__ __forceinline__ void load8(const T* p, float* v) {
+    if constexpr (sizeof(T) == 2) {
+        const u32x4 u = *reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[2 * k] = __builtin_bit_cast(float, u[k] << 16);
+            v[2 * k + 1] = __builtin_bit_cast(float, u[k] & 0xFFFF0000u);
+        }
+    } else {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { v[k] = a[k]; v[4 + k] = b[k]; }
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void store8(T* p, const float* v) {
+    if constexpr (sizeof(T) == 2) {
+        u32x4 u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) u[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
+        *reinterpret_cast<u32x4*>(p) = u;
+    } else {
+        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    }
+}
 
 // one k-step of a 16x16 tile: acc += A(16 x 4 chunks) * B(4 chunks x 16)
 template <typename T> __device__ __forceinline__ void mma_step(const u32x4& a, const u32x4& b, f32x4& acc);

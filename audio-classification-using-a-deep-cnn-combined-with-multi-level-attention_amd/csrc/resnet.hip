@@ -11,20 +11,17 @@
 //                     the finish around an all-reduce of [sum x, sum x^2, rows] (SyncBN across data-parallel ranks)
 //   rn_bn_apply_kernel  y = x * scale + shift [+ residual] [ReLU] (train mode)
 //   rn_maxpool_kernel   MaxPool2d(3, 2, 1);  rn_avgpool_kernel  AdaptiveAvgPool2d(1) -> f32 (N, C)
-#include "common.h"
-#include "mma_core.h"
+#include "rn_core.h"
 
 namespace {
 
-using mma::bf16_t;
-using mma::f32x4;
-using mma::u32x4;
+using namespace rn;
+using mma::load8;
+using mma::store8;
 
 // ------------------------------------------------------------------------------------------------
 // stem: x (N, 224, 224) f32 -> out NHWC (N, 112, 112, 64)
 // ------------------------------------------------------------------------------------------------
-constexpr int kImg = 224, kStemOut = 112, kStemC = 64;
-
 template <typename T>
 __global__ __launch_bounds__(256) void rn_stem_kernel(const float* __restrict__ x, int single, const float* __restrict__ w,
                                                       const float* __restrict__ scale, const float* __restrict__ shift,
@@ -38,13 +35,12 @@ __global__ __launch_bounds__(256) void rn_stem_kernel(const float* __restrict__ 
         xs[ky][ix] = (iy >= 0 && iy < kImg) ? x[(n * kImg + iy) * kImg + ix] : 0.f;
     }
     // per-tap coefficients of the normalised channels: sum_c w_c (x_c - m_c) / s_c = a x + b for a tap inside the image
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, inv[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
     float a[49], b[49];
 #pragma unroll
     for (int k = 0; k < 49; ++k) {
         const float w0 = w[(o * 3 + 0) * 49 + k], w1 = w[(o * 3 + 1) * 49 + k], w2 = w[(o * 3 + 2) * 49 + k];
-        a[k] = single ? w0 * inv[0] : w0 * inv[0] + w1 * inv[1] + w2 * inv[2];
-        b[k] = -(w0 * mean[0] * inv[0] + w1 * mean[1] * inv[1] + w2 * mean[2] * inv[2]);
+        a[k] = single ? w0 * kNormInv[0] : w0 * kNormInv[0] + w1 * kNormInv[1] + w2 * kNormInv[2];
+        b[k] = -(w0 * kNormMean[0] * kNormInv[0] + w1 * kNormMean[1] * kNormInv[1] + w2 * kNormMean[2] * kNormInv[2]);
     }
     __syncthreads();
     const float sc = scale ? scale[o] : 1.f, sh = scale ? shift[o] : 0.f;
@@ -67,30 +63,19 @@ __global__ __launch_bounds__(256) void rn_stem_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// implicit-GEMM conv: rows = output pixels (N*Ho*Wo), cols = Cout, K = KS*KS*Cin (tap-major, channel-minor).
-// Workgroup tile 128 pixels x BN channels, 4 waves as 2 x 2, one 128-byte LDS row per pixel / weight row per k-block
-// (64 bf16 or 32 f32 channels of one tap). The next k-block is loaded into registers while the current one computes.
+// implicit-GEMM conv: rows = output pixels (N*Ho*Wo), cols = Cout, K = KS*KS*Cin, on the tile of rn_core.h (conv_tile).
 // ------------------------------------------------------------------------------------------------
 template <typename T, int BN>
 __global__ __launch_bounds__(256) void rn_conv_kernel(const T* __restrict__ in, const T* __restrict__ w, T* __restrict__ out,
                                                       const float* __restrict__ scale, const float* __restrict__ shift,
                                                       const T* __restrict__ res, int relu, int64_t M, int H, int W, int Cin,
                                                       int Ho, int Wo, int Cout, int KS, int stride, int pad) {
-    constexpr int EPC = mma::Elem<T>::kPerChunk, EPR = mma::Elem<T>::kPerRow;
-    constexpr int BM = 128, AL = BM * 8 / 256, BL = BN * 8 / 256, TN = BN / 32;
-    __shared__ __attribute__((aligned(16))) char lds[(BM + BN) * mma::kRowBytes];
-    char* As = lds;
-    char* Bs = lds + BM * mma::kRowBytes;
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, q = t & 7, r0 = t >> 3;
-    const int64_t m0 = int64_t(blockIdx.x) * BM;
-    const int n0 = blockIdx.y * BN;
-
-    int64_t abase[AL];
-    int aiy[AL], aix[AL];
-    bool aval[AL];
+    int64_t abase[kTileAL];
+    int aiy[kTileAL], aix[kTileAL];
+    bool aval[kTileAL];
 #pragma unroll
-    for (int i = 0; i < AL; ++i) {
-        const int64_t m = m0 + r0 + 32 * i;
+    for (int i = 0; i < kTileAL; ++i) {
+        const int64_t m = int64_t(blockIdx.x) * kTileM + (threadIdx.x >> 3) + 32 * i;
         aval[i] = m < M;
         const int64_t mm = aval[i] ? m : 0;
         const int ox = int(mm % Wo);
@@ -100,74 +85,25 @@ __global__ __launch_bounds__(256) void rn_conv_kernel(const T* __restrict__ in, 
         aiy[i] = oy * stride - pad;
         aix[i] = ox * stride - pad;
     }
-    const int KK = KS * KS, csteps = Cin / EPR, nk = KK * csteps;
-    u32x4 ra[AL], rb[BL];
-    auto load = [&](int k) {
-        const int tap = k / csteps, cs = k - tap * csteps, ky = tap / KS, kx = tap - ky * KS;
-        const int c0 = cs * EPR + q * EPC;
-#pragma unroll
-        for (int i = 0; i < AL; ++i) {
+    conv_tile<T, BN, false>(                     // never empty: KS * KS >= 1 taps, Cin >= 64 (mla_rn_conv checks both)
+        w, KS * KS, Cin, KS * KS, M,
+        [&](int i, int tap, int c0) {
+            const int ky = tap / KS, kx = tap - ky * KS;
             const int iy = aiy[i] + ky, ix = aix[i] + kx;
             const bool ok = aval[i] && iy >= 0 && iy < H && ix >= 0 && ix < W;
-            ra[i] = ok ? *reinterpret_cast<const u32x4*>(in + ((abase[i] + iy) * W + ix) * Cin + c0) : mma::zero16();
-        }
-#pragma unroll
-        for (int j = 0; j < BL; ++j) {
-            const int64_t co = n0 + r0 + 32 * j;
-            rb[j] = *reinterpret_cast<const u32x4*>(w + (co * KK + tap) * Cin + c0);
-        }
-    };
-
-    f32x4 acc[4][TN];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int wm = wid & 1, wn = wid >> 1;
-    load(0);
-    for (int k = 0; k < nk; ++k) {
-#pragma unroll
-        for (int i = 0; i < AL; ++i) mma::lds_write16(As, mma::tile_off(r0 + 32 * i, q), ra[i]);
-#pragma unroll
-        for (int j = 0; j < BL; ++j) mma::lds_write16(Bs, mma::tile_off(r0 + 32 * j, q), rb[j]);
-        __syncthreads();
-        if (k + 1 < nk) load(k + 1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int ch = ks * 4 + (lane >> 4);
-            u32x4 a[4], b[TN];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = mma::lds_read16(As, mma::tile_off(wm * 64 + i * 16 + (lane & 15), ch));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = mma::lds_read16(Bs, mma::tile_off(wn * (BN / 2) + j * 16 + (lane & 15), ch));
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) mma::mma_step<T>(a[i], b[j], acc[i][j]);
-        }
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int co = n0 + wn * (BN / 2) + j * 16 + (lane & 15);
-        const float sc = scale ? scale[co] : 1.f, sh = scale ? shift[co] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int64_t m = m0 + wm * 64 + i * 16 + 4 * (lane >> 4) + e;
-                if (m >= M) continue;
+            return ok ? *reinterpret_cast<const u32x4*>(in + ((abase[i] + iy) * W + ix) * Cin + c0) : mma::zero16();
+        },
+        [](int tap) { return tap; },
+        [&](int co) {
+            const float sc = scale ? scale[co] : 1.f, sh = scale ? shift[co] : 0.f;
+            return [=](int64_t m, float v) {
                 const int64_t off = m * Cout + co;
-                float v = acc[i][j][e];
                 if (scale) v = v * sc + sh;
                 if (res) v += mma::load_elem<T>(res + off);
                 if (relu) v = fmaxf(v, 0.f);
                 mma::store_elem<T>(out + off, v);
-            }
-        }
-    }
+            };
+        });
 }
 
 // OIHW f32 -> [O][KH][KW][I] in T
@@ -184,76 +120,16 @@ __global__ void rn_repack_kernel(const float* __restrict__ w, T* __restrict__ ou
 }
 
 // ------------------------------------------------------------------------------------------------
-// BatchNorm2d statistics: block (channel group of 64, row slice p). Thread: 8 channels (chunk q) of rows r0, r0+32, ...
-// of its slice; sums in double; the 32 row lanes are added in LDS in a fixed order, the P slices by the finish kernel
-// in a fixed order -> the same bits on every run for a given shape.
+// BatchNorm2d statistics: sum x and sum x^2 by (channel group, row slice) with bn_slice_sums (rn_core.h); the finish
+// kernels add the slices in slice order.
 // ------------------------------------------------------------------------------------------------
-constexpr int kMaxSlices = 512;
-
-int bn_slices(int64_t rows) {
-    const int64_t p = (rows + 2047) / 2048;
-    return int(p < 1 ? 1 : (p > kMaxSlices ? kMaxSlices : p));
-}
-
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float* v) {
-    if constexpr (sizeof(T) == 2) {
-        const u32x4 u = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[2 * k] = __builtin_bit_cast(float, u[k] << 16);
-            v[2 * k + 1] = __builtin_bit_cast(float, u[k] & 0xFFFF0000u);
-        }
-    } else {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k] = a[k]; v[4 + k] = b[k]; }
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void store8(T* p, const float* v) {
-    if constexpr (sizeof(T) == 2) {
-        u32x4 u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) u[k] = mma::pack_bf16x2(v[2 * k], v[2 * k + 1]);
-        *reinterpret_cast<u32x4*>(p) = u;
-    } else {
-        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void rn_bn_partial_kernel(const T* __restrict__ x, int64_t rows, int C, double* __restrict__ part) {
-    __shared__ double red[2][32][64];
-    const int t = threadIdx.x, q = t & 7, r0 = t >> 3;
-    const int c0 = blockIdx.x * 64 + q * 8, P = gridDim.y, p = blockIdx.y;
-    double s[8], s2[8];
+    bn_slice_sums(rows, C, part, [&](int64_t off, int, float* a, float* b) {
+        load8<T>(x + off, a);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] = s2[k] = 0.0;
-    for (int64_t r = int64_t(p) * 32 + r0; r < rows; r += int64_t(P) * 32) {
-        float v[8];
-        load8<T>(x + r * C + c0, v);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { s[k] += v[k]; s2[k] += double(v[k]) * v[k]; }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { red[0][r0][q * 8 + k] = s[k]; red[1][r0][q * 8 + k] = s2[k]; }
-    __syncthreads();
-    if (t < 128) {
-        const int which = t >> 6, c = t & 63;
-        double acc = 0.0;
-        for (int i = 0; i < 32; ++i) acc += red[which][i][c];
-        part[(int64_t(which) * P + p) * C + blockIdx.x * 64 + c] = acc;
-    }
-}
-
-// The P slices of one channel, added in slice order: the fixed order that rn_bn_finish_kernel and rn_bn_sums_kernel share.
-__device__ __forceinline__ void bn_sum_slices(const double* __restrict__ part, int P, int C, int c, double& s, double& s2) {
-    s = 0.0;
-    s2 = 0.0;
-    for (int p = 0; p < P; ++p) { s += part[int64_t(p) * C + c]; s2 += part[int64_t(P + p) * C + c]; }
+        for (int k = 0; k < 8; ++k) b[k] = a[k];
+    });
 }
 
 // One channel's statistics from its sums over n rows: one expression sequence for the single-process and the two-stage path.
@@ -384,11 +260,6 @@ __global__ __launch_bounds__(256) void rn_avgpool_kernel(const T* __restrict__ i
     }
 }
 
-unsigned grid_for(int64_t work, int64_t cap = 16384) {
-    const int64_t g = (work + 255) / 256;
-    return unsigned(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace
 
 extern "C" int mla_rn_repack(const float* w_oihw, int64_t cout, int64_t cin, int64_t ks, void* out, int dtype, mla_stream_t stream) {
@@ -396,10 +267,10 @@ extern "C" int mla_rn_repack(const float* w_oihw, int64_t cout, int64_t cin, int
     MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_repack dtype %d", dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t total = cout * ks * ks * cin;
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_repack_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<float*>(out), cout, int(cin), int(ks * ks));
-    else
-        hipLaunchKernelGGL(rn_repack_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<bf16_t*>(out), cout, int(cin), int(ks * ks));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_repack_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<T*>(out), cout, int(cin), int(ks * ks));
+    });
     MLA_LAUNCH_OK("rn_repack_kernel");
     return MLA_OK;
 }
@@ -414,10 +285,10 @@ extern "C" int mla_rn_stem(const float* x, int64_t n, int64_t H, int64_t W, int 
     MLA_REQUIRE(n * kStemOut <= 0x7fffffffLL, MLA_E_SHAPE, "rn_stem: %lld images exceed the grid", (long long)n);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(unsigned(n * kStemOut));
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_stem_kernel<float>, grid, dim3(256), 0, s, x, single, w, scale, shift, relu, static_cast<float*>(out));
-    else
-        hipLaunchKernelGGL(rn_stem_kernel<bf16_t>, grid, dim3(256), 0, s, x, single, w, scale, shift, relu, static_cast<bf16_t*>(out));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_stem_kernel<T>, grid, dim3(256), 0, s, x, single, w, scale, shift, relu, static_cast<T*>(out));
+    });
     MLA_LAUNCH_OK("rn_stem_kernel");
     return MLA_OK;
 }
@@ -426,11 +297,7 @@ extern "C" int mla_rn_conv(const void* in, int64_t n, int64_t H, int64_t W, int6
                            int64_t stride, const float* scale, const float* shift, const void* residual, int relu, void* out, int dtype,
                            mla_stream_t stream) {
     MLA_REQUIRE(n >= 0 && H > 0 && W > 0, MLA_E_ARG, "rn_conv n %lld H %lld W %lld", (long long)n, (long long)H, (long long)W);
-    MLA_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2), MLA_E_SHAPE, "rn_conv: kernel %lld stride %lld not compiled",
-                (long long)ks, (long long)stride);
-    MLA_REQUIRE(cin > 0 && cout > 0 && cin % 64 == 0 && cout % 64 == 0 && cin <= 4096 && cout <= 4096, MLA_E_SHAPE,
-                "rn_conv: Cin %lld / Cout %lld must be multiples of 64 (<= 4096)", (long long)cin, (long long)cout);
-    MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_conv dtype %d", dtype);
+    RN_CONV_REQUIRE("rn_conv", ks, stride, cin, cout, dtype);
     if (n == 0) return MLA_OK;
     MLA_REQUIRE(in && w_packed && out && (!scale || shift), MLA_E_ARG, "null rn_conv buffers");
     MLA_REQUIRE(mla::aligned(in, 16) && mla::aligned(w_packed, 16), MLA_E_ARG, "rn_conv buffers must be 16-byte aligned");
@@ -440,16 +307,12 @@ extern "C" int mla_rn_conv(const void* in, int64_t n, int64_t H, int64_t W, int6
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool wide = cout % 128 == 0;
     const dim3 grid(unsigned((M + 127) / 128), unsigned(cout / (wide ? 128 : 64)));
-#define RN_CONV(T, BN)                                                                                                          \
-    hipLaunchKernelGGL((rn_conv_kernel<T, BN>), grid, dim3(256), 0, s, static_cast<const T*>(in), static_cast<const T*>(w_packed), \
-                       static_cast<T*>(out), scale, shift, static_cast<const T*>(residual), relu, M, int(H), int(W), int(cin),  \
-                       int(Ho), int(Wo), int(cout), int(ks), int(stride), int(pad))
-    if (dtype == MLA_F32) {
-        if (wide) RN_CONV(float, 128); else RN_CONV(float, 64);
-    } else {
-        if (wide) RN_CONV(bf16_t, 128); else RN_CONV(bf16_t, 64);
-    }
-#undef RN_CONV
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((wide ? rn_conv_kernel<T, 128> : rn_conv_kernel<T, 64>), grid, dim3(256), 0, s, static_cast<const T*>(in),
+                           static_cast<const T*>(w_packed), static_cast<T*>(out), scale, shift, static_cast<const T*>(residual), relu, M,
+                           int(H), int(W), int(cin), int(Ho), int(Wo), int(cout), int(ks), int(stride), int(pad));
+    });
     MLA_LAUNCH_OK("rn_conv_kernel");
     return MLA_OK;
 }
@@ -468,10 +331,10 @@ static int rn_bn_partials(const void* x, int64_t rows, int64_t channels, int dty
     const int P = bn_slices(rows);
     double* part = static_cast<double*>(workspace);
     const dim3 grid(unsigned(channels / 64), unsigned(P));
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_bn_partial_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), rows, int(channels), part);
-    else
-        hipLaunchKernelGGL(rn_bn_partial_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(x), rows, int(channels), part);
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_bn_partial_kernel<T>, grid, dim3(256), 0, s, static_cast<const T*>(x), rows, int(channels), part);
+    });
     MLA_LAUNCH_OK("rn_bn_partial_kernel");
     *slices = P;
     return MLA_OK;
@@ -536,12 +399,11 @@ extern "C" int mla_rn_bn_apply(const void* x, int64_t rows, int64_t channels, co
     MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_bn_apply dtype %d", dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t n8 = rows * channels / 8;
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_bn_apply_kernel<float>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const float*>(x), n8, int(channels),
-                           scale, shift, static_cast<const float*>(residual), relu, static_cast<float*>(out));
-    else
-        hipLaunchKernelGGL(rn_bn_apply_kernel<bf16_t>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const bf16_t*>(x), n8, int(channels),
-                           scale, shift, static_cast<const bf16_t*>(residual), relu, static_cast<bf16_t*>(out));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_bn_apply_kernel<T>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const T*>(x), n8, int(channels), scale, shift,
+                           static_cast<const T*>(residual), relu, static_cast<T*>(out));
+    });
     MLA_LAUNCH_OK("rn_bn_apply_kernel");
     return MLA_OK;
 }
@@ -555,12 +417,11 @@ extern "C" int mla_rn_maxpool(const void* in, int64_t n, int64_t H, int64_t W, i
     const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned g = grid_for(n * Ho * Wo * channels / 8);
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_maxpool_kernel<float>, dim3(g), dim3(256), 0, s, static_cast<const float*>(in), n, int(H), int(W), int(channels),
-                           int(Ho), int(Wo), static_cast<float*>(out));
-    else
-        hipLaunchKernelGGL(rn_maxpool_kernel<bf16_t>, dim3(g), dim3(256), 0, s, static_cast<const bf16_t*>(in), n, int(H), int(W),
-                           int(channels), int(Ho), int(Wo), static_cast<bf16_t*>(out));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_maxpool_kernel<T>, dim3(g), dim3(256), 0, s, static_cast<const T*>(in), n, int(H), int(W), int(channels), int(Ho),
+                           int(Wo), static_cast<T*>(out));
+    });
     MLA_LAUNCH_OK("rn_maxpool_kernel");
     return MLA_OK;
 }
@@ -573,10 +434,10 @@ extern "C" int mla_rn_avgpool(const void* in, int64_t n, int64_t hw, int64_t cha
     MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_avgpool dtype %d", dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned g = grid_for(n * channels);
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_avgpool_kernel<float>, dim3(g), dim3(256), 0, s, static_cast<const float*>(in), n, int(hw), int(channels), out);
-    else
-        hipLaunchKernelGGL(rn_avgpool_kernel<bf16_t>, dim3(g), dim3(256), 0, s, static_cast<const bf16_t*>(in), n, int(hw), int(channels), out);
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_avgpool_kernel<T>, dim3(g), dim3(256), 0, s, static_cast<const T*>(in), n, int(hw), int(channels), out);
+    });
     MLA_LAUNCH_OK("rn_avgpool_kernel");
     return MLA_OK;
 }

@@ -11,48 +11,13 @@
 //   rn_bn_bwd_*              BatchNorm2d train-mode backward (+ fused ReLU mask, + residual-path gradient)
 //   rn_maxpool_bwd_kernel    MaxPool2d(3, 2, 1) backward as a gather (first maximum in torch's scan order)
 //   rn_avgpool_bwd_kernel    AdaptiveAvgPool2d(1) backward: dY / HW broadcast
-#include "common.h"
-#include "mma_core.h"
+#include "rn_core.h"
 
 namespace {
 
-using mma::bf16_t;
-using mma::f32x4;
-using mma::u32x4;
-
-unsigned grid_for(int64_t work, int64_t cap = 16384) {
-    const int64_t g = (work + 255) / 256;
-    return unsigned(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float* v) {
-    if constexpr (sizeof(T) == 2) {
-        const u32x4 u = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[2 * k] = __builtin_bit_cast(float, u[k] << 16);
-            v[2 * k + 1] = __builtin_bit_cast(float, u[k] & 0xFFFF0000u);
-        }
-    } else {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k] = a[k]; v[4 + k] = b[k]; }
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void store8(T* p, const float* v) {
-    if constexpr (sizeof(T) == 2) {
-        u32x4 u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) u[k] = mma::pack_bf16x2(v[2 * k], v[2 * k + 1]);
-        *reinterpret_cast<u32x4*>(p) = u;
-    } else {
-        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
-}
+using namespace rn;
+using mma::load8;
+using mma::store8;
 
 // ------------------------------------------------------------------------------------------------
 // dgrad weights: w (Cout, Cin, k, k) f32 -> out[ci][t][co] = w[co][ci][k*k-1-t] in T
@@ -73,32 +38,24 @@ __global__ void rn_repack_dgrad_kernel(const float* __restrict__ w, T* __restric
 // stride-2 data gradient. Forward: y[oy] = sum_ky x[2 oy - pad + ky] w[ky]. An input row iy = 2a + py receives the taps
 // ky = ky0 + 2j (ky0 = (py + pad) & 1) from the output row oy = a + (py + pad - ky) / 2; so each of the four parity classes
 // (py, px) is a stride-1 gather over the output grid with its own tap subset (no zero taps reach the matrix cores).
-// Rows = the class's input pixels, cols = Cin, K = class taps x Cout. Tile and pipeline as rn_conv_kernel (resnet.hip).
+// Rows = the class's input pixels, cols = Cin, K = class taps x Cout, on the tile of rn_conv_kernel (rn_core.h conv_tile).
 // A class without taps (odd positions of a 1x1/2 downsample) writes the residual alone.
 // ------------------------------------------------------------------------------------------------
 template <typename T, int BN>
 __global__ __launch_bounds__(256) void rn_dgrad_s2_kernel(const T* __restrict__ dy, const T* __restrict__ wd, const T* __restrict__ res,
                                                           T* __restrict__ out, int64_t Mc, int Ho, int Wo, int Cout, int H, int W,
                                                           int Cin, int KS, int pad) {
-    constexpr int EPC = mma::Elem<T>::kPerChunk, EPR = mma::Elem<T>::kPerRow;
-    constexpr int BM = 128, AL = BM * 8 / 256, BL = BN * 8 / 256, TN = BN / 32;
-    __shared__ __attribute__((aligned(16))) char lds[(BM + BN) * mma::kRowBytes];
-    char* As = lds;
-    char* Bs = lds + BM * mma::kRowBytes;
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6, q = t & 7, r0 = t >> 3;
-    const int64_t m0 = int64_t(blockIdx.x) * BM;
-    const int n0 = blockIdx.y * BN;
     const int py = blockIdx.z >> 1, px = blockIdx.z & 1;
     const int Hc = H / 2, Wc = W / 2;
     const int ky0 = (py + pad) & 1, kx0 = (px + pad) & 1;
     const int nty = (KS - ky0 + 1) / 2, ntx = (KS - kx0 + 1) / 2;
 
-    int64_t abase[AL];
-    int aa[AL], ab[AL];
-    bool aval[AL];
+    int64_t abase[kTileAL];
+    int aa[kTileAL], ab[kTileAL];
+    bool aval[kTileAL];
 #pragma unroll
-    for (int i = 0; i < AL; ++i) {
-        const int64_t m = m0 + r0 + 32 * i;
+    for (int i = 0; i < kTileAL; ++i) {
+        const int64_t m = int64_t(blockIdx.x) * kTileM + (threadIdx.x >> 3) + 32 * i;
         aval[i] = m < Mc;
         const int64_t mm = aval[i] ? m : 0;
         ab[i] = int(mm % Wc);
@@ -106,78 +63,36 @@ __global__ __launch_bounds__(256) void rn_dgrad_s2_kernel(const T* __restrict__ 
         aa[i] = int(tmp % Hc);
         abase[i] = (tmp / Hc) * Ho;
     }
-    const int KK = KS * KS, csteps = Cout / EPR, nk = nty * ntx * csteps;
-    u32x4 ra[AL], rb[BL];
-    auto load = [&](int k) {
-        const int tap = k / csteps, cs = k - tap * csteps, jy = tap / ntx, jx = tap - jy * ntx;
-        const int ky = ky0 + 2 * jy, kx = kx0 + 2 * jx;
-        const int dyo = (py + pad - ky) / 2, dxo = (px + pad - kx) / 2;
-        const int c0 = cs * EPR + q * EPC;
-#pragma unroll
-        for (int i = 0; i < AL; ++i) {
-            const int oy = aa[i] + dyo, ox = ab[i] + dxo;
-            const bool ok = aval[i] && oy >= 0 && oy < Ho && ox >= 0 && ox < Wo;
-            ra[i] = ok ? *reinterpret_cast<const u32x4*>(dy + ((abase[i] + oy) * Wo + ox) * Cout + c0) : mma::zero16();
-        }
-        const int wt = (KS - 1 - ky) * KS + (KS - 1 - kx);       // the flipped tap of the dgrad repack
-#pragma unroll
-        for (int j = 0; j < BL; ++j) {
-            const int64_t ci = n0 + r0 + 32 * j;
-            rb[j] = *reinterpret_cast<const u32x4*>(wd + (ci * KK + wt) * Cout + c0);
-        }
+    auto taps = [&](int tap, int& ky, int& kx) {
+        const int jy = tap / ntx, jx = tap - jy * ntx;
+        ky = ky0 + 2 * jy;
+        kx = kx0 + 2 * jx;
     };
-
-    f32x4 acc[4][TN];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int wm = wid & 1, wn = wid >> 1;
-    if (nk > 0) load(0);
-    for (int k = 0; k < nk; ++k) {
-#pragma unroll
-        for (int i = 0; i < AL; ++i) mma::lds_write16(As, mma::tile_off(r0 + 32 * i, q), ra[i]);
-#pragma unroll
-        for (int j = 0; j < BL; ++j) mma::lds_write16(Bs, mma::tile_off(r0 + 32 * j, q), rb[j]);
-        __syncthreads();
-        if (k + 1 < nk) load(k + 1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int ch = ks * 4 + (lane >> 4);
-            u32x4 a[4], b[TN];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = mma::lds_read16(As, mma::tile_off(wm * 64 + i * 16 + (lane & 15), ch));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = mma::lds_read16(Bs, mma::tile_off(wn * (BN / 2) + j * 16 + (lane & 15), ch));
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) mma::mma_step<T>(a[i], b[j], acc[i][j]);
-        }
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int ci = n0 + wn * (BN / 2) + j * 16 + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int64_t m = m0 + wm * 64 + i * 16 + 4 * (lane >> 4) + e;
-                if (m >= Mc) continue;
+    conv_tile<T, BN, true>(
+        wd, KS * KS, Cout, nty * ntx, Mc,
+        [&](int i, int tap, int c0) {
+            int ky, kx;
+            taps(tap, ky, kx);
+            const int oy = aa[i] + (py + pad - ky) / 2, ox = ab[i] + (px + pad - kx) / 2;
+            const bool ok = aval[i] && oy >= 0 && oy < Ho && ox >= 0 && ox < Wo;
+            return ok ? *reinterpret_cast<const u32x4*>(dy + ((abase[i] + oy) * Wo + ox) * Cout + c0) : mma::zero16();
+        },
+        [&](int tap) {
+            int ky, kx;
+            taps(tap, ky, kx);
+            return (KS - 1 - ky) * KS + (KS - 1 - kx);       // the flipped tap of the dgrad repack
+        },
+        [&](int ci) {
+            return [=](int64_t m, float v) {
                 const int b = int(m % Wc);
                 const int64_t tmp = m / Wc;
                 const int a = int(tmp % Hc);
                 const int64_t img = tmp / Hc;
                 const int64_t off = ((img * H + 2 * a + py) * W + 2 * b + px) * Cin + ci;
-                float v = acc[i][j][e];
                 if (res) v += mma::load_elem<T>(res + off);
                 mma::store_elem<T>(out + off, v);
-            }
-        }
-    }
+            };
+        });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -307,8 +222,6 @@ __global__ void rn_wgrad_reduce_kernel(const float* __restrict__ ws, int S, int 
 // channel o = t & 63 at every 4th column; the four column groups are added in LDS in a fixed order, the blocks' partials
 // by the finish kernel in block order (double).
 // ------------------------------------------------------------------------------------------------
-constexpr int kImg = 224, kStemOut = 112, kStemC = 64;
-
 template <typename T>
 __global__ __launch_bounds__(256) void rn_stem_wgrad_partial_kernel(const float* __restrict__ x, const T* __restrict__ dy,
                                                                     int64_t rows, int rpb, float* __restrict__ part) {
@@ -369,26 +282,18 @@ __global__ void rn_stem_wgrad_finish_kernel(const float* __restrict__ part, int 
         s1 += part[(int64_t(s) * kStemC * 49 + i) * 2];
         s0 += part[(int64_t(s) * kStemC * 49 + i) * 2 + 1];
     }
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, inv[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const double carry = (c == 0 || !single) ? 1.0 : 0.0;
-        dw[(o * 3 + c) * 49 + k] = float(double(inv[c]) * (carry * s1 - double(mean[c]) * s0));
+        dw[(o * 3 + c) * 49 + k] = float(double(kNormInv[c]) * (carry * s1 - double(kNormMean[c]) * s0));
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // BatchNorm2d backward (train mode). g = dy [* (y > 0)]; xhat = (x - mean) * invstd;
 // dx = gamma invstd (g - mean(g) - xhat mean(g xhat)); dgamma = sum g xhat, dbeta = sum g.
-// Sums in double, partials by (channel group, row slice) and slices added in order: the layout of rn_bn_partial_kernel.
+// Sums in double by (channel group, row slice) with bn_slice_sums, the slices added by bn_sum_slices (rn_core.h).
 // ------------------------------------------------------------------------------------------------
-constexpr int kMaxSlices = 512;
-
-int bn_slices(int64_t rows) {
-    const int64_t p = (rows + 2047) / 2048;
-    return int(p < 1 ? 1 : (p > kMaxSlices ? kMaxSlices : p));
-}
-
 template <typename T>
 __device__ __forceinline__ void bn_bwd_elems(const T* x, const T* dy, const T* y, const float* mean, const float* invstd, int c,
                                              float* g, float* xh) {
@@ -413,27 +318,9 @@ template <typename T>
 __global__ __launch_bounds__(256) void rn_bn_bwd_partial_kernel(const T* __restrict__ x, const T* __restrict__ dy, const T* __restrict__ y,
                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                 int64_t rows, int C, double* __restrict__ part) {
-    __shared__ double red[2][32][64];
-    const int t = threadIdx.x, q = t & 7, r0 = t >> 3;
-    const int c0 = blockIdx.x * 64 + q * 8, P = gridDim.y, p = blockIdx.y;
-    double s[8], s2[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] = s2[k] = 0.0;
-    for (int64_t r = int64_t(p) * 32 + r0; r < rows; r += int64_t(P) * 32) {
-        float g[8], xh[8];
-        bn_bwd_elems<T>(x + r * C + c0, dy + r * C + c0, y ? y + r * C + c0 : nullptr, mean, invstd, c0, g, xh);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { s[k] += g[k]; s2[k] += double(g[k]) * xh[k]; }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { red[0][r0][q * 8 + k] = s[k]; red[1][r0][q * 8 + k] = s2[k]; }
-    __syncthreads();
-    if (t < 128) {
-        const int which = t >> 6, c = t & 63;
-        double acc = 0.0;
-        for (int i = 0; i < 32; ++i) acc += red[which][i][c];
-        part[(int64_t(which) * P + p) * C + blockIdx.x * 64 + c] = acc;
-    }
+    bn_slice_sums(rows, C, part, [&](int64_t off, int c0, float* g, float* xh) {
+        bn_bwd_elems<T>(x + off, dy + off, y ? y + off : nullptr, mean, invstd, c0, g, xh);
+    });
 }
 
 // per channel: coef[c] = mean(g), coef[C + c] = mean(g xhat), coef[2C + c] = gamma invstd; dgamma / dbeta if requested
@@ -442,8 +329,8 @@ __global__ void rn_bn_bwd_finish_kernel(const double* __restrict__ part, int P, 
                                         float* __restrict__ dbeta) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double s = 0.0, s2 = 0.0;
-    for (int p = 0; p < P; ++p) { s += part[int64_t(p) * C + c]; s2 += part[int64_t(P + p) * C + c]; }
+    double s, s2;
+    bn_sum_slices(part, P, C, c, s, s2);
     coef[c] = float(s / double(rows));
     coef[C + c] = float(s2 / double(rows));
     coef[2 * C + c] = gamma[c] * invstd[c];
@@ -560,20 +447,18 @@ extern "C" int mla_rn_repack_dgrad(const float* w_oihw, int64_t cout, int64_t ci
     MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_repack_dgrad dtype %d", dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t total = cout * ks * ks * cin;
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_repack_dgrad_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<float*>(out), int(cout), cin,
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_repack_dgrad_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<T*>(out), int(cout), cin,
                            int(ks * ks));
-    else
-        hipLaunchKernelGGL(rn_repack_dgrad_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w_oihw, static_cast<bf16_t*>(out), int(cout),
-                           cin, int(ks * ks));
+    });
     MLA_LAUNCH_OK("rn_repack_dgrad_kernel");
     return MLA_OK;
 }
 
 extern "C" int mla_rn_conv_dgrad(const void* dy, int64_t n, int64_t Ho, int64_t Wo, int64_t cout, const void* w_dgrad, int64_t cin, int64_t ks,
                                  int64_t stride, int64_t H, int64_t W, const void* residual, void* dx, int dtype, mla_stream_t stream) {
-    MLA_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2), MLA_E_SHAPE, "rn_conv_dgrad: kernel %lld stride %lld not compiled",
-                (long long)ks, (long long)stride);
+    RN_CONV_REQUIRE("rn_conv_dgrad", ks, stride, cin, cout, dtype);
     if (stride == 1) {
         MLA_REQUIRE(H == Ho && W == Wo, MLA_E_SHAPE, "rn_conv_dgrad: stride 1 keeps the size (%lld x %lld vs %lld x %lld)", (long long)H,
                     (long long)W, (long long)Ho, (long long)Wo);
@@ -582,9 +467,6 @@ extern "C" int mla_rn_conv_dgrad(const void* dy, int64_t n, int64_t Ho, int64_t 
     MLA_REQUIRE(n >= 0 && Ho > 0 && Wo > 0 && H == 2 * Ho && W == 2 * Wo && H <= 4096 && W <= 4096, MLA_E_SHAPE,
                 "rn_conv_dgrad stride 2: input %lld x %lld must be twice the output %lld x %lld", (long long)H, (long long)W, (long long)Ho,
                 (long long)Wo);
-    MLA_REQUIRE(cin > 0 && cout > 0 && cin % 64 == 0 && cout % 64 == 0 && cin <= 4096 && cout <= 4096, MLA_E_SHAPE,
-                "rn_conv_dgrad: Cin %lld / Cout %lld must be multiples of 64 (<= 4096)", (long long)cin, (long long)cout);
-    MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_conv_dgrad dtype %d", dtype);
     if (n == 0) return MLA_OK;
     MLA_REQUIRE(dy && w_dgrad && dx, MLA_E_ARG, "null rn_conv_dgrad buffers");
     MLA_REQUIRE(mla::aligned(dy, 16) && mla::aligned(w_dgrad, 16), MLA_E_ARG, "rn_conv_dgrad buffers must be 16-byte aligned");
@@ -593,16 +475,12 @@ extern "C" int mla_rn_conv_dgrad(const void* dy, int64_t n, int64_t Ho, int64_t 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool wide = cin % 128 == 0;
     const dim3 grid(unsigned((Mc + 127) / 128), unsigned(cin / (wide ? 128 : 64)), 4);
-#define RN_DGRAD(T, BN)                                                                                                            \
-    hipLaunchKernelGGL((rn_dgrad_s2_kernel<T, BN>), grid, dim3(256), 0, s, static_cast<const T*>(dy), static_cast<const T*>(w_dgrad), \
-                       static_cast<const T*>(residual), static_cast<T*>(dx), Mc, int(Ho), int(Wo), int(cout), int(H), int(W), int(cin),  \
-                       int(ks), int(ks / 2))
-    if (dtype == MLA_F32) {
-        if (wide) RN_DGRAD(float, 128); else RN_DGRAD(float, 64);
-    } else {
-        if (wide) RN_DGRAD(bf16_t, 128); else RN_DGRAD(bf16_t, 64);
-    }
-#undef RN_DGRAD
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((wide ? rn_dgrad_s2_kernel<T, 128> : rn_dgrad_s2_kernel<T, 64>), grid, dim3(256), 0, s, static_cast<const T*>(dy),
+                           static_cast<const T*>(w_dgrad), static_cast<const T*>(residual), static_cast<T*>(dx), Mc, int(Ho), int(Wo), int(cout),
+                           int(H), int(W), int(cin), int(ks), int(ks / 2));
+    });
     MLA_LAUNCH_OK("rn_dgrad_s2_kernel");
     return MLA_OK;
 }
@@ -615,13 +493,9 @@ extern "C" int64_t mla_rn_conv_wgrad_workspace_floats(int64_t n, int64_t Ho, int
 
 extern "C" int mla_rn_conv_wgrad(const void* x, const void* dy, int64_t n, int64_t H, int64_t W, int64_t cin, int64_t cout, int64_t ks,
                                  int64_t stride, float* workspace, int64_t workspace_floats, float* dw_oihw, int dtype, mla_stream_t stream) {
-    MLA_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2), MLA_E_SHAPE, "rn_conv_wgrad: kernel %lld stride %lld not compiled",
-                (long long)ks, (long long)stride);
     MLA_REQUIRE(n > 0 && H > 0 && W > 0 && H <= 4096 && W <= 4096, MLA_E_SHAPE, "rn_conv_wgrad n %lld H %lld W %lld", (long long)n,
                 (long long)H, (long long)W);
-    MLA_REQUIRE(cin > 0 && cout > 0 && cin % 64 == 0 && cout % 64 == 0 && cin <= 4096 && cout <= 4096, MLA_E_SHAPE,
-                "rn_conv_wgrad: Cin %lld / Cout %lld must be multiples of 64 (<= 4096)", (long long)cin, (long long)cout);
-    MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_conv_wgrad dtype %d", dtype);
+    RN_CONV_REQUIRE("rn_conv_wgrad", ks, stride, cin, cout, dtype);
     MLA_REQUIRE(x && dy && workspace && dw_oihw, MLA_E_ARG, "null rn_conv_wgrad buffers");
     MLA_REQUIRE(mla::aligned(x, 16) && mla::aligned(dy, 16), MLA_E_ARG, "rn_conv_wgrad buffers must be 16-byte aligned");
     const int64_t pad = ks / 2, Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
@@ -631,13 +505,11 @@ extern "C" int mla_rn_conv_wgrad(const void* x, const void* dy, int64_t n, int64
     const WgradPlan pl = wgrad_plan(n * Ho * Wo, cin, cout, ks, dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(unsigned(cout / 64), unsigned((cin / 64) * ks * ks), unsigned(pl.S));
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_wgrad_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), static_cast<const float*>(dy), workspace,
-                           n * Ho * Wo, pl.kb_per, int(H), int(W), int(cin), int(Ho), int(Wo), int(cout), int(ks), int(stride), int(pad));
-    else
-        hipLaunchKernelGGL(rn_wgrad_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(dy),
-                           workspace, n * Ho * Wo, pl.kb_per, int(H), int(W), int(cin), int(Ho), int(Wo), int(cout), int(ks), int(stride),
-                           int(pad));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_wgrad_kernel<T>, grid, dim3(256), 0, s, static_cast<const T*>(x), static_cast<const T*>(dy), workspace, n * Ho * Wo,
+                           pl.kb_per, int(H), int(W), int(cin), int(Ho), int(Wo), int(cout), int(ks), int(stride), int(pad));
+    });
     MLA_LAUNCH_OK("rn_wgrad_kernel");
     hipLaunchKernelGGL(rn_wgrad_reduce_kernel, dim3(grid_for(cout * cin * ks * ks)), dim3(256), 0, s, workspace, pl.S, int(cout), int(cin),
                        int(ks * ks), dw_oihw);
@@ -662,11 +534,10 @@ extern "C" int mla_rn_stem_wgrad(const float* x, int64_t n, int single, const vo
     const int64_t rows = n * kStemOut, rpb = stem_rows_per_block(rows);
     const int S = int((rows + rpb - 1) / rpb);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_stem_wgrad_partial_kernel<float>, dim3(S), dim3(256), 0, s, x, static_cast<const float*>(dy), rows, int(rpb), workspace);
-    else
-        hipLaunchKernelGGL(rn_stem_wgrad_partial_kernel<bf16_t>, dim3(S), dim3(256), 0, s, x, static_cast<const bf16_t*>(dy), rows, int(rpb),
-                           workspace);
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_stem_wgrad_partial_kernel<T>, dim3(S), dim3(256), 0, s, x, static_cast<const T*>(dy), rows, int(rpb), workspace);
+    });
     MLA_LAUNCH_OK("rn_stem_wgrad_partial_kernel");
     hipLaunchKernelGGL(rn_stem_wgrad_finish_kernel, dim3((kStemC * 49 + 255) / 256), dim3(256), 0, s, workspace, S, single, dw);
     MLA_LAUNCH_OK("rn_stem_wgrad_finish_kernel");
@@ -697,24 +568,20 @@ extern "C" int mla_rn_bn_bwd(const void* x, const void* dy, const void* y, int64
     MLA_LAUNCH_OK("rn_bn_bwd_invstd_kernel");
     const dim3 grid(unsigned(channels / 64), unsigned(P));
     const int64_t n8 = rows * channels / 8;
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_bn_bwd_partial_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), static_cast<const float*>(dy),
-                           static_cast<const float*>(y), mean, invstd, rows, C, part);
-    else
-        hipLaunchKernelGGL(rn_bn_bwd_partial_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(dy),
-                           static_cast<const bf16_t*>(y), mean, invstd, rows, C, part);
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_bn_bwd_partial_kernel<T>, grid, dim3(256), 0, s, static_cast<const T*>(x), static_cast<const T*>(dy),
+                           static_cast<const T*>(y), mean, invstd, rows, C, part);
+    });
     MLA_LAUNCH_OK("rn_bn_bwd_partial_kernel");
     hipLaunchKernelGGL(rn_bn_bwd_finish_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, part, P, C, rows, gamma, invstd, coef,
                        dgamma, dbeta);
     MLA_LAUNCH_OK("rn_bn_bwd_finish_kernel");
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_bn_bwd_apply_kernel<float>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const float*>(x),
-                           static_cast<const float*>(dy), static_cast<const float*>(y), mean, invstd, coef, n8, C, static_cast<float*>(dx),
-                           static_cast<float*>(dres));
-    else
-        hipLaunchKernelGGL(rn_bn_bwd_apply_kernel<bf16_t>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const bf16_t*>(x),
-                           static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y), mean, invstd, coef, n8, C, static_cast<bf16_t*>(dx),
-                           static_cast<bf16_t*>(dres));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_bn_bwd_apply_kernel<T>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const T*>(x), static_cast<const T*>(dy),
+                           static_cast<const T*>(y), mean, invstd, coef, n8, C, static_cast<T*>(dx), static_cast<T*>(dres));
+    });
     MLA_LAUNCH_OK("rn_bn_bwd_apply_kernel");
     return MLA_OK;
 }
@@ -730,12 +597,11 @@ extern "C" int mla_rn_maxpool_bwd(const void* in, const void* dy, int64_t n, int
     const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned g = grid_for(n * H * W * channels / 8);
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_maxpool_bwd_kernel<float>, dim3(g), dim3(256), 0, s, static_cast<const float*>(in), static_cast<const float*>(dy), n,
-                           int(H), int(W), int(channels), int(Ho), int(Wo), static_cast<float*>(dx));
-    else
-        hipLaunchKernelGGL(rn_maxpool_bwd_kernel<bf16_t>, dim3(g), dim3(256), 0, s, static_cast<const bf16_t*>(in), static_cast<const bf16_t*>(dy),
-                           n, int(H), int(W), int(channels), int(Ho), int(Wo), static_cast<bf16_t*>(dx));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_maxpool_bwd_kernel<T>, dim3(g), dim3(256), 0, s, static_cast<const T*>(in), static_cast<const T*>(dy), n, int(H),
+                           int(W), int(channels), int(Ho), int(Wo), static_cast<T*>(dx));
+    });
     MLA_LAUNCH_OK("rn_maxpool_bwd_kernel");
     return MLA_OK;
 }
@@ -748,10 +614,10 @@ extern "C" int mla_rn_avgpool_bwd(const float* d, int64_t n, int64_t hw, int64_t
     MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_avgpool_bwd dtype %d", dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned g = grid_for(n * hw * channels / 8);
-    if (dtype == MLA_F32)
-        hipLaunchKernelGGL(rn_avgpool_bwd_kernel<float>, dim3(g), dim3(256), 0, s, d, n, int(hw), int(channels), static_cast<float*>(dx));
-    else
-        hipLaunchKernelGGL(rn_avgpool_bwd_kernel<bf16_t>, dim3(g), dim3(256), 0, s, d, n, int(hw), int(channels), static_cast<bf16_t*>(dx));
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_avgpool_bwd_kernel<T>, dim3(g), dim3(256), 0, s, d, n, int(hw), int(channels), static_cast<T*>(dx));
+    });
     MLA_LAUNCH_OK("rn_avgpool_bwd_kernel");
     return MLA_OK;
 }

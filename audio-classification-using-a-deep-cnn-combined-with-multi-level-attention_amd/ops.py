@@ -752,24 +752,30 @@ def _rn_workspace(device, channels):
     return _ws[key]
 
 
-def rn_bn_stats(x, bn, running=True, want_stats=False):
-    """Train-mode BatchNorm2d statistics of NHWC x: returns (scale, shift[, mean, var_biased]); updates bn's running
-    statistics (and num_batches_tracked) when `running`."""
-    _chk(x)
+def _rn_bn_finish(x, bn, running, want_stats, name, fn, *head):
+    """What rn_bn_stats and rn_bn_stats_sync share: the outputs, the running buffers and the batch counter around the library
+    call fn(*head, gamma, beta, eps, momentum, running_mean, running_var, mean, var, scale, shift, stream), timed as `name`."""
     C = x.shape[-1]
-    rows = x.numel() // C
     dev = x.device
     scale = torch.empty(C, dtype=torch.float32, device=dev)
     shift = torch.empty(C, dtype=torch.float32, device=dev)
     mean = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
     var = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
     rm, rv = (bn.running_mean, bn.running_var) if running else (None, None)
-    _lib.check(_timed("rn_bn_stats", _lib.lib().mla_rn_bn_stats, _p(x), rows, C, DT[x.dtype], _p(_rn_workspace(dev, C)),
-                      _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps), float(bn.momentum), _p(rm), _p(rv),
+    _lib.check(_timed(name, fn, *head, _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps), float(bn.momentum), _p(rm), _p(rv),
                       _p(mean), _p(var), _p(scale), _p(shift), _lib.stream_ptr()))
     if running:
         _lib.check(_lib.lib().mla_counter_add(_p(bn.num_batches_tracked), 1, _lib.stream_ptr()))
     return (scale, shift, mean, var) if want_stats else (scale, shift)
+
+
+def rn_bn_stats(x, bn, running=True, want_stats=False):
+    """Train-mode BatchNorm2d statistics of NHWC x: returns (scale, shift[, mean, var_biased]); updates bn's running
+    statistics (and num_batches_tracked) when `running`."""
+    _chk(x)
+    C = x.shape[-1]
+    return _rn_bn_finish(x, bn, running, want_stats, "rn_bn_stats", _lib.lib().mla_rn_bn_stats, _p(x), x.numel() // C, C, DT[x.dtype],
+                         _p(_rn_workspace(x.device, C)))
 
 
 def rn_bn_stats_sync(x, bn, dist, running=True, want_stats=False):
@@ -780,23 +786,12 @@ def rn_bn_stats_sync(x, bn, dist, running=True, want_stats=False):
         return rn_bn_stats(x, bn, running, want_stats)
     _chk(x)
     C = x.shape[-1]
-    rows = x.numel() // C
-    dev = x.device
     L = _lib.lib()
-    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
-    _lib.check(_timed("rn_bn_sums", L.mla_rn_bn_sums, _p(x), rows, C, DT[x.dtype], _p(_rn_workspace(dev, C)), _p(sums),
+    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+    _lib.check(_timed("rn_bn_sums", L.mla_rn_bn_sums, _p(x), x.numel() // C, C, DT[x.dtype], _p(_rn_workspace(x.device, C)), _p(sums),
                       _lib.stream_ptr()))
     dist.all_reduce_sum(sums, "syncbn_rn")
-    scale = torch.empty(C, dtype=torch.float32, device=dev)
-    shift = torch.empty(C, dtype=torch.float32, device=dev)
-    mean = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
-    var = torch.empty(C, dtype=torch.float32, device=dev) if want_stats else None
-    rm, rv = (bn.running_mean, bn.running_var) if running else (None, None)
-    _lib.check(_timed("rn_bn_finish", L.mla_rn_bn_finish, _p(sums), C, _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps),
-                      float(bn.momentum), _p(rm), _p(rv), _p(mean), _p(var), _p(scale), _p(shift), _lib.stream_ptr()))
-    if running:
-        _lib.check(L.mla_counter_add(_p(bn.num_batches_tracked), 1, _lib.stream_ptr()))
-    return (scale, shift, mean, var) if want_stats else (scale, shift)
+    return _rn_bn_finish(x, bn, running, want_stats, "rn_bn_finish", L.mla_rn_bn_finish, _p(sums), C)
 
 
 def rn_bn_eval_coeffs(bn):
