@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv1_core.h"
 #include "mma_core.h"
 
 namespace {
@@ -772,45 +773,24 @@ __global__ __launch_bounds__(256, 4) void conv1_kernel(const TIN* __restrict__ x
 template <typename TIN>
 __global__ __launch_bounds__(256, MLA_CONV1_WAVES) void conv1_patch_kernel(const TIN* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, bf16_t* __restrict__ out, int n_img) {
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    using conv1::f32x16;
     constexpr int TR = MLA_CONV1_ROWS;                          // input rows per tile (TR / 2 pooled rows, TR / 8 per wave)
     constexpr int TPC = 96 / TR;                                // tiles per clip
     constexpr int NP = (TR + 2) * 66;                           // staged input elements per tile
     constexpr int NL = (NP + 255) / 256;                        // ... per thread
-    constexpr int PITCH = 68;                                   // bf16 per staged input row: 66 used, element (gy, gx) at column gx + 1
-    constexpr int ROW = 64 * 2 + 16;                            // bytes per pooled pixel in the output stage
+    constexpr int PITCH = conv1::kPitch;                        // bf16 per staged input row: 66 used, element (gy, gx) at column gx + 1
+    constexpr int ROW = conv1::kStageRow;                       // bytes per pooled pixel in the output stage
     __shared__ __attribute__((aligned(16))) uint16_t sX[(TR + 2) * PITCH];
     __shared__ __attribute__((aligned(16))) char sOut[4 * 32 * ROW];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, px = lane & 31, h = lane >> 5;
     const int n_tiles = n_img * TPC;
 
-    // A operand: W'[pos][channel(rho)][8 h + j] for rho = lane & 31, per position and 32-channel tile
+    // A operand (weights, held in registers for the workgroup's life) and the bias the accumulators start from: conv1_core.h
     bf16x8 wa[4][2];
     f32x16 binit[2];
-    {
-        const int rho = px;
-        const int chl = 16 * ((rho >> 2) & 1) + (rho & 3) + 4 * (rho >> 3);
-        _Pragma("unroll") for (int pos = 0; pos < 4; ++pos) {
-            const int dy = pos >> 1, dx = pos & 1;
-            _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) {
-                const int ch = mt * 32 + chl;
-                uint32_t pk[4];
-                _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {
-                    float v[2];
-                    _Pragma("unroll") for (int e = 0; e < 2; ++e) {
-                        const int k = 8 * h + 2 * jj + e, i = k >> 2, c = k & 3;          // patch row i, column c
-                        const int ky = i - dy, kx = c - dx;
-                        v[e] = (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w[ch * 9 + ky * 3 + kx] : 0.f;
-                    }
-                    pk[jj] = pack_bf16x2(v[0], v[1]);
-                }
-                wa[pos][mt] = __builtin_bit_cast(bf16x8, u32x4{pk[0], pk[1], pk[2], pk[3]});
-            }
-        }
-        // C/D: lane (col = pixel, hi = h) register reg <-> MFMA row (reg & 3) + 8 (reg >> 2) + 4 hi <-> channel 16 hi + reg of the tile
-        _Pragma("unroll") for (int mt = 0; mt < 2; ++mt)
-            _Pragma("unroll") for (int reg = 0; reg < 16; ++reg) binit[mt][reg] = bias[mt * 32 + 16 * h + reg];
-    }
+    _Pragma("unroll") for (int pos = 0; pos < 4; ++pos)
+        _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) wa[pos][mt] = conv1::weight_frag(w, pos, mt, lane);
+    _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) binit[mt] = conv1::bias_frag(bias, mt, lane);
 
     // input rows y0-1 .. y0+TR, columns -1 .. 64 of one tile -> NL registers per thread, then LDS (bf16)
     float pre[NL];
@@ -854,37 +834,9 @@ __global__ __launch_bounds__(256, MLA_CONV1_WAVES) void conv1_patch_kernel(const
         if (tile + int(gridDim.x) < n_tiles) patch_load(tile + int(gridDim.x));
         _Pragma("unroll") for (int rr = 0; rr < TR / 8; ++rr) {
             const int prow = wave * (TR / 8) + rr;                                  // pooled row of the tile owned by this wave
-            // B operand: patch rows 2h, 2h+1 of its pixel (local input rows 2 prow + 2h, + 1), columns 2 px .. 2 px + 3 of sX
-            const uint32_t* r0 = reinterpret_cast<const uint32_t*>(sX + (2 * prow + 2 * h) * PITCH) + px;       // 2 px bf16 = px dwords
-            const uint32_t* r1 = reinterpret_cast<const uint32_t*>(sX + (2 * prow + 2 * h + 1) * PITCH) + px;
-            const bf16x8 bfrag = __builtin_bit_cast(bf16x8, u32x4{r0[0], r0[1], r1[0], r1[1]});
-            _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) {
-                f32x16 m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][mt], bfrag, binit[mt], 0, 0, 0);
-                _Pragma("unroll") for (int pos = 1; pos < 4; ++pos) {
-                    const f32x16 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[pos][mt], bfrag, binit[mt], 0, 0, 0);
-                    _Pragma("unroll") for (int reg = 0; reg < 16; ++reg) m[reg] = fmaxf(m[reg], a[reg]);
-                }
-                uint32_t pk[8];
-                _Pragma("unroll") for (int e = 0; e < 8; ++e) pk[e] = pack_bf16x2(fmaxf(m[2 * e], 0.f), fmaxf(m[2 * e + 1], 0.f));
-                char* dst = stage + px * ROW + (mt * 32 + 16 * h) * 2;              // 16 consecutive channels of pixel px
-                *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-                *reinterpret_cast<u32x4*>(dst + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the stage rows belong to this wave only:
-            __builtin_amdgcn_wave_barrier();                            // LDS operations of one wave execute in order
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // local input rows 2 prow .. 2 prow + 3 of sX -> pooled row prow: conv1_core.h
             char* gdst = reinterpret_cast<char*>(out + ((size_t(img) * 48 + y0 / 2 + prow) * 32) * 64);
-            _Pragma("unroll") for (int it = 0; it < 4; ++it) {                      // 32 pixels x 128 B = 4 KiB contiguous per wave
-                const int piece = it * 64 + lane, p = piece >> 3, c = piece & 7;
-#if MLA_CONV_NT_STORE
-                __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(stage + p * ROW + c * 16), reinterpret_cast<u32x4*>(gdst + size_t(piece) * 16));
-#else
-                *reinterpret_cast<u32x4*>(gdst + size_t(piece) * 16) = *reinterpret_cast<const u32x4*>(stage + p * ROW + c * 16);
-#endif
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the reads above precede the next row's stage writes
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            conv1::pooled_row(sX + (2 * prow) * PITCH, wa, binit, stage, gdst, lane);
         }
         lds_barrier();                                              // every wave is done with sX before the next patch lands
     }

@@ -33,6 +33,7 @@
 #include <hip/hip_bf16.h>
 
 #include "common.h"
+#include "conv1_core.h"
 #include "logmel_core.h"
 #include "logmel_tables.h"
 
@@ -187,22 +188,55 @@ __device__ __forceinline__ void mel_pair(const LaneConsts& c, const float* mag_a
     }
 }
 
+// four finished values -> two dwords of bf16 (round-to-nearest-even): the one rounding of a bf16 row, wherever it goes
+__device__ __forceinline__ u32x2 pack_piece(f32x4 v) {
+    const __hip_bfloat16 b0 = __float2bfloat16(v.x), b1 = __float2bfloat16(v.y), b2 = __float2bfloat16(v.z), b3 = __float2bfloat16(v.w);
+    auto bits = [](const __hip_bfloat16& h) { return uint32_t(*reinterpret_cast<const uint16_t*>(&h)); };
+    return u32x2{bits(b0) | (bits(b1) << 16), bits(b2) | (bits(b3) << 16)};
+}
+
 template <typename OutT>
 __device__ __forceinline__ void store_piece(OutT* dst, f32x4 v) {
     if constexpr (sizeof(OutT) == 4) {
         *reinterpret_cast<f32x4*>(dst) = v;
     } else {
-        const __hip_bfloat16 b0 = __float2bfloat16(v.x), b1 = __float2bfloat16(v.y), b2 = __float2bfloat16(v.z), b3 = __float2bfloat16(v.w);
-        auto bits = [](const __hip_bfloat16& h) { return uint32_t(*reinterpret_cast<const uint16_t*>(&h)); };
-        *reinterpret_cast<u32x2*>(dst) = u32x2{bits(b0) | (bits(b1) << 16), bits(b2) | (bits(b3) << 16)};
+        *reinterpret_cast<u32x2*>(dst) = pack_piece(v);
     }
 }
 
+// Where the two finished rows of a frame pair go: lane j holds bands 4 j .. 4 j + 3 of row A (va) and of row B (vb).
+// RowsToGlobal: (example, 96, 64) memory, one 16-byte (f32) / 8-byte (bf16) piece per lane and row.
+template <typename OutT>
+struct RowsToGlobal {
+    OutT* dst;                                                   // row A; row B follows it
+    __device__ __forceinline__ void operator()(int j, f32x4 va, f32x4 vb) const {
+        store_piece<OutT>(dst + 4 * j, va);
+        store_piece<OutT>(dst + kBands + 4 * j, vb);
+    }
+};
+// RowsToStaged: bf16 rows in conv1's staged LDS layout (conv1_core.h: pitch 68, band b at column b + 1, columns 0 and 65 zero).
+// Bands 4 j .. 4 j + 3 sit at columns 4 j + 1 .. 4 j + 4: a half dword, a dword, a half dword.
+struct RowsToStaged {
+    uint16_t* row;                                               // row A; row B is the next staged row
+    __device__ __forceinline__ void one(uint16_t* r, int j, f32x4 v) const {
+        const u32x2 p = pack_piece(v);
+        r[4 * j + 1] = uint16_t(p.x);
+        *reinterpret_cast<uint32_t*>(r + 4 * j + 2) = (p.x >> 16) | (p.y << 16);
+        r[4 * j + 4] = uint16_t(p.y >> 16);
+        if (j == 0) r[0] = 0;
+        if (j == 15) r[65] = 0;
+    }
+    __device__ __forceinline__ void operator()(int j, f32x4 va, f32x4 vb) const {
+        one(row, j, va);
+        one(row + conv1::kPitch, j, vb);
+    }
+};
+
 // One frame pair of a 16-lane group: window (samples already in `smp`), prefetch of the group's next pair, both FFTs, split,
-// mel, log, and the two finished rows to dst / dst + 64. Shared by the dynamic (shipped) and the static (cross-check) kernel.
-template <typename InT, typename OutT, bool VEC, bool WAVE>
+// mel, log, and the two finished rows to `sink`. Shared by the dynamic (shipped), the static (cross-check) and the fused kernel.
+template <typename InT, bool VEC, bool WAVE, typename Sink>
 __device__ __forceinline__ void pair_step(const LaneConsts& c, int j, Samples<InT>& smp, const InT* next_frame, float* xa, float* xb,
-                                          const float* s_win, const float* melw, const float* pw, OutT* dst) {
+                                          const float* s_win, const float* melw, const float* pw, const Sink& sink) {
     float ra[16], ia[16], rb[16], ib[16];
     {   // window: frame B's tap n1 is sample pair U[n1 + 5] under the SAME window value as A's tap n1
         _Pragma("unroll") for (int n1 = 0; n1 < kN1; ++n1) {
@@ -241,8 +275,8 @@ __device__ __forceinline__ void pair_step(const LaneConsts& c, int j, Samples<In
     {
         const f32x4 va = *reinterpret_cast<const f32x4*>(xa + 256 + 4 * j);
         const f32x4 vb = *reinterpret_cast<const f32x4*>(xb + 256 + 4 * j);
-        store_piece<OutT>(dst + 4 * j, va);
-        store_piece<OutT>(dst + kBands + 4 * j, vb);
+        group_sync<WAVE>();             // a staged sink writes LDS that other lanes have just read
+        sink(j, va, vb);
     }
     group_sync<WAVE>();                 // the buffers are rewritten by the next pair
 }
@@ -287,7 +321,7 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void logmel_kernel(const InT* _
             map.locate(next, ns, nr);
             next_frame = pcm + ns + (kPair * g) * kHop;
         }
-        pair_step<InT, OutT, VEC, WAVE>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, out + (row0 + kPair * g) * kBands);
+        pair_step<InT, VEC, WAVE>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, RowsToGlobal<OutT>{out + (row0 + kPair * g) * kBands});
     }
 }
 
@@ -364,7 +398,7 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_dyn_kernel(const InT* _
             locate_item(nxt, nsample, nrow);
             next_frame = pcm + nsample + lane_frame * kHop;
         }
-        pair_step<InT, OutT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, out + (row + lane_frame) * kBands);
+        pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, RowsToGlobal<OutT>{out + (row + lane_frame) * kBands});
         cur = nxt;
         row = nrow;
     }
@@ -374,6 +408,156 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_dyn_kernel(const InT* _
         g_logmel_stamps[blockIdx.x][1 + (t >> 6)] = __builtin_amdgcn_s_memrealtime();
     }
 #endif
+}
+
+// Fused front (bf16 inference): PCM -> conv1's pooled NHWC output in one kernel; the bf16 examples never exist in memory. The
+// stand-alone pair is bound by different things -- logmel_dyn_kernel by vector issue and LDS, conv1_patch_kernel by the store
+// path -- so here conv1's non-temporal stores drain while other waves run FFTs.
+//
+// One 512-thread workgroup per CU owns a contiguous range of WHOLE CLIPS and its 8 waves pull clips from an LDS counter. A wave
+// walks its clip's 12 items (8 frames each) in order, so every hand-off stays inside the wave: no workgroup barrier after the
+// table load, no wait, no spin, no recomputed halo frame. After item i the wave holds input rows <= 8 i + 7, which completes
+// pooled rows 4 i - 1 .. 4 i + 2 (input rows 8 i - 3 .. 8 i + 6): the item's 8 rows land as bf16 in conv1's staged layout inside
+// the wave's own (dead) exchange buffers, the 3 rows before them are carried from the previous item in two pad columns of its
+// exchange buffers (which every FFT otherwise rewrites), and conv1_core.h turns four pooled rows into 4 x 4 KiB of stores. Item 0
+// starts at pooled row 0 with a zero row above, item 11 adds pooled row 47 with a zero row below.
+// LDS: the dynamic kernel's buffers + conv1's weight fragments (8 KiB) and bias; the output stage is exchange-buffer space too.
+constexpr int kClipItems = kExFrames / kItemFrames;         // 12
+constexpr int kFusedWaBytes = 8 * 64 * 16;                  // A fragments of (4 positions x 2 channel tiles) x 64 lanes
+constexpr int kLdsBytesFused = kLdsBytesDyn + kFusedWaBytes + 64 * 4;
+constexpr int kStagedDwords = conv1::kPitch / 2;            // dwords per staged row
+static_assert(kLdsBytesDyn % 16 == 0 && kLdsBytesFused <= 160 * 1024, "fused kernel: LDS");
+static_assert(12 * conv1::kPitch * 2 <= kXchFloats * 4 && conv1::kStageBytes <= 2 * kXchFloats * 4 && kItemFrames * kXchFloats >= 3 * kXchFloats,
+              "staged rows in the wave's first exchange buffer, output stage in the next two");
+static_assert(kThreadsDyn / 64 == 8, "one wave per (position, channel tile) builds the weight fragments");
+
+template <typename InT, bool VEC>
+__global__ __launch_bounds__(kThreadsDyn, 1) void logmel_conv1_kernel(const InT* __restrict__ pcm, int64_t wave_stride, int examples,
+                                                                      int n_clips, const float* __restrict__ tab,
+                                                                      const float* __restrict__ w, const float* __restrict__ bias,
+                                                                      mma::bf16_t* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* s_xch = smem;
+    float* s_mel = s_xch + (kThreadsDyn / 16) * kPair * kXchFloats;
+    float* s_pw = s_mel + 16 * kMelRow;
+    float* s_win = s_pw + 16 * kPwPitch;
+    int* s_next = reinterpret_cast<int*>(s_win + kWinFloats);
+    mma::u32x4* s_wa = reinterpret_cast<mma::u32x4*>(smem + kLdsFloatsDyn);
+    float* s_bias = smem + kLdsFloatsDyn + kFusedWaBytes / 4;
+
+    const int t = threadIdx.x, g = t >> 4, gl = g & 3, j = t & 15, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    float* xa = s_xch + (kPair * g) * kXchFloats;
+    float* xb = xa + kXchFloats;
+    // the wave's 8 exchange buffers: between two FFTs, buffer 0 holds the staged input rows and buffers 1-2 the output stage
+    char* wregion = reinterpret_cast<char*>(s_xch + (kItemFrames * wv) * kXchFloats);
+    uint16_t* sX = reinterpret_cast<uint16_t*>(wregion);
+    uint32_t* sX32 = reinterpret_cast<uint32_t*>(wregion);
+    char* stage = wregion + kXchFloats * 4;
+
+    LaneConsts c;
+    load_consts(c, tab, j);
+    for (int i = t; i < 16 * kMelRow; i += kThreadsDyn) s_mel[i] = tab[kTabMelW + i];
+    for (int i = t; i < 16 * kPwRow; i += kThreadsDyn) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
+    for (int i = t; i < kWinFloats; i += kThreadsDyn) s_win[i] = tab[kTabWindow + i];
+    s_wa[t] = __builtin_bit_cast(mma::u32x4, conv1::weight_frag(w, wv >> 1, wv & 1, lane));
+    if (t < 64) s_bias[t] = bias[t];
+    // this workgroup's contiguous share of the clips
+    const int lo = int(int64_t(n_clips) * int64_t(blockIdx.x) / int64_t(gridDim.x)), hi = int(int64_t(n_clips) * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
+    if (t == 0) *s_next = lo;
+    const float* melw = s_mel + kMelRow * j;
+    const float* pw = s_pw + kPwPitch * j;
+    __syncthreads();                        // the only workgroup barrier (no store is in flight yet): tables and the counter visible
+
+    auto pull = [&]() {                      // wave-uniform: one lane takes the next clip of the workgroup's share
+        int v = 0;
+        if (lane == 0) v = atomicAdd(s_next, 1);
+        return __builtin_amdgcn_readfirstlane(v);
+    };
+    const int lane_frame = kPair * gl;                        // this group's frame pair inside the item
+    auto item_frame = [&](int clip, int item) {               // first sample of this group's pair in (clip, item)
+        const int wf = clip / examples, e = clip - wf * examples;
+        return pcm + int64_t(wf) * wave_stride + (int64_t(e) * kExFrames + item * kItemFrames + lane_frame) * kHop;
+    };
+    auto wave_fence = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    Samples<InT> smp;
+    int clip = pull(), item = 0;
+    if (clip < hi) smp.template fetch<VEC>(item_frame(clip, 0), j);
+    // The 3 staged rows an item hands to the next one must survive the FFTs in between, which rewrite the exchange buffers --
+    // except the two pad columns of every exchange row (phase 1 writes 16 of a row's 18 complex). The pads of exchange rows
+    // 9 .. 15 also lie beyond the magnitudes and the finished row (floats 0 .. 319), so nothing touches them: 28 dwords per
+    // buffer. Dword d of the 102 parks in buffer 3 + d / 28 (buffers 0 .. 2 hold the staged rows and the stage).
+    uint32_t* parked = reinterpret_cast<uint32_t*>(wregion) + 3 * kXchFloats;
+    auto park_slot = [](int d) { return (d / 28) * kXchFloats + 2 * kXchStride * (9 + (d % 28) / 4) + 32 + d % 4; };
+    const int second = 64 + lane < 3 * kStagedDwords ? 64 + lane : 3 * kStagedDwords - 1;
+    // conv1 of one finished item: staged rows 3 .. 10 are in place (written by the item's FFT pass)
+    auto conv_item = [&](int clip, int item) {
+        {   // rows 0 .. 2 = 102 dwords, parked by the previous item (zero at a clip's start)
+            const uint32_t k0 = parked[park_slot(lane)], k1 = parked[park_slot(second)];
+            sX32[lane] = item == 0 ? 0u : k0;
+            if (lane < 3 * kStagedDwords - 64) sX32[64 + lane] = item == 0 ? 0u : k1;
+        }
+        if (lane < kStagedDwords) sX32[11 * kStagedDwords + lane] = 0u;         // row 11: the zero row below the clip (read by item 11 only)
+        wave_fence();
+        {
+            mma::bf16x8 wa[4][2];
+            conv1::f32x16 binit[2];
+            _Pragma("unroll") for (int pos = 0; pos < 4; ++pos)
+                _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) wa[pos][mt] = __builtin_bit_cast(mma::bf16x8, s_wa[(pos * 2 + mt) * 64 + lane]);
+            _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) binit[mt] = conv1::bias_frag(s_bias, mt, lane);
+            // pooled row 4 item - 1 + q from staged rows 2 q .. 2 q + 3. Item 0 has no q = 0 (pooled row -1): it writes its q = 1
+            // twice, so that every item issues the same 16 stores in straight-line code. Item 11's fifth row, the clip's last,
+            // goes first, under a uniform branch.
+            auto row = [&](int q) {
+                char* gdst = reinterpret_cast<char*>(out + ((size_t(clip) * 48 + size_t(4 * item - 1 + q)) * 32) * 64);
+                conv1::pooled_row(sX + (2 * q) * conv1::kPitch, wa, binit, stage, gdst, lane);
+            };
+            if (item == kClipItems - 1) row(4);
+            row(item == 0 ? 1 : 0);
+            row(1);
+            row(2);
+            row(3);
+        }
+        {   // rows 8 .. 10 become rows 0 .. 2 of the next item
+            const uint32_t k0 = sX32[8 * kStagedDwords + lane], k1 = sX32[8 * kStagedDwords + second];
+            parked[park_slot(lane)] = k0;
+            parked[park_slot(second)] = k1;         // lanes past the end rewrite the last dword with its own value
+        }
+        wave_fence();                       // the staged rows and the stage are rewritten by the next FFT
+    };
+    while (clip < hi) {
+        int nclip = clip, nitem = item + 1;
+        if (nitem == kClipItems) { nclip = pull(); nitem = 0; }
+        const InT* next_frame = nclip < hi ? item_frame(nclip, nitem) : nullptr;
+        // staged row r <-> input row 8 item - 3 + r: this item's rows are r = 3 .. 10
+        pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, RowsToStaged{sX + (3 + lane_frame) * conv1::kPitch});
+        conv_item(clip, item);
+        clip = nclip;
+        item = nitem;
+    }
+}
+
+template <typename InT>
+int launch_fused(const void* pcm, int64_t n_wave, int64_t wave_stride, int64_t examples, const float* tables, const float* w,
+                 const float* bias, void* out, hipStream_t stream) {
+    const int64_t n_clips = n_wave * examples;
+    if (n_clips == 0) return MLA_OK;
+    MLA_REQUIRE(n_clips <= 0x7fffffff / kClipItems, MLA_E_SHAPE, "too many clips for one launch (%lld)", (long long)n_clips);
+    const bool vec = mla::aligned(pcm, 2 * sizeof(InT)) && (wave_stride % 2 == 0);
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t wgs = n_clips < cus ? n_clips : cus;
+    auto go = [&](auto kern) -> int {
+        MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesFused));
+        hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(kThreadsDyn), kLdsBytesFused, stream, static_cast<const InT*>(pcm), wave_stride,
+                           int(examples), int(n_clips), tables, w, bias, static_cast<mma::bf16_t*>(out));
+        MLA_LAUNCH_OK("logmel_conv1_kernel");
+        return MLA_OK;
+    };
+    return vec ? go(logmel_conv1_kernel<InT, true>) : go(logmel_conv1_kernel<InT, false>);
 }
 
 template <typename InT, typename OutT>
@@ -476,4 +660,22 @@ extern "C" int mla_logmel_examples(const void* pcm, int pcm_dtype, int64_t n_wav
     }
     return out_dtype == MLA_F32 ? launch<int16_t, float>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s)
                                 : launch<int16_t, __hip_bfloat16>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s);
+}
+
+extern "C" int mla_logmel_conv1(const void* pcm, int pcm_dtype, int64_t n_wave, int64_t n_samples, int64_t wave_stride,
+                                const float* tables, const float* w, const float* bias, void* out, mla_stream_t stream) {
+    MLA_REQUIRE(n_wave >= 0 && wave_stride >= n_samples, MLA_E_ARG, "bad n_wave %lld / stride %lld < n_samples %lld",
+                (long long)n_wave, (long long)wave_stride, (long long)n_samples);
+    int64_t frames = 0, examples = 0;
+    const int rc = mla_logmel_counts(n_samples, &frames, &examples);
+    if (rc != MLA_OK) return rc;
+    if (n_wave == 0 || examples == 0) return MLA_OK;
+    MLA_REQUIRE(pcm && tables && w && bias && out, MLA_E_ARG, "null pcm/tables/w/bias/out");
+    MLA_REQUIRE(mla::aligned(out, 16) && mla::aligned(tables, 4) && mla::aligned(w, 4) && mla::aligned(bias, 4), MLA_E_ARG,
+                "out must be 16-byte aligned");
+    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d", pcm_dtype);
+    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return pcm_dtype == MLA_F32 ? launch_fused<float>(pcm, n_wave, wave_stride, examples, tables, w, bias, out, s)
+                                : launch_fused<int16_t>(pcm, n_wave, wave_stride, examples, tables, w, bias, out, s);
 }

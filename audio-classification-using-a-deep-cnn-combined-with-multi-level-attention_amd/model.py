@@ -17,7 +17,7 @@ from torch import nn
 
 from . import differentiable, mla_train, ops, resnet
 from .params import *  # noqa: F401,F403  (T, H, K, DR, M_VGGISH, M_VGGISH_JB, S_VGGISH_SHAPE: model.py:9)
-from .torchvggish.vggish import Linear, VGGish
+from .torchvggish.vggish import Linear, PcmInput, VGGish
 
 
 class BatchNorm1d(nn.Module):
@@ -117,6 +117,12 @@ class Ensemble(nn.Module):
         self._waveforms_only_vggish()
         from . import frontend
         dtype = torch.bfloat16 if self.cnn.precision == "bf16" else torch.float32
+        feats = self.cnn.cnn_model[0] if self.just_bottlenecks else self.cnn.cnn_model.features
+        if ops.FUSED_FRONT and dtype == torch.bfloat16 and not differentiable.wants_grad(feats):
+            # bf16 inference: front-end + conv1 in one kernel, the examples tensor is never written
+            assert pcm.dim() == 2 and frontend.counts(pcm.shape[1])[1] == T, "each waveform must yield exactly T examples"
+            features = self.cnn(PcmInput(pcm))
+            return self.mla(features.reshape(-1, T, self.emb_input_size))
         ex = frontend.waveforms_to_examples(pcm, out_dtype=dtype)
         assert ex.shape[0] == pcm.shape[0] * T, "each waveform must yield exactly T examples"
         features = self.cnn(ex)

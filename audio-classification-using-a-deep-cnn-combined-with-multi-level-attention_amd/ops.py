@@ -3,6 +3,7 @@ buffers and the current stream; every number is produced by a HIP kernel of libm
 Nothing here falls back to torch ops."""
 
 import ctypes
+import os
 
 import torch
 
@@ -127,6 +128,29 @@ def conv1(x, w, b, dtype, split=False):
     out = torch.empty((n, 48, 32, 128 if split else 64), dtype=dtype, device=x.device)
     _lib.check(_timed("conv1", _lib.lib().mla_vggish_conv1, _p(x), DT[x.dtype], n, _p(w), _p(b), _p(out),
                       _lib.BF16X3 if split else DT[dtype], _lib.stream_ptr()))
+    return out
+
+
+# MLA_FUSED_FRONT=0 (read once, here): Ensemble.forward_waveforms in bf16 runs the front-end and conv1 as two kernels again
+# (A/B and bisecting). Tests flip the module variable.
+FUSED_FRONT = os.environ.get("MLA_FUSED_FRONT", "1") != "0"
+
+
+def logmel_conv1(pcm, w, b):
+    """(W, n) device PCM (float32 or int16) -> (W * N, 48, 32, 64) NHWC bf16 = conv1(waveforms_to_examples(pcm, bf16)), bit for
+    bit, in one kernel. Timed under the front-end's name ("logmel"); there is no "conv1" entry on this path."""
+    from . import frontend
+    assert pcm.dim() == 2 and pcm.is_cuda and pcm.stride(1) == 1 and pcm.dtype in (torch.float32, torch.int16)
+    _chk(w, torch.float32); _chk(b, torch.float32)
+    assert tuple(w.shape) == (64, 1, 3, 3)
+    n_wave, n_samples = pcm.shape
+    _, n_ex = frontend.counts(n_samples)
+    out = torch.empty((n_wave * n_ex, 48, 32, 64), dtype=torch.bfloat16, device=pcm.device)
+    if n_wave * n_ex == 0:
+        return out
+    tab = frontend.device_tables(pcm.device)
+    _lib.check(_timed("logmel", _lib.lib().mla_logmel_conv1, _p(pcm), DT[pcm.dtype], n_wave, n_samples,
+                      pcm.stride(0) if n_wave > 1 else n_samples, _p(tab), _p(w), _p(b), _p(out), _lib.stream_ptr()))
     return out
 
 

@@ -65,6 +65,14 @@ class _Cache:
         return self.val
 
 
+class PcmInput:
+    """(W, n) device PCM handed to VGGFeatures in place of log-mel examples: the bf16 inference path computes the front-end and
+    conv1 in one kernel (ops.logmel_conv1) and enters the stack at conv2."""
+
+    def __init__(self, pcm):
+        self.pcm = pcm
+
+
 class VGGFeatures(nn.Sequential):
     """nn.Sequential with the reference's layer indices (vggish.py:108-118) whose forward is the
     HIP conv stack: (N, 1, 96, 64) -> (N, 512, 6, 4). The result is an NCHW-shaped VIEW of NHWC
@@ -82,6 +90,15 @@ class VGGFeatures(nn.Sequential):
     def forward_nhwc(self, x, dtype):
         """x: (N, 96, 64) or (N, 1, 96, 64) examples, f32 or bf16 -> (N, 6, 4, 512) NHWC
         (precision "bf16x3": (N, 6, 4, 1024) = [hi(512) | lo(512)] per pixel)."""
+        convs = self._convs
+        if isinstance(x, PcmInput):
+            assert dtype == torch.bfloat16 and self.precision == "bf16", "the fused front is the bf16 inference path"
+            packed = self._cache.get([c.weight for c in convs[1:]], dtype,
+                                     lambda: [ops.repack_conv_weight(c.weight.detach().contiguous(), dtype) for c in convs[1:]])
+            h = ops.logmel_conv1(x.pcm, convs[0].weight.detach().contiguous(), convs[0].bias.detach())
+            for layer, (c, w) in enumerate(zip(convs[1:], packed), start=2):
+                h = ops.conv(layer, h, w, c.bias.detach())
+            return h
         x = x.detach().reshape(-1, 96, 64)
         if x.dtype not in (torch.float32, torch.bfloat16):
             x = x.float()
@@ -103,6 +120,8 @@ class VGGFeatures(nn.Sequential):
 
     def forward(self, x):
         from .. import differentiable as D
+        if isinstance(x, PcmInput):
+            return self.forward_nhwc(x, _DTYPES[self.precision]).permute(0, 3, 1, 2)
         if D.wants_grad(self):
             # a conv parameter requires grad and autograd is recording (the reference's loop, train.py:124-138, after
             # cnn_trainable=True / set_requires_grad): training forward with a tape, HIP backward kernels behind loss.backward()

@@ -149,6 +149,13 @@ int mla_linear_bf16x3(const void* a, int64_t lda, const void* w, int64_t ldw, co
 int mla_vggish_conv1(const void* x, int x_dtype, int64_t n, const float* w, const float* bias, void* out,
                      int dtype, mla_stream_t stream);
 
+/* mla_logmel_examples (bf16 examples) followed by mla_vggish_conv1 (bf16 in, bf16 out) as ONE kernel: the examples never
+ * exist in memory (vggish_input.py:30-82 -> mel_features.py:192-223 -> vggish.py:108-118 features[0..2] applied at :22).
+ * pcm / n_wave / n_samples / wave_stride / tables as for mla_logmel_examples, w / bias as for
+ * mla_vggish_conv1; out: (n_wave * examples, 48, 32, 64) NHWC bf16, bit-identical to the two calls. */
+int mla_logmel_conv1(const void* pcm, int pcm_dtype, int64_t n_wave, int64_t n_samples, int64_t wave_stride,
+                     const float* tables, const float* w, const float* bias, void* out, mla_stream_t stream);
+
 /* conv `layer` in 2..6 = features[3], [6], [8], [11], [13], each fused with its ReLU and,
  * for layers 2, 4 and 6, with the MaxPool2d(2, 2) that follows it:
  *   2: (n,48,32, 64) -> (n,24,16,128)     3: (n,24,16,128) -> (n,24,16,256)
