@@ -148,6 +148,8 @@ def lib():
         L.mla_rn_bn_bwd_workspace_bytes.restype = i64
         L.mla_rn_bn_bwd_workspace_bytes.argtypes = [i64]
         L.mla_rn_bn_bwd.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, cf, vp, vp, vp, vp, vp, ci, vp]
+        L.mla_rn_bn_bwd_sums.argtypes = [vp, vp, vp, i64, i64, vp, vp, cf, vp, vp, vp, vp, ci, vp]
+        L.mla_rn_bn_bwd_apply.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, cf, vp, vp, vp, vp, ci, vp]
         L.mla_rn_maxpool_bwd.argtypes = [vp, vp, i64, i64, i64, i64, vp, ci, vp]
         L.mla_rn_avgpool_bwd.argtypes = [vp, i64, i64, i64, vp, ci, vp]
         _lib = L

@@ -8,7 +8,9 @@
 //   rn_wgrad_kernel          weight gradient, a GEMM over the output pixels, split-K with f32 partials reduced in split
 //                            order by rn_wgrad_reduce_kernel; both operands go through an LDS transpose
 //   rn_stem_wgrad_*          stem weight gradient with the Input normalisation folded in (two sums per output / tap)
-//   rn_bn_bwd_*              BatchNorm2d train-mode backward (+ fused ReLU mask, + residual-path gradient)
+//   rn_bn_bwd_*              BatchNorm2d train-mode backward (+ fused ReLU mask, + residual-path gradient); rn_bn_bwd_sums_kernel
+//                            / rn_bn_bwd_coef_kernel split it around an all-reduce of [sum g, sum g xhat, rows] (SyncBN
+//                            across data-parallel ranks: the batch means of the global batch)
 //   rn_maxpool_bwd_kernel    MaxPool2d(3, 2, 1) backward as a gather (first maximum in torch's scan order)
 //   rn_avgpool_bwd_kernel    AdaptiveAvgPool2d(1) backward: dY / HW broadcast
 #include "rn_core.h"
@@ -309,9 +311,12 @@ __device__ __forceinline__ void bn_bwd_elems(const T* x, const T* dy, const T* y
     for (int k = 0; k < 8; ++k) xh[k] = (xv[k] - mean[c + k]) * invstd[c + k];
 }
 
+// one definition of 1 / sqrt(var + eps): rn_bn_bwd_invstd_kernel and stage 2's rn_bn_bwd_coef_kernel give the same bits
+__device__ __forceinline__ float bn_bwd_invstd(float var, float eps) { return float(1.0 / sqrt(double(var) + double(eps))); }
+
 __global__ void rn_bn_bwd_invstd_kernel(const float* __restrict__ var, float eps, int C, float* __restrict__ invstd) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) invstd[c] = float(1.0 / sqrt(double(var[c]) + double(eps)));
+    if (c < C) invstd[c] = bn_bwd_invstd(var[c], eps);
 }
 
 template <typename T>
@@ -323,19 +328,62 @@ __global__ __launch_bounds__(256) void rn_bn_bwd_partial_kernel(const T* __restr
     });
 }
 
-// per channel: coef[c] = mean(g), coef[C + c] = mean(g xhat), coef[2C + c] = gamma invstd; dgamma / dbeta if requested
+// What the fused and the split (SyncBN) backward share per channel. bn_bwd_local: the local sums in slice order, dgamma / dbeta
+// from them if requested. bn_bwd_coefs: coef[c] = mean(g), coef[C + c] = mean(g xhat), coef[2C + c] = gamma invstd, the means
+// over `count` rows (the local rows, or the global batch's after an all-reduce of the sums).
+__device__ __forceinline__ void bn_bwd_local(const double* __restrict__ part, int P, int C, int c, float* __restrict__ dgamma,
+                                             float* __restrict__ dbeta, double& s, double& s2) {
+    bn_sum_slices(part, P, C, c, s, s2);
+    if (dgamma) dgamma[c] = float(s2);
+    if (dbeta) dbeta[c] = float(s);
+}
+
+__device__ __forceinline__ void bn_bwd_coefs(int C, int c, double s, double s2, double count, float gamma, float invstd,
+                                             float* __restrict__ coef) {
+    coef[c] = float(s / count);
+    coef[C + c] = float(s2 / count);
+    coef[2 * C + c] = gamma * invstd;
+}
+
 __global__ void rn_bn_bwd_finish_kernel(const double* __restrict__ part, int P, int C, int64_t rows, const float* __restrict__ gamma,
                                         const float* __restrict__ invstd, float* __restrict__ coef, float* __restrict__ dgamma,
                                         float* __restrict__ dbeta) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double s, s2;
-    bn_sum_slices(part, P, C, c, s, s2);
-    coef[c] = float(s / double(rows));
-    coef[C + c] = float(s2 / double(rows));
-    coef[2 * C + c] = gamma[c] * invstd[c];
-    if (dgamma) dgamma[c] = float(s2);
-    if (dbeta) dbeta[c] = float(s);
+    bn_bwd_local(part, P, C, c, dgamma, dbeta, s, s2);
+    bn_bwd_coefs(C, c, s, s2, double(rows), gamma[c], invstd[c], coef);
+}
+
+// Stage 1 of the split: sums = [sum g (C), sum g xhat (C), rows], the message of the all-reduce. dgamma / dbeta are this
+// rank's part (the gradient all-reduce adds the ranks' parts), so they are written here, from the LOCAL sums.
+__global__ void rn_bn_bwd_sums_kernel(const double* __restrict__ part, int P, int C, int64_t rows, double* __restrict__ sums,
+                                      float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double s, s2;
+    bn_bwd_local(part, P, C, c, dgamma, dbeta, s, s2);
+    sums[c] = s;
+    sums[C + c] = s2;
+    if (c == 0) sums[2 * int64_t(C)] = double(rows);
+}
+
+// Stage 2: invstd (recomputed: nothing has to survive in the workspace from stage 1) and the coefficients from the
+// (all-reduced) sums; the row count is the message's last element. A count that is not > 0 (a message that did not come from
+// stage 1 on every rank) cannot be refused on the host without a device-to-host copy: the coefficients become NaN, so that
+// every dx element is NaN instead of a plausible wrong number.
+__global__ void rn_bn_bwd_coef_kernel(const double* __restrict__ sums, int C, const float* __restrict__ var, float eps,
+                                      const float* __restrict__ gamma, float* __restrict__ invstd, float* __restrict__ coef) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float is = bn_bwd_invstd(var[c], eps);
+    invstd[c] = is;
+    const double count = sums[2 * int64_t(C)];
+    if (count > 0.0) {
+        bn_bwd_coefs(C, c, sums[c], sums[C + c], count, gamma[c], is, coef);
+    } else {
+        coef[c] = coef[C + c] = coef[2 * C + c] = __builtin_nanf("");
+    }
 }
 
 template <typename T>
@@ -548,42 +596,108 @@ extern "C" int64_t mla_rn_bn_bwd_workspace_bytes(int64_t channels) {
     return 2 * int64_t(kMaxSlices) * channels * int64_t(sizeof(double)) + 4 * channels * int64_t(sizeof(float));
 }
 
-extern "C" int mla_rn_bn_bwd(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean, const float* var,
-                             const float* gamma, float eps, void* workspace, float* dgamma, float* dbeta, void* dx, void* dres, int dtype,
-                             mla_stream_t stream) {
+namespace {
+
+// The workspace of mla_rn_bn_bwd_workspace_bytes: [slice partials: 2 kMaxSlices C doubles][invstd: C floats][coef: 3 C floats].
+struct BnBwdWs {
+    double* part;
+    float* invstd;
+    float* coef;
+    BnBwdWs(void* workspace, int64_t channels)
+        : part(static_cast<double*>(workspace)), invstd(reinterpret_cast<float*>(part + 2 * int64_t(kMaxSlices) * channels)),
+          coef(invstd + channels) {}
+};
+
+// The argument checks of the three entry points; `others` / `others_aligned`: what the caller found for its own buffers
+// (gamma, sums, dx, dres), folded in so that the order of the checks is shape, NULL, alignment, dtype for each of them.
+int bn_bwd_check(const char* who, const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean,
+                 const float* var, const void* workspace, bool others, bool others_aligned, int dtype) {
     MLA_REQUIRE(rows > 0 && channels > 0 && channels % 64 == 0 && channels <= 65536 * 64, MLA_E_SHAPE,
-                "rn_bn_bwd rows %lld channels %lld (channels: multiple of 64)", (long long)rows, (long long)channels);
-    MLA_REQUIRE(x && dy && mean && var && gamma && workspace && dx, MLA_E_ARG, "null rn_bn_bwd buffers");
-    MLA_REQUIRE(mla::aligned(x, 16) && mla::aligned(dy, 16) && mla::aligned(y, 16) && mla::aligned(dx, 16) && mla::aligned(dres, 16) &&
-                    mla::aligned(workspace, 8),
-                MLA_E_ARG, "rn_bn_bwd buffers must be 16-byte aligned");
-    MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_bn_bwd dtype %d", dtype);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                "%s rows %lld channels %lld (channels: multiple of 64)", who, (long long)rows, (long long)channels);
+    MLA_REQUIRE(x && dy && mean && var && workspace && others, MLA_E_ARG, "null %s buffers", who);
+    MLA_REQUIRE(mla::aligned(x, 16) && mla::aligned(dy, 16) && mla::aligned(y, 16) && mla::aligned(workspace, 8) && others_aligned, MLA_E_ARG,
+                "%s buffers must be 16-byte aligned (sums: 8-byte)", who);
+    MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "%s dtype %d", who, dtype);
+    return MLA_OK;
+}
+
+// invstd and the slice partials of (g, g xhat): the first half of the fused call and of stage 1
+int bn_bwd_partials(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean, const float* var,
+                    float eps, const BnBwdWs& ws, int dtype, hipStream_t s, int* slices) {
     const int P = bn_slices(rows);
     const int C = int(channels);
-    double* part = static_cast<double*>(workspace);
-    float* invstd = reinterpret_cast<float*>(part + 2 * int64_t(kMaxSlices) * channels);
-    float* coef = invstd + channels;
-    hipLaunchKernelGGL(rn_bn_bwd_invstd_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, var, eps, C, invstd);
+    hipLaunchKernelGGL(rn_bn_bwd_invstd_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, var, eps, C, ws.invstd);
     MLA_LAUNCH_OK("rn_bn_bwd_invstd_kernel");
     const dim3 grid(unsigned(channels / 64), unsigned(P));
-    const int64_t n8 = rows * channels / 8;
     rn_dispatch(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
         hipLaunchKernelGGL(rn_bn_bwd_partial_kernel<T>, grid, dim3(256), 0, s, static_cast<const T*>(x), static_cast<const T*>(dy),
-                           static_cast<const T*>(y), mean, invstd, rows, C, part);
+                           static_cast<const T*>(y), mean, ws.invstd, rows, C, ws.part);
     });
     MLA_LAUNCH_OK("rn_bn_bwd_partial_kernel");
-    hipLaunchKernelGGL(rn_bn_bwd_finish_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, part, P, C, rows, gamma, invstd, coef,
-                       dgamma, dbeta);
-    MLA_LAUNCH_OK("rn_bn_bwd_finish_kernel");
+    *slices = P;
+    return MLA_OK;
+}
+
+// dx (and dres) from ws.invstd / ws.coef: the second half of the fused call and of stage 2
+int bn_bwd_elementwise(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean, const BnBwdWs& ws,
+                       void* dx, void* dres, int dtype, hipStream_t s) {
+    const int64_t n8 = rows * channels / 8;
     rn_dispatch(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
         hipLaunchKernelGGL(rn_bn_bwd_apply_kernel<T>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const T*>(x), static_cast<const T*>(dy),
-                           static_cast<const T*>(y), mean, invstd, coef, n8, C, static_cast<T*>(dx), static_cast<T*>(dres));
+                           static_cast<const T*>(y), mean, ws.invstd, ws.coef, n8, int(channels), static_cast<T*>(dx), static_cast<T*>(dres));
     });
     MLA_LAUNCH_OK("rn_bn_bwd_apply_kernel");
     return MLA_OK;
+}
+
+}  // namespace
+
+extern "C" int mla_rn_bn_bwd(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean, const float* var,
+                             const float* gamma, float eps, void* workspace, float* dgamma, float* dbeta, void* dx, void* dres, int dtype,
+                             mla_stream_t stream) {
+    int rc = bn_bwd_check("rn_bn_bwd", x, dy, y, rows, channels, mean, var, workspace, gamma && dx,
+                          mla::aligned(dx, 16) && mla::aligned(dres, 16), dtype);
+    if (rc != MLA_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const BnBwdWs ws(workspace, channels);
+    int P = 0;
+    if ((rc = bn_bwd_partials(x, dy, y, rows, channels, mean, var, eps, ws, dtype, s, &P)) != MLA_OK) return rc;
+    hipLaunchKernelGGL(rn_bn_bwd_finish_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, ws.part, P, int(channels), rows,
+                       gamma, ws.invstd, ws.coef, dgamma, dbeta);
+    MLA_LAUNCH_OK("rn_bn_bwd_finish_kernel");
+    return bn_bwd_elementwise(x, dy, y, rows, channels, mean, ws, dx, dres, dtype, s);
+}
+
+extern "C" int mla_rn_bn_bwd_sums(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean,
+                                  const float* var, float eps, void* workspace, double* sums, float* dgamma, float* dbeta, int dtype,
+                                  mla_stream_t stream) {
+    int rc = bn_bwd_check("rn_bn_bwd_sums", x, dy, y, rows, channels, mean, var, workspace, sums != nullptr, mla::aligned(sums, 8), dtype);
+    if (rc != MLA_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const BnBwdWs ws(workspace, channels);
+    int P = 0;
+    if ((rc = bn_bwd_partials(x, dy, y, rows, channels, mean, var, eps, ws, dtype, s, &P)) != MLA_OK) return rc;
+    hipLaunchKernelGGL(rn_bn_bwd_sums_kernel, dim3(unsigned((channels + 255) / 256)), dim3(256), 0, s, ws.part, P, int(channels), rows, sums,
+                       dgamma, dbeta);
+    MLA_LAUNCH_OK("rn_bn_bwd_sums_kernel");
+    return MLA_OK;
+}
+
+extern "C" int mla_rn_bn_bwd_apply(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean,
+                                   const float* var, const float* gamma, float eps, const double* sums, void* workspace, void* dx, void* dres,
+                                   int dtype, mla_stream_t stream) {
+    const int rc = bn_bwd_check("rn_bn_bwd_apply", x, dy, y, rows, channels, mean, var, workspace, gamma && sums && dx,
+                                mla::aligned(sums, 8) && mla::aligned(dx, 16) && mla::aligned(dres, 16), dtype);
+    if (rc != MLA_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const BnBwdWs ws(workspace, channels);
+    const int C = int(channels);
+    const dim3 per_channel(unsigned((channels + 255) / 256));
+    hipLaunchKernelGGL(rn_bn_bwd_coef_kernel, per_channel, dim3(256), 0, s, sums, C, var, eps, gamma, ws.invstd, ws.coef);
+    MLA_LAUNCH_OK("rn_bn_bwd_coef_kernel");
+    return bn_bwd_elementwise(x, dy, y, rows, channels, mean, ws, dx, dres, dtype, s);
 }
 
 extern "C" int mla_rn_maxpool_bwd(const void* in, const void* dy, int64_t n, int64_t H, int64_t W, int64_t channels, void* dx, int dtype,

@@ -926,6 +926,34 @@ def rn_bn_bwd(x, dy, mean, var, bn, y=None, want_dres=False, dgamma=None, dbeta=
     return dx, dres
 
 
+def rn_bn_bwd_sync(x, dy, mean, var, bn, dist, y=None, want_dres=False, dgamma=None, dbeta=None):
+    """rn_bn_bwd under SyncBN: mean / var are the statistics of the data-parallel group's global batch (rn_bn_stats_sync with
+    want_stats), and so are the two batch means of the backward: [sum g, sum g xhat, rows] of the local shard, all-reduced (tag
+    "syncbn_rn_bwd"), then applied to the local rows. The row count travels in the message, so shards may differ in size. dgamma /
+    dbeta receive this rank's part (from the local sums): the gradient all-reduce adds the ranks' parts. Without an active SyncBN
+    group (no group, or sync_bn=False) this is rn_bn_bwd itself, bit for bit. The message's last element, the global row
+    count, must come out > 0 (every rank contributes its own rows); stage 2 reads it on the device and answers anything else with
+    an all-NaN dx, not with an exception."""
+    if not dist.bn_active:
+        return rn_bn_bwd(x, dy, mean, var, bn, y=y, want_dres=want_dres, dgamma=dgamma, dbeta=dbeta)
+    _chk(x); _chk(dy, x.dtype)
+    if y is not None:
+        _chk(y, x.dtype)
+    C = x.shape[-1]
+    rows = x.numel() // C
+    L = _lib.lib()
+    ws = torch.empty(int(L.mla_rn_bn_bwd_workspace_bytes(C)) // 8, dtype=torch.float64, device=x.device)
+    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+    _lib.check(_timed("rn_bn_bwd_sums", L.mla_rn_bn_bwd_sums, _p(x), _p(dy), _p(y), rows, C, _p(mean), _p(var), float(bn.eps), _p(ws), _p(sums),
+                      _p(dgamma), _p(dbeta), DT[x.dtype], _lib.stream_ptr()))
+    dist.all_reduce_sum(sums, "syncbn_rn_bwd")
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if want_dres else None
+    _lib.check(_timed("rn_bn_bwd_apply", L.mla_rn_bn_bwd_apply, _p(x), _p(dy), _p(y), rows, C, _p(mean), _p(var), _p(bn.weight.detach()),
+                      float(bn.eps), _p(sums), _p(ws), _p(dx), _p(dres), DT[x.dtype], _lib.stream_ptr()))
+    return dx, dres
+
+
 def rn_maxpool_bwd(x, dy):
     """MaxPool2d(3, 2, 1) backward: x the pooled input (N, H, W, C), dy (N, Ho, Wo, C) -> dx like x."""
     _chk(x); _chk(dy, x.dtype)

@@ -240,12 +240,15 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None, tape=None
     return ops.rn_avgpool(h)
 
 
-def trunk_backward(cnn_model, tape, d_feats, grads):
+def trunk_backward(cnn_model, tape, d_feats, grads, dist=None):
     """Backward of the train-mode trunk forward recorded in `tape`: d_feats (N, 2048) f32, the gradient of the features ->
     the f32 gradients of the trunk parameters in `grads` ({id(parameter): tensor to write}); only those are computed. The
     blocks are walked in reverse (at a block input the main-path and skip-path gradients are summed by the conv epilogue)
     down to the lowest unit holding a requested parameter; weight gradients nobody asked for are skipped. The tape is
-    consumed (its tensors are released as the walk passes them)."""
+    consumed (its tensors are released as the walk passes them). dist: the ``ops.Dist`` the forward ran under; with SyncBN
+    active every BatchNorm2d backward all-reduces its two batch sums (one message per layer the walk passes), so dx is that of
+    the global batch. Convs, weight gradients, stem and pools are per-sample linear: they stay local, and `grads` holds this
+    rank's part of every parameter gradient (the caller's gradient all-reduce sums the parts)."""
     conv1, bn1, layers, _ = parts(cnn_model)
     blocks = [b for layer in layers for b in layer]
     units = [[conv1, bn1]] + [[b] for b in blocks]                 # unit 0: stem; unit k: blocks[k - 1]
@@ -254,6 +257,7 @@ def trunk_backward(cnn_model, tape, d_feats, grads):
         return
     lowest = wanted.index(True)
     dtype, bns = tape["dtype"], tape["bn"]
+    dist = dist or ops._local()
     g = grads.get
     d = ops.rn_avgpool_bwd(d_feats, tape["last_shape"], dtype)
 
@@ -266,7 +270,7 @@ def trunk_backward(cnn_model, tape, d_feats, grads):
 
     def bn_bwd(bn, dy, want_dres=False):
         x, mean, var, y = bns.pop(id(bn))
-        return ops.rn_bn_bwd(x, dy, mean, var, bn, y=y, want_dres=want_dres, dgamma=g(id(bn.weight)), dbeta=g(id(bn.bias)))
+        return ops.rn_bn_bwd_sync(x, dy, mean, var, bn, dist, y=y, want_dres=want_dres, dgamma=g(id(bn.weight)), dbeta=g(id(bn.bias)))
 
     for k in range(len(blocks), max(lowest, 1) - 1, -1):
         b = blocks[k - 1]

@@ -64,13 +64,17 @@ class TrainStep:
     (model.py:237-238); like torch's Adam (which skips ``grad is None``) they are left untouched.
     """
 
-    def __init__(self, clf, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, params=None, sync_bn=True, graph=None):
+    def __init__(self, clf, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, params=None, sync_bn=True, graph=None,
+                 trunk_data_parallel=False):
         """``params``: the parameters the caller's optimizer holds (``optimizer.param_groups[...]["params"]``); None =
         every parameter that requires grad. Exactly the tensors in ``params`` that require grad are updated, as
         ``optimizer.step()`` does in the reference (train.py:138; torch's Adam skips parameters whose ``.grad`` is None,
         i.e. the frozen ones). Gradients of parameters OUTSIDE that set are not computed: the reference computes and then
         never applies them (its ``__main__`` builds the Adam before ``set_requires_grad(clf, True)``, train.py:369-370 vs
-        :96-97, so its "finetune" run only ever steps the MLA head) -- the updated model is the same."""
+        :96-97, so its "finetune" run only ever steps the MLA head) -- the updated model is the same.
+        ``trunk_data_parallel``: allow ResNet trunk parameters in the update set under a process group (off: that combination is
+        refused). The step then equals the single-process step on the global batch: SyncBN in the trunk's forward AND backward
+        (``ops.rn_bn_bwd_sync``), gradients summed by one flat all-reduce. The head keeps its equal-shard contract."""
         self.clf, self.lr, self.betas, self.eps, self.t = clf, lr, betas, eps, 0
         # sync_bn=False: per-shard BatchNorm statistics under data parallelism (DistributedDataParallel semantics) instead of the
         # global-batch statistics that reproduce the reference's single-process step; see ops.Dist
@@ -99,7 +103,11 @@ class TrainStep:
             if trunk and not getattr(clf.cnn, "trunk_backward", False):
                 raise NotImplementedError("gradients into the ResNet trunk are off (parameter %s is in the update set); turn the HIP "
                                           "trunk backward on with clf.set_trunk_backward(True)" % trunk[0])
-            if trunk and (self.dist.active or self.dist.backend is not None):       # under a torch.distributed process group
+            # under a torch.distributed process group: opt-in (trunk_data_parallel=True). The trunk backward then all-reduces the
+            # two batch sums of each BatchNorm2d it passes (SyncBN; none with sync_bn=False), and the trunk's gradients travel in
+            # the one flat all-reduce after the backward -- no overlapped buckets: the per-layer collectives of the compute stream
+            # and bucket all-reduces of a second stream would use the one communicator from two streams at once
+            if trunk and (self.dist.active or self.dist.backend is not None) and not trunk_data_parallel:
                 raise NotImplementedError("data-parallel training of the ResNet trunk is not built: its SyncBN backward needs sum(dy) "
                                           "and sum(dy * xhat) all-reduced per BatchNorm2d layer (parameter %s is in the update set); "
                                           "frozen-trunk data parallelism is supported" % trunk[0])
@@ -297,7 +305,7 @@ class TrainStep:
                                            gb if gb is not None else torch.empty_like(fc.bias, dtype=torch.float32))
         if self.rn_trunk:                      # head -> fc -> trunk: the trunk's gradients land in the flat buffer
             from . import resnet
-            resnet.trunk_backward(clf.cnn.cnn_model, rn_tape, d_feats.reshape(-1, 2048).contiguous(), self.rn_trunk)
+            resnet.trunk_backward(clf.cnn.cnn_model, rn_tape, d_feats.reshape(-1, 2048).contiguous(), self.rn_trunk, dist=self.dist)
         bucketed = self.dist.active and self.finetune and self.overlap
         if bucketed:
             # the head's gradients are final: reduce them while the CNN backward runs; each CNN bucket follows as soon as

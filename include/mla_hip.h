@@ -508,6 +508,27 @@ int64_t mla_rn_bn_bwd_workspace_bytes(int64_t channels);
 int mla_rn_bn_bwd(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean, const float* var_biased,
                   const float* gamma, float eps, void* workspace, float* dgamma, float* dbeta, void* dx, void* dres, int dtype,
                   mla_stream_t stream);
+/* mla_rn_bn_bwd in two stages, so that an all-reduce over the data-parallel ranks fits between them: the backward of the
+ * trunk's SyncBN (bn1..bn3 / downsample.1 / resnet.bn1 of model.py:129 under loss.backward(), train.py:137, on the GLOBAL
+ * batch). mean / var_biased are the statistics the forward normalised with (under SyncBN those of the global batch,
+ * mla_rn_bn_finish). Stage 1 runs the sums of mla_rn_bn_bwd (same kernels, same ReLU mask from y, slices added in the same
+ * order) on this rank's rows and writes sums = [sum g (channels), sum g xhat (channels), rows] in double (2*channels + 1
+ * elements): the row count travels with the message, so ranks may hold different numbers of rows. dgamma / dbeta (each NULL
+ * to skip) are written by STAGE 1 from the LOCAL sums: they are this rank's part of a parameter gradient, which the gradient
+ * all-reduce adds over the ranks (taken from the all-reduced sums they would be counted once per rank). Stage 2 forms
+ * mean(g) = sums[c] / sums[2*channels] and mean(g xhat) likewise -- the count is read from the message on the device and must
+ * be > 0 (it is whenever every contribution came from stage 1, which refuses rows <= 0); the host cannot see it without a
+ * blocking copy, so a count that is not > 0 is not MLA_E_ARG but makes every element of dx NaN -- and applies them to this rank's
+ * `rows` rows: dx, and dres (or NULL) as in mla_rn_bn_bwd. For one rank, stage 1 followed by stage 2 gives the bits of
+ * mla_rn_bn_bwd (same partial and apply kernels, the same per-channel arithmetic). workspace:
+ * mla_rn_bn_bwd_workspace_bytes(channels) bytes for either stage; nothing in it has to survive from stage 1 to stage 2
+ * (stage 2 holds its per-channel coefficients there). No float atomics; every reduction runs in a fixed order. */
+int mla_rn_bn_bwd_sums(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean,
+                       const float* var_biased, float eps, void* workspace, double* sums, float* dgamma, float* dbeta, int dtype,
+                       mla_stream_t stream);
+int mla_rn_bn_bwd_apply(const void* x, const void* dy, const void* y, int64_t rows, int64_t channels, const float* mean,
+                        const float* var_biased, const float* gamma, float eps, const double* sums, void* workspace, void* dx, void* dres,
+                        int dtype, mla_stream_t stream);
 /* Backward of mla_rn_maxpool (resnet.maxpool, model.py:129): in (n, H, W, channels) the pooled input, dy the pooled gradient ->
  * dx (n, H, W, channels). Gradient routed to the FIRST maximum of each window in torch's scan order (ky-major, strict >). */
 int mla_rn_maxpool_bwd(const void* in, const void* dy, int64_t n, int64_t H, int64_t W, int64_t channels, void* dx, int dtype,

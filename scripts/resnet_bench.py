@@ -3,12 +3,17 @@
 5 120 images, the frozen training step (TrainStep) at 8 and 64 bags, and -- as a yardstick only -- the same network built
 from torch.nn.functional.conv2d in channels-last bf16 (MIOpen). Prints one JSON line.
 
-    python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank] [--finetune]
+    python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank [--finetune]] [--finetune]
 
 --per-conv: instead, each distinct bf16 conv (and the stem) timed alone at 80 images against its own roofline.
 --dp-one-rank: instead, the cost of the trunk's SyncBN on one GPU: the frozen bf16 step (eager) at 8 and 64 bags without a
 process group and on a one-rank RCCL group with the collectives forced on (ops.Dist(always=True)), where each of the 53
 BatchNorm2d layers runs sums -> all-reduce -> finish; the all-reduces are counted and timed from ops.Dist.trace.
+--dp-one-rank --finetune: the same question for the trunk-FINETUNING bf16 step (cnn_trainable=True, 53 forward + 53 backward
+SyncBN all-reduces and one flat gradient all-reduce per step): the step without a group (default graph mode: the yardstick, to
+be read against profiles/resnet_finetune.json), without a group but eager, and on the one-rank RCCL group with the collectives
+forced on (TrainStep(..., trunk_data_parallel=True); eager, as every data-parallel step), interleaved round by round in one
+session on one device; writes profiles/resnet_dp_finetune_one_rank.json. More than one rank is not measured by this.
 --finetune: instead, the trunk-finetuning step (cnn_trainable=True with the HIP trunk backward on, TrainStep, default graph
 mode) in bf16 and f32 at 8 and 64 bags next to the frozen bf16 step, and torch autograd's forward + backward of the restated
 ResNet-50 trunk (channels-last bf16, MIOpen, train mode) as the yardstick; writes profiles/resnet_finetune.json.
@@ -153,6 +158,73 @@ def dp_one_rank(sd):
     dist.destroy_process_group()
 
 
+def dp_finetune_one_rank(sd):
+    """See --dp-one-rank --finetune in the module docstring."""
+    import statistics
+    import torch.distributed as dist
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+
+    def make(**kw):
+        ens = M.Ensemble("repeat", dict(CONF, cnn_trainable=True), [2, 1], dev, precision="bf16", trunk_backward=True)
+        ens.load_state_dict(sd)
+        return TR.TrainStep(ens.cuda(), lr=1e-4, **kw)
+    os.environ["MLA_DIST_ALWAYS"] = "0"
+    steps = {"no_group": make(), "no_group_eager": make(graph=False)}          # built before any process group exists
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if "MASTER_PORT" not in os.environ:                                        # a free port: several users may share the host
+        import socket
+        with socket.socket() as sock:
+            sock.bind(("127.0.0.1", 0))
+            os.environ["MASTER_PORT"] = str(sock.getsockname()[1])
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    os.environ["MLA_DIST_ALWAYS"] = "1"
+    steps["dist_one_rank"] = make(trunk_data_parallel=True)
+    os.environ.pop("MLA_DIST_ALWAYS", None)
+    assert steps["dist_one_rank"].dist.active and not steps["no_group"].dist.active and not steps["no_group_eager"].dist.active
+    res = {"metric": "resnet50_finetune_step_dp_one_rank", "device": torch.cuda.get_device_name(0), "precision": "bf16",
+           "just_bottlenecks": True, "optimizer": "adam lr 1e-4", "transport": steps["dist_one_rank"].dist.describe()["transport"],
+           "rounds": 3, "steps_per_round": 5, "ranks_measured": 1}
+    for bags in (8, 64):
+        x = torch.rand(bags, 10, 1, 224, 224, device=dev)
+        y = torch.arange(bags, device=dev) % 10
+        times = {k: [] for k in steps}
+        for step in steps.values():                                            # eager first step, graph capture, clocks
+            timeit(lambda: step(x, y), 3, 1)
+        for _ in range(res["rounds"]):
+            for k, step in steps.items():
+                times[k].append(timeit(lambda: step(x, y), 0, res["steps_per_round"]) * 1e3)
+        for k, v in times.items():
+            res["finetune_step_%d_bags_ms_%s" % (bags, k)] = round(statistics.median(v), 2)
+            res["finetune_step_%d_bags_ms_%s_rounds" % (bags, k)] = [round(t, 2) for t in v]
+        step = steps["dist_one_rank"]
+        step.dist.trace, n = [], 5
+        for _ in range(n):
+            step(x, y)
+        torch.cuda.synchronize()
+        for tag in ("syncbn_rn", "syncbn_rn_bwd", "grad:flat"):
+            sel = [t for t in step.dist.trace if t[0] == tag]
+            key = tag.replace(":", "_")
+            # counts and bytes do not depend on the number of bags (one key, written by both passes); the times do
+            res["%s_allreduces_per_step" % key] = len(sel) // n
+            res["%s_bytes_per_step" % key] = sum(t[1] for t in sel) // n
+            res["%s_ms_per_step_%d_bags" % (key, bags)] = round(sum(t[2].elapsed_time(t[3]) for t in sel) / n, 3)
+        res["other_allreduces_per_step"] = sum(t[0] not in ("syncbn_rn", "syncbn_rn_bwd", "grad:flat") for t in step.dist.trace) // n
+        step.dist.trace = None
+        res["peak_gb_%d_bags" % bags] = round(torch.cuda.max_memory_allocated() / 1e9, 2)     # the three steps together
+        # two yardsticks: the eager no-group step isolates the collectives; the graphed one adds what eager launching costs
+        res["dist_overhead_ms_%d_bags_vs_eager" % bags] = round(res["finetune_step_%d_bags_ms_dist_one_rank" % bags] -
+                                                               res["finetune_step_%d_bags_ms_no_group_eager" % bags], 2)
+        res["dist_overhead_ms_%d_bags_vs_graph" % bags] = round(res["finetune_step_%d_bags_ms_dist_one_rank" % bags] -
+                                                               res["finetune_step_%d_bags_ms_no_group" % bags], 2)
+    steps["dist_one_rank"].dist.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "resnet_dp_finetune_one_rank.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    dist.destroy_process_group()
+
+
 def finetune(sd):
     """See --finetune in the module docstring."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -198,7 +270,7 @@ def main():
     dev = torch.device("cuda")
     sd = {k: torch.as_tensor(v) for k, v in W.make_state_dict(21, W.ensemble_shapes((2, 1), True, cnn_type="resnet")).items()}
     if "--dp-one-rank" in sys.argv:
-        return dp_one_rank(sd)
+        return dp_finetune_one_rank(sd) if "--finetune" in sys.argv else dp_one_rank(sd)
     if "--finetune" in sys.argv:
         return finetune(sd)
     if "--per-conv" in sys.argv:
