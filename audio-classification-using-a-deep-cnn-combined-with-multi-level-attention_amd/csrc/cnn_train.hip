@@ -338,6 +338,7 @@ extern "C" int mla_maxpool2x2(const float* a, float* out, int64_t n, int H, int 
 extern "C" int mla_relu_pool_bwd(const float* a, const float* d_out, float* dz, int64_t n, int H, int W, int C, int pool,
                                  mla_stream_t stream) {
     MLA_REQUIRE(a && d_out && dz && n >= 0, MLA_E_ARG, "bad relu_pool_bwd arguments");
+    MLA_REQUIRE(!pool || (H % 2 == 0 && W % 2 == 0), MLA_E_SHAPE, "pooling needs even H, W");
     const int64_t total = pool ? n * (H / 2) * (W / 2) * C : n * H * W * C;
     if (total == 0) return MLA_OK;
     const unsigned grid = unsigned((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);

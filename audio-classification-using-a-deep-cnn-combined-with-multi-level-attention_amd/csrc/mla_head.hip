@@ -594,8 +594,13 @@ extern "C" int mla_bn_bwd_apply(const float* x, int64_t ldx, const float* dy, in
                                 const float* var, const float* gamma, float eps, const double* sums_global,
                                 const double* sums_local, double count, float* dx, int64_t ld_dx, int accumulate,
                                 float* dgamma, float* dbeta, mla_stream_t stream) {
-    MLA_REQUIRE(x && dy && mean && var && gamma && sums_global && sums_local && count > 0, MLA_E_ARG, "bad bn_bwd_apply arguments");
+    MLA_REQUIRE(x && dy && mean && var && gamma && sums_global && sums_local && count > 0 && rows > 0 && cols > 0, MLA_E_ARG,
+                "bad bn_bwd_apply arguments");
     MLA_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), MLA_E_ARG, "dgamma and dbeta go together");
+    MLA_REQUIRE(act == 0 || yout, MLA_E_ARG, "bn_bwd needs the forward output for act %d", act);
+    // the same channel layout mla_bn_bwd_sums accepts (period 0 in mode 0 would reach r % period on the device)
+    MLA_REQUIRE((mode == 0 && period >= 1 && period <= kMaxChannels && rows % period == 0) || (mode == 1 && cols <= kMaxChannels),
+                MLA_E_SHAPE, "bn_bwd channel layout");
     BwdOp op{x, dy, yout, mean, var, ldx, ld_dy, ld_y, act, drop_scale, eps};
     const int64_t total = rows * cols;
     const unsigned grid = dx ? unsigned((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192) : 1u;

@@ -58,6 +58,16 @@ def _chk(t, dtype=None):
     return t
 
 
+def _chk_rows(t, dtype=None):
+    """A 2-D operand of an entry point that takes a row pitch: whatever _chk accepts, and rows that are strided (a column slice
+    of a wider tensor)."""
+    assert t.is_cuda and t.dim() == 2 and (t.is_contiguous() or (t.stride(1) == 1 and t.stride(0) >= t.shape[1])), \
+        "HIP ops need CUDA matrices with contiguous rows"
+    if dtype is not None:
+        assert t.dtype == dtype, (t.dtype, dtype)
+    return t
+
+
 def repack_conv_weight(w, dtype):
     """(Cout, Cin, 3, 3) f32 -> (Cout, 9, Cin) in `dtype`."""
     _chk(w, torch.float32)
@@ -254,10 +264,10 @@ def bn_stats(x, mode, period, running_mean=None, running_var=None, momentum=-1.0
 
 
 def bn_apply(x, mode, period, mean, var, gamma, beta, act=0, keep_mask=None, drop_scale=1.0, out=None):
-    _chk(x, torch.float32)
+    _chk_rows(x, torch.float32)
     rows, cols = x.shape
     if out is None:
-        out = torch.empty_like(x)
+        out = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
     if keep_mask is not None:
         _chk(keep_mask, torch.uint8)
         assert keep_mask.numel() == rows * cols
@@ -468,11 +478,17 @@ def bn_stats_sync(x, mode, period, dist, running_mean=None, running_var=None, mo
 
 
 def bn_backward(x, dy, yout, act, drop_scale, mode, period, mean, var, gamma, dist, dgamma, dbeta, want_dx=True,
-                dx=None, accumulate=False, batch_stats=True):
+                dx=None, accumulate=False, batch_stats=True, count=None):
     """BatchNorm backward through the fused activation/dropout. Writes dgamma/dbeta (local parts) and returns dx (global-batch
     exact under data parallelism). batch_stats=False: the forward normalised with FIXED statistics (eval mode: mean / var are the
-    running buffers), so dx = gamma * rstd * g without the two batch-mean terms -- the same kernels with zero sums for dx."""
-    _chk(x, torch.float32)
+    running buffers), so dx = gamma * rstd * g without the two batch-mean terms -- the same kernels with zero sums for dx.
+    x, dy, yout: rows may be strided (the kernels take a pitch; 16-byte loads only where pitch and address allow).
+    count: elements per channel in the GLOBAL batch; None = this shard's count times the number of shards (the training step's
+    equal-shard contract). Shards of different sizes pass the true global count. Only this backward takes it: bn_stats_sync and
+    the training step still assume equal shards, so unequal shards are NOT supported end to end."""
+    _chk_rows(x, torch.float32); _chk_rows(dy, torch.float32)
+    if yout is not None:
+        _chk_rows(yout, torch.float32)
     rows, cols = x.shape
     ch = period if mode == 0 else cols
     L = _lib.lib()
@@ -485,7 +501,8 @@ def bn_backward(x, dy, yout, act, drop_scale, mode, period, mean, var, gamma, di
         glob = torch.zeros_like(local)
     elif dist.bn_active:
         glob = dist.all_reduce_sum(local.clone(), "syncbn_bwd")
-    count = (rows // period * cols if mode == 0 else rows) * dist.bn_world
+    if count is None:
+        count = (rows // period * cols if mode == 0 else rows) * dist.bn_world
     if want_dx and dx is None:
         dx = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
     _lib.check(L.mla_bn_bwd_apply(_p(x), x.stride(0), _p(dy), dy.stride(0), _p(yout), ld_y, act, float(drop_scale), rows, cols, mode,
@@ -512,14 +529,14 @@ def linear_small_bwd(a, w, dz, dw, db):
 
 def transpose_padded(x):
     """(R, C) f32 | bf16 -> (C, R~) with zero padding (R~ = R rounded up to a 16-byte row), K-contiguous for the MFMA GEMM."""
-    _chk(x)
+    _chk_rows(x)
     R, C = x.shape
     if x.dtype == torch.bfloat16:
         ld = (R + 7) // 8 * 8
         out = torch.empty((C, ld), dtype=torch.bfloat16, device=x.device)
         _lib.check(_lib.lib().mla_transpose_bf16(_p(x), x.stride(0), _p(out), ld, R, C, _lib.stream_ptr()))
         return out
-    _chk(x, torch.float32)
+    _chk_rows(x, torch.float32)
     ld = (R + 3) // 4 * 4
     out = torch.zeros((C, ld), dtype=torch.float32, device=x.device) if ld != R else torch.empty((C, ld), dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().mla_transpose_f32(_p(x), x.stride(0), _p(out), ld, R, C, _lib.stream_ptr()))
@@ -568,11 +585,11 @@ def raise_on_bad_labels(hits):
 def cross_entropy(scores, labels, inv_total, want_grad=True):
     """CrossEntropyLoss(mean over the GLOBAL batch) on (B, K) scores: (loss, dscores, hits) with hits = int32 [n_correct,
     n_bad]; n_bad > 0 (and a NaN loss): that many labels were outside [0, K) -- see check_labels."""
-    _chk(scores, torch.float32); _chk(labels, torch.int64)
+    _chk_rows(scores, torch.float32); _chk(labels, torch.int64)
     B, K = scores.shape
     loss = torch.empty(1, dtype=torch.float32, device=scores.device)
     hits = torch.empty(2, dtype=torch.int32, device=scores.device)
-    d = torch.empty_like(scores) if want_grad else None
+    d = torch.empty((B, K), dtype=torch.float32, device=scores.device) if want_grad else None
     _lib.check(_lib.lib().mla_cross_entropy(_p(scores), scores.stride(0), _p(labels), B, K, float(inv_total), _p(loss), _p(d),
                                             K, _p(hits), _lib.stream_ptr()))
     return loss, d, hits

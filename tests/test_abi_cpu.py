@@ -153,6 +153,39 @@ def test_argument_errors_are_reported_before_any_launch(L):
     assert lib.mla_vggish_conv(2, None, None, None, None, 0, L.BF16, None) == 0
     rc = lib.mla_vggish_conv(9, fake, fake, fake, fake, 4, L.BF16, None)
     assert rc in (E_ARG, E_SHAPE) and b"layer" in lib.mla_last_error()
+    # training kernels: pooled ReLU backward needs even H, W in BOTH forms (an odd size would leave the last row / column of dZ
+    # unwritten); un-pooled it does not, and zero images are a no-op
+    expect(E_SHAPE, lib.mla_relu_pool_bwd(fake, fake, fake, 2, 13, 8, 64, 1, None), "even")
+    expect(E_SHAPE, lib.mla_relu_pool_bwd(fake, fake, fake, 2, 12, 7, 64, 1, None), "even")
+    expect(E_SHAPE, lib.mla_relu_pool_bwd_bias(fake, fake, fake, 2, 13, 8, 64, 1, fake, fake, None), "even")
+    expect(E_ARG, lib.mla_relu_pool_bwd(None, fake, fake, 2, 12, 8, 64, 1, None))
+    assert lib.mla_relu_pool_bwd(fake, fake, fake, 0, 13, 7, 64, 0, None) == 0
+    assert lib.mla_relu_pool_bwd(fake, fake, fake, 0, 12, 8, 64, 1, None) == 0
+    # BatchNorm backward, second stage: the channel layout is validated exactly as in the first (mla_bn_bwd_sums)
+    cd = ctypes.c_double
+
+    def bwd_sums(rows, cols, mode, period, act=0, yout=None):
+        return lib.mla_bn_bwd_sums(fake, cols, fake, cols, yout, cols, act, 1.0, rows, cols, mode, period, fake, fake, 1e-5, fake, fake, None)
+
+    def bwd_apply(rows, cols, mode, period, act=0, yout=None, count=1.0):
+        return lib.mla_bn_bwd_apply(fake, cols, fake, cols, yout, cols, act, 1.0, rows, cols, mode, period, fake, fake, fake, 1e-5,
+                                    fake, fake, cd(count), fake, cols, 0, fake, fake, None)
+
+    for rows, cols, mode, period, code in ((20, 8, 0, 0, E_SHAPE),          # period 0: r % period on the device
+                                           (20, 8, 0, -1, E_SHAPE), (20, 8, 0, 65, E_SHAPE),      # more than 64 channels
+                                           (20, 8, 0, 3, E_SHAPE),           # rows not a multiple of the period
+                                           (20, 65, 1, 0, E_SHAPE),          # mode 1: columns are channels
+                                           (20, 8, 2, 10, E_SHAPE), (20, 8, -1, 10, E_SHAPE),     # no such mode
+                                           (0, 8, 0, 10, E_ARG), (-10, 8, 0, 10, E_ARG), (20, 0, 1, 0, E_ARG)):
+        expect(code, bwd_sums(rows, cols, mode, period))
+        expect(code, bwd_apply(rows, cols, mode, period))
+    expect(E_ARG, bwd_sums(20, 8, 0, 10, act=1), "forward output")
+    expect(E_ARG, bwd_apply(20, 8, 0, 10, act=1), "forward output")
+    expect(E_ARG, bwd_apply(20, 8, 0, 10, count=0.0))
+    expect(E_ARG, lib.mla_bn_bwd_apply(fake, 8, fake, 8, None, 8, 0, 1.0, 20, 8, 0, 10, fake, fake, fake, 1e-5, fake, fake, cd(1.0), fake, 8,
+                                       0, fake, None, None), "go together")
+    # an uncompiled wgrad shape is refused by the dispatcher, not launched
+    expect(E_SHAPE, lib.mla_conv_wgrad(fake, fake, 3, 24, 16, 64, 128, fake, 1 << 30, fake, None), "not compiled")
 
 
 def _build_c_example(L, tmp_path):
