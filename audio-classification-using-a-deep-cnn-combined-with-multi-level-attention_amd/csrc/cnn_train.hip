@@ -1,12 +1,15 @@
 // cnn_train.hip -- backward pieces of the VGGish feature stack for the finetune training step
 // (train.py:96-97 set_requires_grad(clf, True), then loss.backward() at train.py:137 reaches the
-// CNN). All f32, NHWC. The forward in training mode runs the convolutions WITHOUT the fused
-// pool (conv.hip, pool = 0) so that the pre-pool activations exist for the pool / ReLU backward.
+// CNN), NHWC: everything that is exact f32 or generic in the element type. What exists only in bf16
+// (the step at speed) is cnn_train_bf16.hip; the rules both share are cnn_train_core.h. The forward
+// in training mode runs the convolutions WITHOUT the fused pool (conv.hip, pool = 0) so that the
+// pre-pool activations exist for the pool / ReLU backward.
 //
-//   maxpool2x2            nn.MaxPool2d(2, 2) forward on a kept activation
-//   relu_pool_bwd         dZ (pre-pool resolution) from the gradient of the pooled (or un-pooled)
+//   maxpool2x2<T>         nn.MaxPool2d(2, 2) forward on a kept activation, f32 or bf16: one 16-byte
+//                         chunk (4 floats / 8 bf16) per lane
+//   relu_pool_bwd         f32 dZ (pre-pool resolution) from the gradient of the pooled (or un-pooled)
 //                         output: routed to the first maximum of each 2x2 window (torch's
-//                         tie rule) and masked by ReLU (output > 0)
+//                         tie rule) and masked by ReLU (output > 0); optionally the bias gradient
 //   conv_wgrad            dW[co][tap][ci] = sum_pixels dZ[p][co] * A[p + tap][ci] as an implicit
 //                         GEMM with K = pixels on v_mfma_f32_16x16x4_f32: NHWC puts 16 consecutive
 //                         channels of one pixel on 16 lanes, which is exactly the f32 MFMA operand
@@ -15,115 +18,53 @@
 //                         patch with halo is staged once and serves all nine taps; split over
 //                         images, deterministic two-stage reduction that also restores the
 //                         state_dict layout (Cout, Cin, 3, 3).
-//   conv1_bwd             Cin = 1 special case: recomputes the four pre-pool outputs of each pooled
-//                         pixel (f32 fma chain; the forward's MFMA sums differ in the last bits, which
-//                         can only flip the routing between two near-equal maxima), routes the gradient
-//                         and reduces dW (64 x 9) and db (64).
-#include "common.h"
-#include "mma_core.h"
+//   conv1_bwd<TD>         Cin = 1 special case on the vector pipe, incoming gradient f32 or bf16: recomputes
+//                         the four pre-pool outputs of each pooled pixel (f32 fma chain; the forward's MFMA
+//                         sums differ in the last bits, which can only flip the routing between two near-equal
+//                         maxima), routes the gradient and reduces dW (64 x 9) and db (64). bf16 runs it only
+//                         when built with -DMLA_CONV1_BWD_MFMA=0 (cnn_train_bf16.hip has the MFMA form).
+#include "cnn_train_core.h"
 
 namespace {
 
-using namespace mma;
+using namespace ct;
 
-__global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ a, float* __restrict__ out, int64_t n_out,
-                                                      int H, int W, int C) {
-    const int c4 = C / 4, WO = W / 2, HO = H / 2;
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ a, T* __restrict__ out, int64_t n_out, int H, int W, int C) {
+    constexpr int V = Elem<T>::kPerChunk;
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_out; i += int64_t(gridDim.x) * 256) {
-        const int c = int(i % c4);
-        int64_t r = i / c4;
-        const int xo = int(r % WO); r /= WO;
-        const int yo = int(r % HO);
-        const int64_t n = r / HO;
-        const f32x4* p = reinterpret_cast<const f32x4*>(a + ((n * H + 2 * yo) * W + 2 * xo) * C) + c;
-        const f32x4 v00 = p[0], v01 = p[c4], v10 = p[int64_t(W) * c4], v11 = p[int64_t(W) * c4 + c4];
-        f32x4 m;
-        m.x = fmaxf(fmaxf(v00.x, v01.x), fmaxf(v10.x, v11.x));
-        m.y = fmaxf(fmaxf(v00.y, v01.y), fmaxf(v10.y, v11.y));
-        m.z = fmaxf(fmaxf(v00.z, v01.z), fmaxf(v10.z, v11.z));
-        m.w = fmaxf(fmaxf(v00.w, v01.w), fmaxf(v10.w, v11.w));
-        reinterpret_cast<f32x4*>(out)[i] = m;
+        const Window win = window_of<V>(i, H, W, C);
+        float v[4][V], m[V];
+        _Pragma("unroll") for (int k = 0; k < 4; ++k) load_chunk(a + win.base + win.off[k], v[k]);
+        _Pragma("unroll") for (int e = 0; e < V; ++e) m[e] = fmaxf(fmaxf(v[0][e], v[1][e]), fmaxf(v[2][e], v[3][e]));
+        store_chunk(out + i * V, m);                             // bf16: the max of bf16 values is a bf16 value, the repack is exact
     }
 }
 
-// pooled: one thread per (n, yo, xo, c): dZ[window] = 0 except the first position equal to the max
-// (scan order (0,0),(0,1),(1,0),(1,1)), which receives dP if the max is > 0 (ReLU').
-// un-pooled: dZ = dA * (A > 0).
-__global__ __launch_bounds__(256) void relu_pool_bwd_kernel(const float* __restrict__ a, const float* __restrict__ d_out,
-                                                            float* __restrict__ dz, int64_t total, int H, int W, int C, int pool) {
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += int64_t(gridDim.x) * 256) {
-        if (!pool) {
-            dz[i] = a[i] > 0.f ? d_out[i] : 0.f;
-            continue;
-        }
-        const int WO = W / 2, HO = H / 2;
-        const int c = int(i % C);
-        int64_t r = i / C;
-        const int xo = int(r % WO); r /= WO;
-        const int yo = int(r % HO);
-        const int64_t n = r / HO;
-        const int64_t base = ((n * H + 2 * yo) * W + 2 * xo) * C + c;
-        const int64_t off[4] = {0, C, int64_t(W) * C, int64_t(W) * C + C};
-        float best = a[base];
-        int arg = 0;
-        _Pragma("unroll") for (int k = 1; k < 4; ++k) {
-            const float v = a[base + off[k]];
-            if (v > best) { best = v; arg = k; }
-        }
-        const float g = best > 0.f ? d_out[i] : 0.f;
-        _Pragma("unroll") for (int k = 0; k < 4; ++k) dz[base + off[k]] = (k == arg) ? g : 0.f;
-    }
-}
-
-// Same, and the bias gradient db[c] = sum over pixels of dZ[., c] on the way (it used to be a second pass over dZ, the largest
+// pooled: one thread per (n, yo, xo, c): dZ[window] = 0 except the first position equal to the max, which receives dP if the
+// max is > 0 (cnn_train_core.h route). un-pooled: dZ = dA * (A > 0).
+// SLOTS: also the bias gradient db[c] = sum over pixels of dZ[., c] on the way (it used to be a second pass over dZ, the largest
 // tensor of the backward pass). The grid-stride step is a multiple of C, so a thread's channel never changes: each thread sums
-// its elements in double precision into slot blockIdx * 256 + t; slot s belongs to channel s % C.
-__global__ __launch_bounds__(256) void relu_pool_bwd_bias_kernel(const float* __restrict__ a, const float* __restrict__ d_out,
-                                                                 float* __restrict__ dz, int64_t total, int H, int W, int C, int pool,
-                                                                 double* __restrict__ slots) {
+// its elements in double precision into slot blockIdx * 256 + t, and bias_slots_finish_kernel<1> adds the slots of a channel.
+template <bool SLOTS>
+__global__ __launch_bounds__(256) void relu_pool_bwd_kernel(const float* __restrict__ a, const float* __restrict__ d_out,
+                                                            float* __restrict__ dz, int64_t total, int H, int W, int C, int pool,
+                                                            double* __restrict__ slots) {
     double acc = 0.0;
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += int64_t(gridDim.x) * 256) {
+        float g;
         if (!pool) {
-            const float g = a[i] > 0.f ? d_out[i] : 0.f;
+            g = a[i] > 0.f ? d_out[i] : 0.f;
             dz[i] = g;
-            acc += g;
-            continue;
+        } else {
+            const Window win = window_of<1>(i, H, W, C);
+            const float* p = a + win.base;
+            const int arg = route(p[0], p[win.off[1]], p[win.off[2]], p[win.off[3]], d_out[i], g);
+            _Pragma("unroll") for (int k = 0; k < 4; ++k) dz[win.base + win.off[k]] = (k == arg) ? g : 0.f;
         }
-        const int WO = W / 2, HO = H / 2;
-        const int c = int(i % C);
-        int64_t r = i / C;
-        const int xo = int(r % WO); r /= WO;
-        const int yo = int(r % HO);
-        const int64_t n = r / HO;
-        const int64_t base = ((n * H + 2 * yo) * W + 2 * xo) * C + c;
-        const int64_t off[4] = {0, C, int64_t(W) * C, int64_t(W) * C + C};
-        float best = a[base];
-        int arg = 0;
-        _Pragma("unroll") for (int k = 1; k < 4; ++k) {
-            const float v = a[base + off[k]];
-            if (v > best) { best = v; arg = k; }
-        }
-        const float g = best > 0.f ? d_out[i] : 0.f;
-        _Pragma("unroll") for (int k = 0; k < 4; ++k) dz[base + off[k]] = (k == arg) ? g : 0.f;
-        acc += g;
+        if constexpr (SLOTS) acc += g;
     }
-    slots[int64_t(blockIdx.x) * 256 + threadIdx.x] = acc;
-}
-
-// db[c] = sum of the slots of channel c (slots c, c + C, ...), one workgroup per channel, fixed order
-__global__ __launch_bounds__(256) void bias_slots_finish_kernel(const double* __restrict__ slots, int64_t n_slots, int C,
-                                                                float* __restrict__ db) {
-    __shared__ double part[256];
-    const int c = blockIdx.x;
-    double s = 0.0;
-    for (int64_t k = int64_t(c) + int64_t(threadIdx.x) * C; k < n_slots; k += int64_t(256) * C) s += slots[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (int(threadIdx.x) < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) db[c] = float(part[0]);
+    if constexpr (SLOTS) slots[int64_t(blockIdx.x) * 256 + threadIdx.x] = acc;
 }
 
 // ------------------------------------------------------------------------------------ wgrad ---
@@ -207,21 +148,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_kernel(const float* __restrict__
             }
 }
 
-// dW[co][ci][tap] (state_dict layout) = sum over splits of partial[split][co][tap][ci]
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, int splits, int cout, int cin,
-                                                           float* __restrict__ dw) {
-    const int64_t total = int64_t(cout) * cin * 9;
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += int64_t(gridDim.x) * 256) {
-        const int tap = int(i % 9);
-        const int ci = int((i / 9) % cin);
-        const int co = int(i / (int64_t(9) * cin));
-        const size_t src = (size_t(co) * 9 + tap) * cin + ci;
-        float s = 0.f;
-        for (int k = 0; k < splits; ++k) s += partial[size_t(k) * total + src];
-        dw[i] = s;
-    }
-}
-
 template <int CIN, int COUT, int H, int W>
 int launch_wgrad(const float* dz, const float* ain, int64_t n, float* partial, int64_t partial_floats, float* dw, hipStream_t s) {
     using C = WCfg<CIN, COUT, H, W>;
@@ -242,9 +168,10 @@ int launch_wgrad(const float* dz, const float* ain, int64_t n, float* partial, i
 // ----------------------------------------------------------------------------- conv1 backward ---
 // block (x = pixel block, y = channel group of 8): each lane owns pooled pixels, recomputes the four
 // pre-pool outputs per channel, routes d_pooled to the first maximum and accumulates
-// dW (8 x 9) and db (8) in registers; block tree-reduction -> partial[blockIdx.x][cg][80].
+// dW (8 x 9) and db (8) in registers; block tree-reduction -> partial[blockIdx.x][cg][80]. TD: element type of d_pooled.
+template <typename TD>
 __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                        const float* __restrict__ bias, const float* __restrict__ d_pooled,
+                                                        const float* __restrict__ bias, const TD* __restrict__ d_pooled,
                                                         int64_t n_pix, float* __restrict__ partial) {
     __shared__ float red[4][80];
     const int cg = blockIdx.y;
@@ -262,6 +189,8 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
                 const int iy = 2 * py - 1 + a, ix = 2 * px - 1 + b;
                 patch[a][b] = (iy >= 0 && iy < 96 && ix >= 0 && ix < 64) ? x[(n * 96 + iy) * 64 + ix] : 0.f;
             }
+        float dv[8];                                             // bf16: the group's 8 gradients are one 16-byte load; f32: read one by one
+        if constexpr (sizeof(TD) == 2) load8(d_pooled + idx * 64 + cg * 8, dv);
         _Pragma("unroll") for (int c = 0; c < 8; ++c) {
             const int ch = cg * 8 + c;
             float o[4] = {0.f, 0.f, 0.f, 0.f};
@@ -273,11 +202,9 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
                     o[2] = fmaf(patch[ky + 1][kx], wv, o[2]);
                     o[3] = fmaf(patch[ky + 1][kx + 1], wv, o[3]);
                 }
-            float best = o[0];
-            int arg = 0;
-            _Pragma("unroll") for (int k = 1; k < 4; ++k)
-                if (o[k] > best) { best = o[k]; arg = k; }
-            const float g = (best + bias[ch] > 0.f) ? d_pooled[idx * 64 + ch] : 0.f;
+            float best;
+            const int arg = first_max(o[0], o[1], o[2], o[3], best);
+            const float g = (best + bias[ch] > 0.f) ? (sizeof(TD) == 2 ? dv[c] : load_elem(d_pooled + idx * 64 + ch)) : 0.f;       // the bias is added after the pool
             gb[c] += g;
             const int dy = arg >> 1, dx = arg & 1;
             _Pragma("unroll") for (int ky = 0; ky < 3; ++ky)
@@ -306,33 +233,61 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
 // one workgroup per (cg, c, k): the partials of all blocks are summed by 256 lanes and a fixed tree (it used to be one serial
 // loop over the 1 024 blocks per output: 0.42 ms of the finetune step)
 __global__ __launch_bounds__(256) void conv1_bwd_finish_kernel(const float* __restrict__ partial, int blocks, float* __restrict__ dw, float* __restrict__ db) {
-    __shared__ double part[256];
     const int i = blockIdx.x;                                      // 0 .. 639: (cg, c, k)
     const int cg = i / 80, rem = i % 80, c = rem / 10, k = rem % 10;
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += 256) s += partial[(size_t(b) * 8 + cg) * 80 + rem];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (int(threadIdx.x) < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
+    s = block_sum256(s);
     if (threadIdx.x == 0) {
-        if (k < 9) dw[(cg * 8 + c) * 9 + k] = float(part[0]);
-        else db[cg * 8 + c] = float(part[0]);
+        if (k < 9) dw[(cg * 8 + c) * 9 + k] = float(s);
+        else db[cg * 8 + c] = float(s);
     }
+}
+
+// workspace: 1024 * 8 * 80 floats
+template <typename TD>
+int launch_conv1_bwd(const float* x, const float* w, const float* bias, const TD* d_pooled, int64_t n, float* workspace, float* dw,
+                     float* db, hipStream_t s) {
+    const int64_t n_pix = n * 48 * 32;
+    const int blocks = int((n_pix + 255) / 256 < 1024 ? (n_pix + 255) / 256 : 1024);
+    hipLaunchKernelGGL(conv1_bwd_kernel<TD>, dim3(blocks, 8), dim3(256), 0, s, x, w, bias, d_pooled, n_pix, workspace);
+    MLA_LAUNCH_OK("conv1_bwd");
+    hipLaunchKernelGGL(conv1_bwd_finish_kernel, dim3(640), dim3(256), 0, s, workspace, blocks, dw, db);
+    MLA_LAUNCH_OK("conv1_bwd_finish");
+    return MLA_OK;
+}
+
+unsigned grid_for(int64_t total) { return unsigned((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384); }
+
+template <typename T>
+int maxpool(const void* a, void* out, int64_t n, int H, int W, int C, mla_stream_t stream) {
+    constexpr int V = Elem<T>::kPerChunk;
+    MLA_REQUIRE(a && out && n >= 0 && H % 2 == 0 && W % 2 == 0 && C % V == 0, MLA_E_ARG, "bad maxpool arguments");
+    if constexpr (sizeof(T) == 2)                                  // (the f32 entry never asked for it)
+        MLA_REQUIRE(mla::aligned(a, 16) && mla::aligned(out, 16), MLA_E_ARG, "maxpool buffers must be 16-byte aligned");
+    const int64_t total = n * (H / 2) * (W / 2) * (C / V);
+    if (total == 0) return MLA_OK;
+    hipLaunchKernelGGL(maxpool_kernel<T>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const T*>(a),
+                       static_cast<T*>(out), total, H, W, C);
+    MLA_LAUNCH_OK("maxpool");
+    return MLA_OK;
 }
 
 }  // namespace
 
+#if !MLA_CONV1_BWD_MFMA
+int ct::conv1_bwd_vector(const float* x, const float* w, const float* bias, const bf16_t* d_pooled, int64_t n, float* workspace,
+                         float* dw, float* db, hipStream_t s) {
+    return launch_conv1_bwd(x, w, bias, d_pooled, n, workspace, dw, db, s);
+}
+#endif
+
 extern "C" int mla_maxpool2x2(const float* a, float* out, int64_t n, int H, int W, int C, mla_stream_t stream) {
-    MLA_REQUIRE(a && out && n >= 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0, MLA_E_ARG, "bad maxpool arguments");
-    const int64_t total = n * (H / 2) * (W / 2) * (C / 4);
-    if (total == 0) return MLA_OK;
-    const unsigned grid = unsigned((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipLaunchKernelGGL(maxpool_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a, out, total, H, W, C);
-    MLA_LAUNCH_OK("maxpool");
-    return MLA_OK;
+    return maxpool<float>(a, out, n, H, W, C, stream);
+}
+
+extern "C" int mla_maxpool2x2_bf16(const void* a, void* out, int64_t n, int H, int W, int C, mla_stream_t stream) {
+    return maxpool<bf16_t>(a, out, n, H, W, C, stream);
 }
 
 extern "C" int mla_relu_pool_bwd(const float* a, const float* d_out, float* dz, int64_t n, int H, int W, int C, int pool,
@@ -341,13 +296,13 @@ extern "C" int mla_relu_pool_bwd(const float* a, const float* d_out, float* dz, 
     MLA_REQUIRE(!pool || (H % 2 == 0 && W % 2 == 0), MLA_E_SHAPE, "pooling needs even H, W");
     const int64_t total = pool ? n * (H / 2) * (W / 2) * C : n * H * W * C;
     if (total == 0) return MLA_OK;
-    const unsigned grid = unsigned((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipLaunchKernelGGL(relu_pool_bwd_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a, d_out, dz, total, H, W, C, pool);
+    hipLaunchKernelGGL(relu_pool_bwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), a, d_out, dz, total,
+                       H, W, C, pool, static_cast<double*>(nullptr));
     MLA_LAUNCH_OK("relu_pool_bwd");
     return MLA_OK;
 }
 
-constexpr int kBiasGrid = 4096;            // workgroups of relu_pool_bwd_bias_kernel (a multiple of C / 256 for C <= 1024)
+constexpr int kBiasGrid = 4096;            // workgroups of relu_pool_bwd_kernel<true> (a multiple of C / 256 for C <= 1024)
 
 extern "C" int64_t mla_relu_pool_bwd_bias_workspace_bytes(void) { return int64_t(kBiasGrid) * 256 * 8; }
 
@@ -358,10 +313,10 @@ extern "C" int mla_relu_pool_bwd_bias(const float* a, const float* d_out, float*
     MLA_REQUIRE(!pool || (H % 2 == 0 && W % 2 == 0), MLA_E_SHAPE, "pooling needs even H, W");
     const int64_t total = pool ? n * (H / 2) * (W / 2) * C : n * H * W * C;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(relu_pool_bwd_bias_kernel, dim3(kBiasGrid), dim3(256), 0, s, a, d_out, dz, total, H, W, C, pool,
+    hipLaunchKernelGGL(relu_pool_bwd_kernel<true>, dim3(kBiasGrid), dim3(256), 0, s, a, d_out, dz, total, H, W, C, pool,
                        static_cast<double*>(workspace));
     MLA_LAUNCH_OK("relu_pool_bwd_bias");
-    hipLaunchKernelGGL(bias_slots_finish_kernel, dim3(unsigned(C)), dim3(256), 0, s, static_cast<const double*>(workspace),
+    hipLaunchKernelGGL(bias_slots_finish_kernel<1>, dim3(unsigned(C)), dim3(256), 0, s, static_cast<const double*>(workspace),
                        int64_t(kBiasGrid) * 256, C, db);
     MLA_LAUNCH_OK("bias_slots_finish");
     return MLA_OK;
@@ -375,25 +330,14 @@ extern "C" int mla_conv_wgrad(const float* dz, const float* a_in, int64_t n, int
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define MLA_WGRAD_CASE(CI, CO, HH, WW) \
     if (cin == CI && cout == CO && H == HH && W == WW) return launch_wgrad<CI, CO, HH, WW>(dz, a_in, n, workspace, workspace_floats, dw_oihw, s);
-    MLA_WGRAD_CASE(64, 128, 48, 32)
-    MLA_WGRAD_CASE(128, 256, 24, 16)
-    MLA_WGRAD_CASE(256, 256, 24, 16)
-    MLA_WGRAD_CASE(256, 512, 12, 8)
-    MLA_WGRAD_CASE(512, 512, 12, 8)
+    MLA_WGRAD_SHAPES(MLA_WGRAD_CASE)
 #undef MLA_WGRAD_CASE
     return mla::fail(MLA_E_SHAPE, "wgrad %dx%d %d->%d is not compiled", H, W, cin, cout);
 }
 
-// x (n, 96, 64) f32, d_pooled (n, 48, 32, 64): dw (64, 1, 3, 3), db (64). workspace: 1024 * 8 * 80 floats.
+// x (n, 96, 64) f32, d_pooled (n, 48, 32, 64): dw (64, 1, 3, 3), db (64)
 extern "C" int mla_conv1_bwd(const float* x, const float* w, const float* bias, const float* d_pooled, int64_t n, float* workspace,
                              float* dw, float* db, mla_stream_t stream) {
     MLA_REQUIRE(x && w && bias && d_pooled && workspace && dw && db && n > 0, MLA_E_ARG, "bad conv1_bwd arguments");
-    const int64_t n_pix = n * 48 * 32;
-    const int blocks = int((n_pix + 255) / 256 < 1024 ? (n_pix + 255) / 256 : 1024);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(conv1_bwd_kernel, dim3(blocks, 8), dim3(256), 0, s, x, w, bias, d_pooled, n_pix, workspace);
-    MLA_LAUNCH_OK("conv1_bwd");
-    hipLaunchKernelGGL(conv1_bwd_finish_kernel, dim3(640), dim3(256), 0, s, workspace, blocks, dw, db);
-    MLA_LAUNCH_OK("conv1_bwd_finish");
-    return MLA_OK;
+    return launch_conv1_bwd(x, w, bias, d_pooled, n, workspace, dw, db, static_cast<hipStream_t>(stream));
 }

@@ -1,11 +1,15 @@
-// cnn_train_bf16.hip -- the finetune backward of the VGGish feature stack in bf16 (train.py:96-97 set_requires_grad(clf, True),
-// then loss.backward() at train.py:137 reaches the CNN): bf16 activations and gradients, f32 accumulation, f32 weight
-// gradients into the flat gradient buffer, f32 master weights (the bf16 weight copies are re-derived after every Adam step).
-// The f32 forms (exact-MFMA parity mode) live in cnn_train.hip; this file is what the step runs in at speed.
+// cnn_train_bf16.hip -- what the finetune backward of the VGGish feature stack has in bf16 only (train.py:96-97
+// set_requires_grad(clf, True), then loss.backward() at train.py:137 reaches the CNN): bf16 activations and gradients, f32
+// accumulation, f32 weight gradients into the flat gradient buffer, f32 master weights (the bf16 weight copies are re-derived
+// after every Adam step). This file is what the step runs in at speed. The exact-f32 forms and everything generic in the
+// element type (maxpool2x2, the vector-pipe conv1 backward) live in cnn_train.hip, the rules both share (pool routing, bias
+// slots, block tree, wgrad reduction) in cnn_train_core.h, the Linear-backward helpers in train_kernels.hip and the dgrad
+// weight repack in conv.hip.
 //
-//   maxpool2x2_bf16       nn.MaxPool2d(2, 2) on a kept pre-pool activation, 8 channels (16 B) per lane
 //   relu_pool_bwd_bf16    dZ from the gradient of relu(.) / maxpool(relu(.)): first-maximum routing (torch's tie rule) and
-//                         ReLU mask; the layer's bias gradient (column sums of dZ) is accumulated on the way
+//                         ReLU mask, 8 channels (16 B) per lane; the layer's bias gradient (column sums of dZ) is
+//                         accumulated on the way
+//   pool_bwd_codes_bf16   the same dZ from the window codes the training forward wrote instead of the pre-pool activation
 //   wgrad_bf16            dW[co][tap][ci] = sum_pixels dZ[p][co] * A[p + tap][ci] as an implicit GEMM with K = pixels on
 //                         v_mfma_f32_16x16x32_bf16. NHWC keeps a pixel's channels contiguous while the MFMA wants 8
 //                         consecutive k (pixels) of ONE channel per lane: the staged [pixel][channel] tiles are read with
@@ -15,46 +19,26 @@
 //                         32-lane half reads 8 CONSECUTIVE pixel rows: with a 160-byte row pitch these are 8 distinct
 //                         32-byte bank slots -- conflict-free for every tap shift.
 //   conv1_bwd (bf16 dY)   recompute and weight gradient of the Cin = 1 layer as two GEMMs on the matrix cores (conv1_bwd_mfma_kernel)
-//   transpose_bf16, col_sum_bf16   helpers of the Linear backward (K-contiguous operands for the MFMA GEMM; bias gradients)
 //
 // Roofline: wgrad is MFMA-bound (2 * pixels * 9 Cin Cout flop per image, the same as the forward layer); the elementwise
 // kernels are HBM-bound (they read and write each activation-sized tensor once).
-#include "common.h"
-#include "mma_core.h"
+#include "cnn_train_core.h"
 
 namespace {
 
-using namespace mma;
+using namespace ct;
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-__global__ __launch_bounds__(256) void maxpool_bf16_kernel(const bf16_t* __restrict__ a, bf16_t* __restrict__ out, int64_t n_out,
-                                                           int H, int W, int C) {
-    const int c8 = C / 8, WO = W / 2, HO = H / 2;
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_out; i += int64_t(gridDim.x) * 256) {
-        const int c = int(i % c8);
-        int64_t r = i / c8;
-        const int xo = int(r % WO); r /= WO;
-        const int yo = int(r % HO);
-        const int64_t n = r / HO;
-        const bf16_t* p = a + ((n * H + 2 * yo) * W + 2 * xo) * C + c * 8;
-        float v00[8], v01[8], v10[8], v11[8], m[8];
-        load8(p, v00); load8(p + C, v01); load8(p + int64_t(W) * C, v10); load8(p + int64_t(W) * C + C, v11);
-        _Pragma("unroll") for (int k = 0; k < 8; ++k) m[k] = fmaxf(fmaxf(v00[k], v01[k]), fmaxf(v10[k], v11[k]));
-        store8(out + i * 8, m);                              // max of bf16 values is a bf16 value: the repack is exact
-    }
-}
-
 // One lane per (n, yo, xo, 8 channels) [pool] or per 8 consecutive elements [no pool]; dZ in bf16. The grid-stride step is
 // a multiple of C / 8, so a lane's 8 channels never change: their dZ sums go to slots[(block * 256 + t) * 8 + k] in double
-// precision and bias_slots_finish8 adds the slots of a channel in fixed order (deterministic).
+// precision and bias_slots_finish_kernel<8> adds the slots of a channel in fixed order (deterministic).
 template <typename TA, typename TD>
 __global__ __launch_bounds__(256) void relu_pool_bwd_bf16_kernel(const TA* __restrict__ a, const TD* __restrict__ d_out,
                                                                  bf16_t* __restrict__ dz, int64_t total8, int H, int W, int C, int pool,
                                                                  double* __restrict__ slots) {
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int c8 = C / 8;
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total8; i += int64_t(gridDim.x) * 256) {
         float g[8], d[8];
         load8(d_out + i * 8, d);
@@ -64,28 +48,15 @@ __global__ __launch_bounds__(256) void relu_pool_bwd_bf16_kernel(const TA* __res
             _Pragma("unroll") for (int k = 0; k < 8; ++k) g[k] = av[k] > 0.f ? d[k] : 0.f;
             store8(dz + i * 8, g);
         } else {
-            const int WO = W / 2, HO = H / 2;
-            const int c = int(i % c8);
-            int64_t r = i / c8;
-            const int xo = int(r % WO); r /= WO;
-            const int yo = int(r % HO);
-            const int64_t n = r / HO;
-            const int64_t base = ((n * H + 2 * yo) * W + 2 * xo) * C + c * 8;
-            const int64_t off[4] = {0, C, int64_t(W) * C, int64_t(W) * C + C};
+            const Window win = window_of<8>(i, H, W, C);
             float v[4][8];
-            _Pragma("unroll") for (int w = 0; w < 4; ++w) load8(a + base + off[w], v[w]);
+            _Pragma("unroll") for (int w = 0; w < 4; ++w) load8(a + win.base + win.off[w], v[w]);
             int arg[8];
-            _Pragma("unroll") for (int k = 0; k < 8; ++k) {
-                float best = v[0][k];
-                arg[k] = 0;
-                _Pragma("unroll") for (int w = 1; w < 4; ++w)
-                    if (v[w][k] > best) { best = v[w][k]; arg[k] = w; }
-                g[k] = best > 0.f ? d[k] : 0.f;
-            }
+            _Pragma("unroll") for (int k = 0; k < 8; ++k) arg[k] = route(v[0][k], v[1][k], v[2][k], v[3][k], d[k], g[k]);
             _Pragma("unroll") for (int w = 0; w < 4; ++w) {
                 float o[8];
                 _Pragma("unroll") for (int k = 0; k < 8; ++k) o[k] = arg[k] == w ? g[k] : 0.f;
-                store8(dz + base + off[w], o);
+                store8(dz + win.base + win.off[w], o);
             }
         }
         _Pragma("unroll") for (int k = 0; k < 8; ++k) acc[k] += double(g[k]);
@@ -96,22 +67,6 @@ __global__ __launch_bounds__(256) void relu_pool_bwd_bf16_kernel(const TA* __res
     }
 }
 
-// db[c]: lane t of block b holds channels 8 ((b * 256 + t) % (C / 8)) + k
-__global__ __launch_bounds__(256) void bias_slots_finish8_kernel(const double* __restrict__ slots, int64_t n_lanes, int C,
-                                                                 float* __restrict__ db) {
-    __shared__ double part[256];
-    const int c = blockIdx.x, c8 = C / 8, grp = c / 8, k = c % 8;
-    double s = 0.0;
-    for (int64_t l = int64_t(grp) + int64_t(threadIdx.x) * c8; l < n_lanes; l += int64_t(256) * c8) s += slots[l * 8 + k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (int(threadIdx.x) < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) db[c] = float(part[0]);
-}
-
 // Pool / ReLU backward from the window CODES the training forward wrote (mla_conv3x3_train_codes: one byte per pooled element, the
 // position of the first maximum or 4 where the ReLU is off) instead of the pre-pool activation: 1 + 2 bytes read per pooled element
 // instead of 8 + 2, same dZ. One lane per (n, yo, xo, 8 channels); bias slots as relu_pool_bwd_bf16_kernel.
@@ -119,18 +74,11 @@ __global__ __launch_bounds__(256) void pool_bwd_codes_bf16_kernel(const uint8_t*
                                                                   bf16_t* __restrict__ dz, int64_t total8, int H, int W, int C,
                                                                   double* __restrict__ slots) {
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int c8 = C / 8, WO = W / 2, HO = H / 2;
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total8; i += int64_t(gridDim.x) * 256) {
         float d[8], g[8];
         load8(d_out + i * 8, d);
         const u32x2 cw = *reinterpret_cast<const u32x2*>(codes + i * 8);
-        const int c = int(i % c8);
-        int64_t r = i / c8;
-        const int xo = int(r % WO); r /= WO;
-        const int yo = int(r % HO);
-        const int64_t n = r / HO;
-        const int64_t base = ((n * H + 2 * yo) * W + 2 * xo) * C + c * 8;
-        const int64_t off[4] = {0, C, int64_t(W) * C, int64_t(W) * C + C};
+        const Window win = window_of<8>(i, H, W, C);
         uint32_t code[8];
         _Pragma("unroll") for (int k = 0; k < 8; ++k) {
             code[k] = (cw[k >> 2] >> (8 * (k & 3))) & 0xffu;
@@ -140,7 +88,7 @@ __global__ __launch_bounds__(256) void pool_bwd_codes_bf16_kernel(const uint8_t*
         _Pragma("unroll") for (int w = 0; w < 4; ++w) {
             float o[8];
             _Pragma("unroll") for (int k = 0; k < 8; ++k) o[k] = code[k] == uint32_t(w) ? g[k] : 0.f;
-            store8(dz + base + off[w], o);
+            store8(dz + win.base + win.off[w], o);
         }
     }
     if (slots) {
@@ -358,21 +306,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_bf16_kernel(const bf16_t* __rest
             }
 }
 
-// dW[co][ci][tap] (state_dict layout) = sum over splits of partial[split][co][tap][ci]
-__global__ __launch_bounds__(256) void wgrad_reduce_bf16_kernel(const float* __restrict__ partial, int splits, int cout, int cin,
-                                                                float* __restrict__ dw) {
-    const int64_t total = int64_t(cout) * cin * 9;
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += int64_t(gridDim.x) * 256) {
-        const int tap = int(i % 9);
-        const int ci = int((i / 9) % cin);
-        const int co = int(i / (int64_t(9) * cin));
-        const size_t src = (size_t(co) * 9 + tap) * cin + ci;
-        float s = 0.f;
-        for (int k = 0; k < splits; ++k) s += partial[size_t(k) * total + src];
-        dw[i] = s;
-    }
-}
-
 template <int CIN, int COUT, int H, int W>
 int launch_wgrad_bf16(const bf16_t* dz, const bf16_t* ain, int64_t n, float* partial, int64_t partial_floats, float* dw, hipStream_t s) {
     using C = WBCfg<CIN, COUT, H, W>;
@@ -387,91 +320,9 @@ int launch_wgrad_bf16(const bf16_t* dz, const bf16_t* ain, int64_t n, float* par
     MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
     hipLaunchKernelGGL(kern, dim3(splits, tiles), dim3(512), C::LDS_BYTES, s, dz, ain, partial, int(n));
     MLA_LAUNCH_OK("wgrad_bf16_kernel");
-    hipLaunchKernelGGL(wgrad_reduce_bf16_kernel, dim3(1024), dim3(256), 0, s, partial, splits, COUT, CIN, dw);
-    MLA_LAUNCH_OK("wgrad_reduce_bf16_kernel");
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(1024), dim3(256), 0, s, partial, splits, COUT, CIN, dw);
+    MLA_LAUNCH_OK("wgrad_reduce_kernel");
     return MLA_OK;
-}
-
-// ----------------------------------------------------------------------------- conv1 backward ---
-// as conv1_bwd_kernel of cnn_train.hip, the incoming gradient in bf16
-__global__ __launch_bounds__(256) void conv1_bwd_bf16_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, const bf16_t* __restrict__ d_pooled,
-                                                             int64_t n_pix, float* __restrict__ partial) {
-    __shared__ float red[4][80];
-    const int cg = blockIdx.y;
-    float gw[8][9], gb[8];
-    _Pragma("unroll") for (int c = 0; c < 8; ++c) {
-        gb[c] = 0.f;
-        _Pragma("unroll") for (int k = 0; k < 9; ++k) gw[c][k] = 0.f;
-    }
-    for (int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x; idx < n_pix; idx += int64_t(gridDim.x) * 256) {
-        const int px = int(idx & 31), py = int((idx >> 5) % 48);
-        const int64_t n = idx / (48 * 32);
-        float patch[4][4];
-        _Pragma("unroll") for (int a = 0; a < 4; ++a)
-            _Pragma("unroll") for (int b = 0; b < 4; ++b) {
-                const int iy = 2 * py - 1 + a, ix = 2 * px - 1 + b;
-                patch[a][b] = (iy >= 0 && iy < 96 && ix >= 0 && ix < 64) ? x[(n * 96 + iy) * 64 + ix] : 0.f;
-            }
-        float dv[8];
-        load8(d_pooled + idx * 64 + cg * 8, dv);
-        _Pragma("unroll") for (int c = 0; c < 8; ++c) {
-            const int ch = cg * 8 + c;
-            float o[4] = {0.f, 0.f, 0.f, 0.f};
-            _Pragma("unroll") for (int ky = 0; ky < 3; ++ky)
-                _Pragma("unroll") for (int kx = 0; kx < 3; ++kx) {
-                    const float wv = w[ch * 9 + ky * 3 + kx];
-                    o[0] = fmaf(patch[ky][kx], wv, o[0]);
-                    o[1] = fmaf(patch[ky][kx + 1], wv, o[1]);
-                    o[2] = fmaf(patch[ky + 1][kx], wv, o[2]);
-                    o[3] = fmaf(patch[ky + 1][kx + 1], wv, o[3]);
-                }
-            float best = o[0];
-            int arg = 0;
-            _Pragma("unroll") for (int k = 1; k < 4; ++k)
-                if (o[k] > best) { best = o[k]; arg = k; }
-            const float gg = (best + bias[ch] > 0.f) ? dv[c] : 0.f;
-            gb[c] += gg;
-            const int dy = arg >> 1, dx = arg & 1;
-            _Pragma("unroll") for (int ky = 0; ky < 3; ++ky)
-                _Pragma("unroll") for (int kx = 0; kx < 3; ++kx) {
-                    const float v = dy ? (dx ? patch[ky + 1][kx + 1] : patch[ky + 1][kx]) : (dx ? patch[ky][kx + 1] : patch[ky][kx]);
-                    gw[c][ky * 3 + kx] = fmaf(gg, v, gw[c][ky * 3 + kx]);
-                }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    _Pragma("unroll") for (int c = 0; c < 8; ++c) {
-        _Pragma("unroll") for (int k = 0; k < 10; ++k) {
-            float v = k < 9 ? gw[c][k] : gb[c];
-            _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-            if (lane == 0) red[wave][c * 10 + k] = v;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 80)
-        partial[(size_t(blockIdx.x) * 8 + cg) * 80 + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// one workgroup per (cg, c, k): the partials of all blocks are summed by 256 lanes and a fixed tree (it used to be one serial
-// loop over the 1 024 blocks per output: 0.42 ms of the finetune step)
-__global__ __launch_bounds__(256) void conv1_bwd_finish_bf16_kernel(const float* __restrict__ partial, int blocks, float* __restrict__ dw, float* __restrict__ db) {
-    __shared__ double part[256];
-    const int i = blockIdx.x;                                      // 0 .. 639: (cg, c, k)
-    const int cg = i / 80, rem = i % 80, c = rem / 10, k = rem % 10;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += 256) s += partial[(size_t(b) * 8 + cg) * 80 + rem];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (int(threadIdx.x) < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (k < 9) dw[(cg * 8 + c) * 9 + k] = float(part[0]);
-        else db[cg * 8 + c] = float(part[0]);
-    }
 }
 
 // ---- conv1 backward on the matrix cores (round 2) ------------------------------------------------------------------------------
@@ -487,9 +338,6 @@ __global__ __launch_bounds__(256) void conv1_bwd_finish_bf16_kernel(const float*
 // 16+4q+3} for lane group q -- K is a summation index, any order serves as long as the B operand (patch values) uses the same one.
 // No transpose, no per-lane 72-register accumulator file, 48 MFMAs per 32 pixels x 64 channels instead of ~82 vector instructions per
 // (pixel, channel). Deterministic: static row shares, waves of a workgroup added in order, workgroups summed in a fixed tree.
-#ifndef MLA_CONV1_BWD_MFMA
-#define MLA_CONV1_BWD_MFMA 1
-#endif
 constexpr int kC1Part = 4 * 64 * 16 + 64;                   // floats per workgroup partial: dW'[pos][c][k], db[c]
 constexpr int kC1MaxWg = 768;                               // persistent workgroups (3 per CU: 43 KB of LDS each)
 
@@ -629,7 +477,6 @@ __global__ __launch_bounds__(256, 2) void conv1_bwd_mfma_kernel(const float* __r
 // dW[c][ky][kx] = sum over workgroups and positions of dW'[pos][c][4 (dy + ky) + dx + kx]; db[c]: one workgroup per output
 __global__ __launch_bounds__(256) void conv1_bwd_mfma_finish_kernel(const float* __restrict__ partial, int blocks, float* __restrict__ dw,
                                                                     float* __restrict__ db) {
-    __shared__ double part[256];
     const int i = blockIdx.x;                                      // 0 .. 639: channel * 10 + (tap | bias)
     const int c = i / 10, k = i % 10;
     double s = 0.0;
@@ -642,85 +489,22 @@ __global__ __launch_bounds__(256) void conv1_bwd_mfma_finish_kernel(const float*
             _Pragma("unroll") for (int pos = 0; pos < 4; ++pos) s += p[(pos * 64 + c) * 16 + 4 * ((pos >> 1) + ky) + (pos & 1) + kx];
         }
     }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int wv = 128; wv > 0; wv >>= 1) {
-        if (int(threadIdx.x) < wv) part[threadIdx.x] += part[threadIdx.x + wv];
-        __syncthreads();
-    }
+    s = block_sum256(s);
     if (threadIdx.x == 0) {
-        if (k < 9) dw[c * 9 + k] = float(part[0]);
-        else db[c] = float(part[0]);
+        if (k < 9) dw[c * 9 + k] = float(s);
+        else db[c] = float(s);
     }
 }
 
-// ------------------------------------------------------------------- Linear-backward helpers ---
-// out[c][r] = in[r][c] for 2-byte elements; 64 x 64 tiles through LDS
-__global__ __launch_bounds__(256) void transpose_bf16_kernel(const uint16_t* __restrict__ in, int64_t ld_in, uint16_t* __restrict__ out,
-                                                             int64_t ld_out, int64_t rows, int64_t cols) {
-    __shared__ uint16_t tile[64][66];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;          // 64 x 4
-    const int64_t c0 = int64_t(blockIdx.x) * 64, r0 = int64_t(blockIdx.y) * 64;
-    _Pragma("unroll") for (int j = 0; j < 64; j += 4) {
-        const int64_t r = r0 + ty + j, c = c0 + tx;
-        tile[ty + j][tx] = (r < rows && c < cols) ? in[r * ld_in + c] : uint16_t(0);
-    }
-    __syncthreads();
-    _Pragma("unroll") for (int j = 0; j < 64; j += 4) {
-        const int64_t c = c0 + ty + j, r = r0 + tx;
-        if (c < cols && r < ld_out) out[c * ld_out + r] = r < rows ? tile[tx][ty + j] : uint16_t(0);     // zero the row padding too
-    }
-}
+constexpr int kBiasGrid8 = 1024;           // workgroups of the two pool / ReLU backward kernels
 
-__global__ __launch_bounds__(256) void colsum_partial_bf16_kernel(const bf16_t* __restrict__ x, int64_t ldx, int64_t rows, int cols,
-                                                                  double* __restrict__ partial) {
-    __shared__ double part[4][64];
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
-    const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
-    const int64_t r0 = int64_t(blockIdx.y) * per, r1 = r0 + per < rows ? r0 + per : rows;
-    double s = 0.0;
-    if (c < cols)
-        for (int64_t r = r0 + g; r < r1; r += 4) s += double(bf2f(x[r * ldx + c].bits));
-    part[g][lane] = s;
-    __syncthreads();
-    if (g == 0 && c < cols) partial[int64_t(blockIdx.y) * cols + c] = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-}
-
-__global__ void colsum_finish_bf16_kernel(const double* __restrict__ partial, int chunks, int cols, float* __restrict__ out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    double s = 0.0;
-    for (int k = 0; k < chunks; ++k) s += partial[int64_t(k) * cols + c];
-    out[c] = float(s);
-}
-
-// (Cout, Cin, 3, 3) f32 -> (Cin, 9, Cout) bf16 with the taps flipped: weights of the dgrad convolution
-__global__ void repack_dgrad_bf16_kernel(const float* __restrict__ w, bf16_t* __restrict__ out, int cout, int cin) {
-    const int64_t total = int64_t(cout) * 9 * cin;
-    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += int64_t(gridDim.x) * blockDim.x) {
-        const int co = int(i % cout);
-        const int tap = int((i / cout) % 9);
-        const int ci = int(i / (int64_t(cout) * 9));
-        out[i].bits = f2bf(w[(int64_t(co) * cin + ci) * 9 + (8 - tap)]);
-    }
-}
-
-constexpr int kBiasGrid8 = 1024;
-
-}  // namespace
-
-extern "C" int mla_maxpool2x2_bf16(const void* a, void* out, int64_t n, int H, int W, int C, mla_stream_t stream) {
-    MLA_REQUIRE(a && out && n >= 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, MLA_E_ARG, "bad maxpool arguments");
-    MLA_REQUIRE(mla::aligned(a, 16) && mla::aligned(out, 16), MLA_E_ARG, "maxpool buffers must be 16-byte aligned");
-    const int64_t total = n * (H / 2) * (W / 2) * (C / 8);
-    if (total == 0) return MLA_OK;
-    const unsigned grid = unsigned((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipLaunchKernelGGL(maxpool_bf16_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(a),
-                       static_cast<bf16_t*>(out), total, H, W, C);
-    MLA_LAUNCH_OK("maxpool_bf16");
+int finish_bias(const double* slots, int C, float* db, hipStream_t s) {
+    hipLaunchKernelGGL(bias_slots_finish_kernel<8>, dim3(unsigned(C)), dim3(256), 0, s, slots, int64_t(kBiasGrid8) * 256, C, db);
+    MLA_LAUNCH_OK("bias_slots_finish");
     return MLA_OK;
 }
+
+}  // namespace
 
 extern "C" int64_t mla_relu_pool_bwd_bf16_workspace_bytes(void) { return int64_t(kBiasGrid8) * 256 * 8 * 8; }
 
@@ -743,11 +527,7 @@ extern "C" int mla_relu_pool_bwd_bf16(const void* a, int a_dtype, const void* d_
         hipLaunchKernelGGL((relu_pool_bwd_bf16_kernel<float, float>), dim3(kBiasGrid8), dim3(256), 0, s, static_cast<const float*>(a),
                            static_cast<const float*>(d_out), static_cast<bf16_t*>(dz), total8, H, W, C, pool, slots);
     MLA_LAUNCH_OK("relu_pool_bwd_bf16");
-    if (db) {
-        hipLaunchKernelGGL(bias_slots_finish8_kernel, dim3(unsigned(C)), dim3(256), 0, s, slots, int64_t(kBiasGrid8) * 256, C, db);
-        MLA_LAUNCH_OK("bias_slots_finish8");
-    }
-    return MLA_OK;
+    return db ? finish_bias(slots, C, db, s) : MLA_OK;
 }
 
 extern "C" int mla_pool_bwd_codes_bf16(const void* codes, const void* d_pooled, void* dz, int64_t n, int H, int W, int C, void* workspace,
@@ -763,11 +543,7 @@ extern "C" int mla_pool_bwd_codes_bf16(const void* codes, const void* d_pooled, 
     hipLaunchKernelGGL(pool_bwd_codes_bf16_kernel, dim3(kBiasGrid8), dim3(256), 0, s, static_cast<const uint8_t*>(codes),
                        static_cast<const bf16_t*>(d_pooled), static_cast<bf16_t*>(dz), total8, H, W, C, slots);
     MLA_LAUNCH_OK("pool_bwd_codes_bf16");
-    if (db) {
-        hipLaunchKernelGGL(bias_slots_finish8_kernel, dim3(unsigned(C)), dim3(256), 0, s, slots, int64_t(kBiasGrid8) * 256, C, db);
-        MLA_LAUNCH_OK("bias_slots_finish8");
-    }
-    return MLA_OK;
+    return db ? finish_bias(slots, C, db, s) : MLA_OK;
 }
 
 extern "C" int mla_conv_wgrad_bf16(const void* dz, const void* a_in, int64_t n, int H, int W, int cin, int cout, float* workspace,
@@ -779,11 +555,7 @@ extern "C" int mla_conv_wgrad_bf16(const void* dz, const void* a_in, int64_t n, 
     const bf16_t* a = static_cast<const bf16_t*>(a_in);
 #define MLA_WGRAD_CASE(CI, CO, HH, WW) \
     if (cin == CI && cout == CO && H == HH && W == WW) return launch_wgrad_bf16<CI, CO, HH, WW>(z, a, n, workspace, workspace_floats, dw_oihw, s);
-    MLA_WGRAD_CASE(64, 128, 48, 32)
-    MLA_WGRAD_CASE(128, 256, 24, 16)
-    MLA_WGRAD_CASE(256, 256, 24, 16)
-    MLA_WGRAD_CASE(256, 512, 12, 8)
-    MLA_WGRAD_CASE(512, 512, 12, 8)
+    MLA_WGRAD_SHAPES(MLA_WGRAD_CASE)
 #undef MLA_WGRAD_CASE
     return mla::fail(MLA_E_SHAPE, "wgrad %dx%d %d->%d is not compiled", H, W, cin, cout);
 }
@@ -796,7 +568,6 @@ extern "C" int64_t mla_conv1_bwd_workspace_floats(void) {
 extern "C" int mla_conv1_bwd_bf16(const float* x, const float* w, const float* bias, const void* d_pooled, int64_t n, float* workspace,
                                   float* dw, float* db, mla_stream_t stream) {
     MLA_REQUIRE(x && w && bias && d_pooled && workspace && dw && db && n > 0, MLA_E_ARG, "bad conv1_bwd arguments");
-    const int64_t n_pix = n * 48 * 32;
     hipStream_t s = static_cast<hipStream_t>(stream);
 #if MLA_CONV1_BWD_MFMA
     MLA_REQUIRE(n * 48 <= 0x7fffffff, MLA_E_SHAPE, "too many rows for one launch");
@@ -808,45 +579,6 @@ extern "C" int mla_conv1_bwd_bf16(const float* x, const float* w, const float* b
     MLA_LAUNCH_OK("conv1_bwd_mfma_finish");
     return MLA_OK;
 #else
-    const int blocks = int((n_pix + 255) / 256 < 1024 ? (n_pix + 255) / 256 : 1024);
-    hipLaunchKernelGGL(conv1_bwd_bf16_kernel, dim3(blocks, 8), dim3(256), 0, s, x, w, bias, static_cast<const bf16_t*>(d_pooled), n_pix, workspace);
-    MLA_LAUNCH_OK("conv1_bwd_bf16");
-    hipLaunchKernelGGL(conv1_bwd_finish_bf16_kernel, dim3(640), dim3(256), 0, s, workspace, blocks, dw, db);
-    MLA_LAUNCH_OK("conv1_bwd_finish_bf16");
-    return MLA_OK;
+    return conv1_bwd_vector(x, w, bias, static_cast<const bf16_t*>(d_pooled), n, workspace, dw, db, s);
 #endif
-}
-
-extern "C" int mla_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int64_t cols,
-                                  mla_stream_t stream) {
-    MLA_REQUIRE(in && out && rows > 0 && cols > 0 && ld_in >= cols && ld_out >= rows, MLA_E_ARG, "bad transpose arguments");
-    hipLaunchKernelGGL(transpose_bf16_kernel, dim3(unsigned((cols + 63) / 64), unsigned((ld_out + 63) / 64)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), static_cast<const uint16_t*>(in), ld_in, static_cast<uint16_t*>(out), ld_out, rows, cols);
-    MLA_LAUNCH_OK("transpose_bf16");
-    return MLA_OK;
-}
-
-// workspace: 64 * cols doubles
-extern "C" int mla_col_sum_bf16(const void* x, int64_t ldx, int64_t rows, int64_t cols, void* workspace, float* out,
-                                mla_stream_t stream) {
-    MLA_REQUIRE(x && workspace && out && rows > 0 && cols > 0 && ldx >= cols, MLA_E_ARG, "bad col_sum arguments");
-    const int chunks = int(rows / 256 < 1 ? 1 : (rows / 256 > 64 ? 64 : rows / 256));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(colsum_partial_bf16_kernel, dim3(unsigned((cols + 63) / 64), unsigned(chunks)), dim3(256), 0, s,
-                       static_cast<const bf16_t*>(x), ldx, rows, int(cols), static_cast<double*>(workspace));
-    MLA_LAUNCH_OK("colsum partial bf16");
-    hipLaunchKernelGGL(colsum_finish_bf16_kernel, dim3(unsigned((cols + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const double*>(workspace), chunks, int(cols), out);
-    MLA_LAUNCH_OK("colsum finish bf16");
-    return MLA_OK;
-}
-
-extern "C" int mla_conv_repack_dgrad_bf16(const float* w_oihw, int64_t cout, int64_t cin, void* out, mla_stream_t stream) {
-    MLA_REQUIRE(w_oihw && out && cout > 0 && cin > 0, MLA_E_ARG, "bad repack arguments");
-    const int64_t total = cout * 9 * cin;
-    const unsigned grid = unsigned((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(repack_dgrad_bf16_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw,
-                       static_cast<bf16_t*>(out), int(cout), int(cin));
-    MLA_LAUNCH_OK("repack_dgrad_bf16_kernel");
-    return MLA_OK;
 }

@@ -855,6 +855,29 @@ __global__ void repack_kernel(const float* __restrict__ w, T* __restrict__ out, 
     }
 }
 
+// (Cout, Cin, 3, 3) f32 -> (Cin, 9, Cout) in the compute type with the taps flipped: the weights of the transposed
+// convolution that maps dZ (N,H,W,Cout) to dA (N,H,W,Cin):  W'[ci][8 - tap][co] = W[co][ci][tap]
+template <typename T>
+__global__ void repack_dgrad_kernel(const float* __restrict__ w, T* __restrict__ out, int cout, int cin) {
+    const int64_t total = int64_t(cout) * 9 * cin;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += int64_t(gridDim.x) * blockDim.x) {
+        const int co = int(i % cout);
+        const int tap = int((i / cout) % 9);
+        const int ci = int(i / (int64_t(cout) * 9));
+        store_elem<T>(out + i, w[(int64_t(co) * cin + ci) * 9 + (8 - tap)]);
+    }
+}
+
+template <typename T>
+int repack_dgrad(const float* w_oihw, int64_t cout, int64_t cin, T* out, mla_stream_t stream) {
+    MLA_REQUIRE(w_oihw && out && cout > 0 && cin > 0, MLA_E_ARG, "bad repack arguments");
+    const int64_t total = cout * 9 * cin;
+    const unsigned grid = unsigned((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(repack_dgrad_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, out, int(cout), int(cin));
+    MLA_LAUNCH_OK("repack_dgrad_kernel");
+    return MLA_OK;
+}
+
 template <typename T>
 __global__ void convert_kernel(const float* __restrict__ in, T* __restrict__ out, int64_t n) {
     for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
@@ -936,18 +959,6 @@ int conv_layer_split(int layer, const void* in, const void* w, const float* bias
         case 6: return launch_conv<Cfg<bf16_t, 512, 512, 12, 8, true, 4, true, true>>(in, w, bias, out, n, s);
     }
     return mla::fail(MLA_E_SHAPE, "conv layer %d is not one of VGGish conv2..conv6", layer);
-}
-
-// (Cout, Cin, 3, 3) f32 -> (Cin, 9, Cout) with the taps flipped: the weights of the transposed
-// convolution that maps dZ (N,H,W,Cout) to dA (N,H,W,Cin):  W'[ci][8 - tap][co] = W[co][ci][tap]
-__global__ void repack_dgrad_kernel(const float* __restrict__ w, float* __restrict__ out, int cout, int cin) {
-    const int64_t total = int64_t(cout) * 9 * cin;
-    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += int64_t(gridDim.x) * blockDim.x) {
-        const int co = int(i % cout);
-        const int tap = int((i / cout) % 9);
-        const int ci = int(i / (int64_t(cout) * 9));
-        out[i] = w[(int64_t(co) * cin + ci) * 9 + (8 - tap)];
-    }
 }
 
 // every compiled (H, W, Cin, Cout, pool, act) combination of the generic entry: VGGish forward with and without the
@@ -1042,12 +1053,11 @@ extern "C" int mla_conv3x3_train_codes(const void* in, const void* w_packed, con
 }
 
 extern "C" int mla_conv_repack_dgrad(const float* w_oihw, int64_t cout, int64_t cin, float* out, mla_stream_t stream) {
-    MLA_REQUIRE(w_oihw && out && cout > 0 && cin > 0, MLA_E_ARG, "bad repack arguments");
-    const int64_t total = cout * 9 * cin;
-    const unsigned grid = unsigned((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(repack_dgrad_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, out, int(cout), int(cin));
-    MLA_LAUNCH_OK("repack_dgrad_kernel");
-    return MLA_OK;
+    return repack_dgrad(w_oihw, cout, cin, out, stream);
+}
+
+extern "C" int mla_conv_repack_dgrad_bf16(const float* w_oihw, int64_t cout, int64_t cin, void* out, mla_stream_t stream) {
+    return repack_dgrad(w_oihw, cout, cin, static_cast<bf16_t*>(out), stream);
 }
 
 extern "C" int mla_conv_repack_weights(const float* w_oihw, int64_t cout, int64_t cin, void* out, int dtype,

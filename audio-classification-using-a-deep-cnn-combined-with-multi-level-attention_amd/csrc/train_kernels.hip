@@ -3,10 +3,13 @@
 // mean reduction, applied on top of model.py:268's sigmoid outputs), helpers for the Linear
 // backward (transposes feeding the MFMA GEMM, column sums for bias gradients), and the Adam
 // update (train.py:369 optim.Adam: betas 0.9/0.999, eps 1e-8, no weight decay, no amsgrad) over
-// one flat parameter buffer.
+// one flat parameter buffer. The helpers come in f32 and bf16 (the bf16 finetune step's Linear layers).
 #include "common.h"
+#include "mma_core.h"
 
 namespace {
+
+using mma::bf16_t;
 
 // out[c][r] = in[r][c]; 32x32 tiles through LDS (padded against bank conflicts)
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, int64_t ld_in, float* __restrict__ out,
@@ -22,6 +25,23 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
     _Pragma("unroll") for (int j = 0; j < 32; j += 8) {
         const int64_t c = c0 + ty + j, r = r0 + tx;
         if (r < rows && c < cols) out[c * ld_out + r] = tile[tx][ty + j];
+    }
+}
+
+// out[c][r] = in[r][c] for 2-byte elements; 64 x 64 tiles through LDS
+__global__ __launch_bounds__(256) void transpose_bf16_kernel(const uint16_t* __restrict__ in, int64_t ld_in, uint16_t* __restrict__ out,
+                                                             int64_t ld_out, int64_t rows, int64_t cols) {
+    __shared__ uint16_t tile[64][66];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;          // 64 x 4
+    const int64_t c0 = int64_t(blockIdx.x) * 64, r0 = int64_t(blockIdx.y) * 64;
+    _Pragma("unroll") for (int j = 0; j < 64; j += 4) {
+        const int64_t r = r0 + ty + j, c = c0 + tx;
+        tile[ty + j][tx] = (r < rows && c < cols) ? in[r * ld_in + c] : uint16_t(0);
+    }
+    __syncthreads();
+    _Pragma("unroll") for (int j = 0; j < 64; j += 4) {
+        const int64_t c = c0 + ty + j, r = r0 + tx;
+        if (c < cols && r < ld_out) out[c * ld_out + r] = r < rows ? tile[tx][ty + j] : uint16_t(0);     // zero the row padding too
     }
 }
 
@@ -75,8 +95,9 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
     }
 }
 
-// column sums of a (rows, cols) matrix: block (x = 64-column tile, y = row chunk) -> partials
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ x, int64_t ldx, int64_t rows, int cols,
+// column sums of a (rows, cols) f32 | bf16 matrix: block (x = 64-column tile, y = row chunk) -> partials
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, int cols,
                                                              double* __restrict__ partial) {
     __shared__ double part[4][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -85,7 +106,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     const int64_t r0 = int64_t(blockIdx.y) * per, r1 = r0 + per < rows ? r0 + per : rows;
     double s = 0.0;
     if (c < cols)
-        for (int64_t r = r0 + g; r < r1; r += 4) s += x[r * ldx + c];
+        for (int64_t r = r0 + g; r < r1; r += 4) s += double(mma::load_elem(x + r * ldx + c));
     part[g][lane] = s;
     __syncthreads();
     if (g == 0 && c < cols) partial[int64_t(blockIdx.y) * cols + c] = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
@@ -221,6 +242,15 @@ extern "C" int mla_transpose_f32(const float* in, int64_t ld_in, float* out, int
     return MLA_OK;
 }
 
+extern "C" int mla_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int64_t cols,
+                                  mla_stream_t stream) {
+    MLA_REQUIRE(in && out && rows > 0 && cols > 0 && ld_in >= cols && ld_out >= rows, MLA_E_ARG, "bad transpose arguments");
+    hipLaunchKernelGGL(transpose_bf16_kernel, dim3(unsigned((cols + 63) / 64), unsigned((ld_out + 63) / 64)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const uint16_t*>(in), ld_in, static_cast<uint16_t*>(out), ld_out, rows, cols);
+    MLA_LAUNCH_OK("transpose_bf16");
+    return MLA_OK;
+}
+
 extern "C" int mla_cross_entropy(const float* x, int64_t ldx, const int64_t* labels, int64_t rows, int K, float inv_total,
                                  float* loss, float* dx, int64_t ld_dx, int* n_correct, mla_stream_t stream) {
     MLA_REQUIRE(x && labels && loss && rows > 0 && K >= 1 && ldx >= K, MLA_E_ARG, "bad cross_entropy arguments");
@@ -235,20 +265,33 @@ extern "C" int mla_col_sum(const float* x, int64_t ldx, int64_t rows, int64_t co
                            mla_stream_t stream) {
     MLA_REQUIRE(x && workspace && out && rows > 0 && cols > 0 && ldx >= cols, MLA_E_ARG, "bad col_sum arguments");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int chunks;
-    if (cols % 4 == 0 && ldx % 4 == 0 && mla::aligned(x, 16)) {          // 16-byte loads, more row chunks (<= 64: the workspace)
-        chunks = int(rows / 64 < 1 ? 1 : (rows / 64 > 64 ? 64 : rows / 64));
+    const int chunks = int(rows / 64 < 1 ? 1 : (rows / 64 > 64 ? 64 : rows / 64));       // <= 64: the workspace
+    if (cols % 4 == 0 && ldx % 4 == 0 && mla::aligned(x, 16)) {          // 16-byte loads
         hipLaunchKernelGGL(colsum_partial4_kernel, dim3(unsigned((cols + 255) / 256), unsigned(chunks)), dim3(256), 0, s, x, ldx, rows,
                            int(cols), static_cast<double*>(workspace));
-    } else {
-        chunks = int(rows / 64 < 1 ? 1 : (rows / 64 > 64 ? 64 : rows / 64));       // narrow matrices (the attention modules' 10 columns): rows are the parallelism
-        hipLaunchKernelGGL(colsum_partial_kernel, dim3(unsigned((cols + 63) / 64), unsigned(chunks)), dim3(256), 0, s, x, ldx, rows,
+    } else {                                                             // narrow matrices (the attention modules' 10 columns): rows are the parallelism
+        hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3(unsigned((cols + 63) / 64), unsigned(chunks)), dim3(256), 0, s, x, ldx, rows,
                            int(cols), static_cast<double*>(workspace));
     }
     MLA_LAUNCH_OK("colsum partial");
     hipLaunchKernelGGL(colsum_finish_kernel, dim3(unsigned((cols + 255) / 256)), dim3(256), 0, s,
                        static_cast<const double*>(workspace), chunks, int(cols), out);
     MLA_LAUNCH_OK("colsum finish");
+    return MLA_OK;
+}
+
+// workspace: 64 * cols doubles
+extern "C" int mla_col_sum_bf16(const void* x, int64_t ldx, int64_t rows, int64_t cols, void* workspace, float* out,
+                                mla_stream_t stream) {
+    MLA_REQUIRE(x && workspace && out && rows > 0 && cols > 0 && ldx >= cols, MLA_E_ARG, "bad col_sum arguments");
+    const int chunks = int(rows / 256 < 1 ? 1 : (rows / 256 > 64 ? 64 : rows / 256));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(colsum_partial_kernel<bf16_t>, dim3(unsigned((cols + 63) / 64), unsigned(chunks)), dim3(256), 0, s,
+                       static_cast<const bf16_t*>(x), ldx, rows, int(cols), static_cast<double*>(workspace));
+    MLA_LAUNCH_OK("colsum partial bf16");
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(unsigned((cols + 255) / 256)), dim3(256), 0, s,
+                       static_cast<const double*>(workspace), chunks, int(cols), out);
+    MLA_LAUNCH_OK("colsum finish bf16");
     return MLA_OK;
 }
 

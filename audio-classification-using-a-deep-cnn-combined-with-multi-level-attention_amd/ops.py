@@ -544,7 +544,7 @@ def transpose_padded(x):
 
 
 def col_sum(x, out):
-    _chk(x)
+    _chk_rows(x)
     rows, cols = x.shape
     key = "colsum/" + str(x.device)
     if key not in _ws or _ws[key].numel() < 64 * cols:
@@ -660,6 +660,15 @@ def conv3x3_train_codes(x, w_packed, b, cout):
     return codes, pooled
 
 
+def _bias_ws(bf16, device):
+    """The double-precision slots of the bias gradient, per device: "biasws16/" for the bf16 kernels (8 channels per lane), "biasws/" f32."""
+    key = ("biasws16/" if bf16 else "biasws/") + str(device)
+    if key not in _ws:
+        nbytes = _lib.lib().mla_relu_pool_bwd_bf16_workspace_bytes() if bf16 else _lib.lib().mla_relu_pool_bwd_bias_workspace_bytes()
+        _ws[key] = torch.empty(int(nbytes) // 8, dtype=torch.float64, device=device)
+    return _ws[key]
+
+
 def pool_bwd_codes(codes, d_out, db=None):
     """dZ (n, H, W, C) bf16 at the pre-pool resolution from the window codes and the pooled gradient; db: bias gradient on the way."""
     assert codes.dtype == torch.uint8 and codes.is_cuda and codes.is_contiguous()
@@ -667,11 +676,8 @@ def pool_bwd_codes(codes, d_out, db=None):
     n, HO, WO, C = codes.shape
     assert tuple(d_out.shape) == tuple(codes.shape)
     dz = torch.empty((n, 2 * HO, 2 * WO, C), dtype=torch.bfloat16, device=codes.device)
-    key = "biasws16/" + str(codes.device)
-    if key not in _ws:
-        _ws[key] = torch.empty(int(_lib.lib().mla_relu_pool_bwd_bf16_workspace_bytes()) // 8, dtype=torch.float64, device=codes.device)
-    _lib.check(_timed("relu_pool_bwd", _lib.lib().mla_pool_bwd_codes_bf16, _p(codes), _p(d_out), _p(dz), n, 2 * HO, 2 * WO, C, _p(_ws[key]),
-                      _p(db), _lib.stream_ptr()))
+    _lib.check(_timed("relu_pool_bwd", _lib.lib().mla_pool_bwd_codes_bf16, _p(codes), _p(d_out), _p(dz), n, 2 * HO, 2 * WO, C,
+                      _p(_bias_ws(True, codes.device)), _p(db), _lib.stream_ptr()))
     return dz
 
 
@@ -703,11 +709,8 @@ def relu_pool_bwd(a, d_out, pool, db=None, bf16=False):
     n, H, W_, C = a4.shape
     if bf16 or a.dtype == torch.bfloat16:
         dz = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device)
-        key = "biasws16/" + str(a.device)
-        if key not in _ws:
-            _ws[key] = torch.empty(int(_lib.lib().mla_relu_pool_bwd_bf16_workspace_bytes()) // 8, dtype=torch.float64, device=a.device)
         _lib.check(_timed("relu_pool_bwd", _lib.lib().mla_relu_pool_bwd_bf16, _p(a), DT[a.dtype], _p(d_out), DT[d_out.dtype], _p(dz), n, H, W_, C,
-                          int(pool), _p(_ws[key]), _p(db), _lib.stream_ptr()))
+                          int(pool), _p(_bias_ws(True, a.device)), _p(db), _lib.stream_ptr()))
         return dz
     _chk(a, torch.float32)
     dz = torch.empty_like(a)
@@ -715,11 +718,8 @@ def relu_pool_bwd(a, d_out, pool, db=None, bf16=False):
         _lib.check(_lib.lib().mla_relu_pool_bwd(_p(a), _p(d_out), _p(dz), n, H, W_, C, int(pool), _lib.stream_ptr()))
         return dz
     _chk(db, torch.float32)
-    key = "biasws/" + str(a.device)
-    if key not in _ws:
-        _ws[key] = torch.empty(int(_lib.lib().mla_relu_pool_bwd_bias_workspace_bytes()) // 8, dtype=torch.float64, device=a.device)
-    _lib.check(_timed("relu_pool_bwd", _lib.lib().mla_relu_pool_bwd_bias, _p(a), _p(d_out), _p(dz), n, H, W_, C, int(pool), _p(_ws[key]), _p(db),
-                      _lib.stream_ptr()))
+    _lib.check(_timed("relu_pool_bwd", _lib.lib().mla_relu_pool_bwd_bias, _p(a), _p(d_out), _p(dz), n, H, W_, C, int(pool),
+                      _p(_bias_ws(False, a.device)), _p(db), _lib.stream_ptr()))
     return dz
 
 

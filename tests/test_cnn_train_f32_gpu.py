@@ -1,5 +1,5 @@
-"""GPU tests of the f32 VGGish backward kernels (csrc/cnn_train.hip, the f32 dgrad instantiations of csrc/conv.hip), one kernel at a
-time against float64 torch autograd on the CPU.
+"""GPU tests of the f32 VGGish backward kernels (csrc/cnn_train.hip with the rules it shares with the bf16 form in
+csrc/cnn_train_core.h, the f32 dgrad instantiations of csrc/conv.hip), one kernel at a time against float64 torch autograd on the CPU.
 
 Most tests here need NO tolerance: operands are drawn from a coarse dyadic grid (multiples of 2^-4 in [-1, 1] unless a test says
 otherwise). A product of two grid values is a multiple of 2^-8, and as long as the sum of the absolute values of all terms of one
@@ -93,7 +93,7 @@ def test_relu_bwd_f32_of_the_last_linear_layer(ops, W):
 
 
 def test_relu_pool_bwd_bias_f32_grid_stride_loop(ops):
-    """relu_pool_bwd_bias_kernel always runs 4096 x 256 threads: pooled (48, 24, 16, 256) has 1 179 648 work items, so 131 072 threads
+    """relu_pool_bwd_kernel<true> (the form with bias slots) always runs 4096 x 256 threads: pooled (48, 24, 16, 256) has 1 179 648 work items, so 131 072 threads
     take a second trip and their slots hold two elements. db: 48 * 12 * 8 = 4608 terms per channel, exact as above."""
     gen = torch.Generator().manual_seed(811)
     n, H, Wd, C = 48, 24, 16, 256
@@ -119,7 +119,7 @@ def test_relu_pool_bwd_f32_beyond_the_grid_cap(ops):
 
 
 def test_maxpool_f32_beyond_the_grid_cap(ops):
-    """maxpool_kernel works on four channels per thread, so its 16384 x 256 cap is passed only above 4 194 304 output QUADS: 1366
+    """maxpool_kernel<float> works on four channels per thread, so its 16384 x 256 cap is passed only above 4 194 304 output QUADS: 1366
     images of (12, 8, 512). No shape passes that cap with less than 4 x 4 194 304 x 4 input values (268 MB of f32): the channel
     count cancels. The float64 reference is taken in slices of 128 images, so the host holds 50 MB of it at a time."""
     gen = torch.Generator().manual_seed(813)

@@ -1,4 +1,5 @@
-"""GPU tests of the bf16 finetune path (csrc/cnn_train_bf16.hip + the bf16 instantiations of the generic conv entry):
+"""GPU tests of the bf16 finetune path (csrc/cnn_train_bf16.hip, the bf16 instantiations of csrc/cnn_train.hip's maxpool, of
+csrc/train_kernels.hip's Linear-backward helpers and of csrc/conv.hip's generic conv entry and dgrad repack; shared rules in csrc/cnn_train_core.h):
 every kernel against a float64 torch-CPU computation on the SAME bf16-rounded operands (so the only differences are the
 f32 accumulation order and the final rounding), then the whole step against the loss curve the reference produced
 (tests/golden/train.npz 'finetune'), with the measured bf16 deviation stated next to the bound."""
@@ -98,6 +99,30 @@ def test_transpose_and_col_sum_bf16(ops, W):
         out = torch.empty(C, dtype=torch.float32, device="cuda")
         ops.col_sum(x.cuda(), out)
         np.testing.assert_allclose(out.cpu().numpy(), x.double().sum(dim=0).numpy(), rtol=1e-6, atol=1e-6)
+
+
+def test_relu_bwd_of_an_f32_linear_output_gives_bf16_dz_and_its_column_sums(ops, W):
+    """relu_pool_bwd_bf16_kernel<float, float> with the bias slots, un-pooled, at (5, 128): 80 lanes of 8 channels, every other
+    slot stays zero. dZ = where(a > 0, d_out, 0) rounded to bf16, bit for bit; db is the column sum of THOSE bf16 values (what the
+    layer's weight gradient is formed from): 5 terms of 8 significant bits are exact in double, one rounding to f32. The f32 inputs
+    hold bf16-representable values, as the activations and gradients of the bf16 step do: the kernel sums its slots before it rounds
+    dZ for the store, so only on such values are "the column sum of dZ" and "the column sum of what was stored" the same number."""
+    h, g = bf(rnd(W, 94, 1, (5, 128))).float().clamp_min(0), bf(rnd(W, 95, 2, (5, 128))).float()
+    db = torch.full((128,), 9.0, device="cuda")
+    dz = ops.relu_pool_bwd(h.cuda(), g.cuda(), pool=False, db=db, bf16=True).cpu()
+    ref = bf(torch.where(h > 0, g, torch.zeros_like(g)))
+    assert dz.dtype == torch.bfloat16 and torch.equal(dz, ref)
+    assert torch.equal(db.cpu(), ref.double().sum(dim=0).float())
+
+
+def test_col_sum_bf16_of_a_strided_column_slice(ops, W):
+    """colsum_partial_kernel<bf16_t> on columns 40 .. 169 of a (1000, 200) matrix (row pitch 200): 1000 // 256 = 3 row chunks of 334
+    rows (the last one 332: neither a multiple of the 4 row groups), three 64-column tiles of which the last holds 2 columns.
+    1000 bf16 values of |v| < 1 add exactly in double (8 + 10 bits of 53), so the result is the float64 sum rounded once to f32."""
+    wide = bf(rnd(W, 96, 1, (1000, 200)))
+    x, out = wide[:, 40:170], torch.full((130,), 9.0, device="cuda")
+    ops.col_sum(wide.cuda()[:, 40:170], out)
+    assert torch.equal(out.cpu(), x.double().sum(dim=0).float())
 
 
 @pytest.mark.parametrize("cin,cout,H,Wd,act", [(64, 128, 48, 32, True), (256, 256, 24, 16, True), (512, 512, 12, 8, True),
