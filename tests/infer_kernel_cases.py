@@ -373,7 +373,8 @@ def conv_case(layer, kind):
         planted = win[0, :, 2, 1, :]                                        # the window behind the block of zeros: four times the bias
         assert torch.equal(planted, bb.view(-1, 1).expand(-1, 4)) and bool((planted > 0).any())
         y = F.max_pool2d(y, 2)
-    return dict(x=x, w=w, b=b, y=y.permute(0, 2, 3, 1).contiguous().cpu(), unit=unit, g=g)
+    return dict(x=x, w=w, b=b, y=y.permute(0, 2, 3, 1).contiguous().cpu(), unit=unit, g=g,
+                pre=pre.permute(0, 2, 3, 1).contiguous().cpu())       # the exact pre-activations, NHWC (tests/cnn_train_bf16_cases.py)
 
 
 def packed_weight(w, dtype):

@@ -161,6 +161,19 @@ def test_argument_errors_are_reported_before_any_launch(L):
     expect(E_ARG, lib.mla_relu_pool_bwd(None, fake, fake, 2, 12, 8, 64, 1, None))
     assert lib.mla_relu_pool_bwd(fake, fake, fake, 0, 13, 7, 64, 0, None) == 0
     assert lib.mla_relu_pool_bwd(fake, fake, fake, 0, 12, 8, 64, 1, None) == 0
+    # the bf16 forms: 8 channels per lane and a fixed grid whose stride must be a multiple of C / 8 (C = 24: 262 144 % 3 != 0); even
+    # H, W; the bias gradient needs the workspace of double slots
+    for bad_c in (24, 12, 0):
+        expect(E_SHAPE, lib.mla_relu_pool_bwd_bf16(fake, L.BF16, fake, L.BF16, fake, 2, 12, 8, bad_c, 1, fake, fake, None), "channel count")
+        expect(E_SHAPE, lib.mla_pool_bwd_codes_bf16(fake, fake, fake, 2, 12, 8, bad_c, fake, fake, None), "channel count")
+    expect(E_SHAPE, lib.mla_relu_pool_bwd_bf16(fake, L.BF16, fake, L.BF16, fake, 2, 13, 8, 64, 1, fake, fake, None), "even")
+    expect(E_SHAPE, lib.mla_relu_pool_bwd_bf16(fake, L.BF16, fake, L.BF16, fake, 2, 12, 7, 64, 1, None, None, None), "even")
+    expect(E_SHAPE, lib.mla_pool_bwd_codes_bf16(fake, fake, fake, 2, 13, 8, 64, fake, fake, None), "even")
+    expect(E_SHAPE, lib.mla_pool_bwd_codes_bf16(fake, fake, fake, 2, 12, 7, 64, None, None, None), "even")
+    expect(E_ARG, lib.mla_relu_pool_bwd_bf16(fake, L.BF16, fake, L.BF16, fake, 2, 12, 8, 64, 1, None, fake, None), "workspace")
+    expect(E_ARG, lib.mla_relu_pool_bwd_bf16(fake, L.BF16, fake, L.BF16, fake, 2, 12, 8, 64, 0, None, fake, None), "workspace")
+    expect(E_ARG, lib.mla_pool_bwd_codes_bf16(fake, fake, fake, 2, 12, 8, 64, None, fake, None), "workspace")
+    expect(E_DTYPE, lib.mla_relu_pool_bwd_bf16(fake, L.BF16, fake, L.F32, fake, 2, 12, 8, 64, 1, fake, fake, None))
     # BatchNorm backward, second stage: the channel layout is validated exactly as in the first (mla_bn_bwd_sums)
     cd = ctypes.c_double
 
