@@ -55,6 +55,15 @@ def lib():
         L.mla_stft_magnitude.argtypes = [vp, i64, vp, vp, i64, i64, i64, vp, vp]
         L.mla_mel_log.argtypes = [vp, vp, i64, i64, i64, cf, vp, vp]
         L.mla_dataset_frames.argtypes = [vp, i64, ci, ci, ci, ci, vp, vp]
+        L.mla_melspec_frames.restype = i64
+        L.mla_melspec_frames.argtypes = [i64, i64]
+        L.mla_melspec_table_floats.restype = i64
+        L.mla_melspec_table_floats.argtypes = [ctypes.c_double, i64]
+        L.mla_melspec_build_tables.argtypes = [ctypes.c_double, i64, vp]
+        L.mla_melspec_workspace_bytes.restype = i64
+        L.mla_melspec_workspace_bytes.argtypes = [i64, i64, i64]
+        L.mla_melspec_db.argtypes = [vp, i64, i64, i64, i64, i64, cf, vp, vp, vp, vp]
+        L.mla_melspec_images.argtypes = [vp, vp, i64, i64, i64, i64, cf, i64, i64, i64, vp, vp]
         L.mla_postprocess.argtypes = [vp, vp, vp, i64, vp, vp]
         L.mla_mono_mix.argtypes = [vp, ci, i64, ci, vp, vp]
         L.mla_split_bf16x3.argtypes = [vp, i64, i64, i64, vp, i64, i64, ci, vp]

@@ -1,0 +1,176 @@
+// melspec.hip -- the ResNet branch's audio front-end on gfx950: batched power mel-dB spectrograms and the
+// top_db clip + split into images (reference: dataset.py:309-316 librosa.feature.melspectrogram + power_to_db,
+// dataset.py:329-363 split). Per-thread arithmetic: melspec_core.h; tables: melspec_tables.h.
+//
+// melspec_db_kernel: one workgroup of 256 threads owns a run of up to 16 consecutive frames of one clip. It stages
+// the run's 2048 + (F - 1) * hop padded samples once in LDS (reflect indexing applied while staging; every read
+// stays inside the clip's row), then per frame: windowed radix-4 FFT of 1024 complex points in LDS (5 barriers),
+// even/odd split to 1025 powers, sparse mel sums (one thread per band, ascending bins, no atomics) and
+// 10 log10(max(amin, .)) into a (band, frame) LDS tile. The tile is flushed band-major: the 16 frames of a band are
+// consecutive in D, so every band's store is one 64-byte run. The run's maximum goes to the clip's workspace slot.
+// A clip's result depends on nothing but its own samples: runs are cut per clip, never across the batch.
+//
+// melspec_images_kernel: reduces the clip's partial maxima (max is exact in any order), then a pure select + gather:
+// out[c][t][0][band][x] = max(D[c][band][t * stride + x], Dmax_c - top_db).
+#include "common.h"
+#include "melspec_core.h"
+#include "melspec_tables.h"
+
+namespace {
+
+using namespace melspec;
+
+__global__ __launch_bounds__(kThreads) void melspec_db_kernel(const float* __restrict__ pcm, int64_t row_stride, int n, int hop,
+                                                              int frames, int runs, int per_run, const float* __restrict__ tab,
+                                                              int n_mels, float amin, float* __restrict__ D,
+                                                              float* __restrict__ partial) {
+    extern __shared__ float lds[];
+    float* win = lds + kLdsWin;
+    float* tw = lds + kLdsTw;
+    float* stage = lds + kLdsStage;
+    float* zr = lds + kLdsZr;
+    float* zi = lds + kLdsZi;
+    float* pw = lds + kLdsPw;
+    float* tile = lds + kLdsTile;
+    const int t = threadIdx.x;
+    const int64_t clip = blockIdx.x / runs;
+    const int run = int(blockIdx.x - clip * runs);
+    const int f0 = run * per_run;
+    const int nf = frames - f0 < per_run ? frames - f0 : per_run;
+    const int* meta = reinterpret_cast<const int*>(tab + kTabMeta);
+    const float* weights = tab + tab_weights(n_mels);
+
+    for (int i = t; i < kFft + 2 * kTw; i += kThreads) lds[i] = tab[i];      // window and twiddles are contiguous in both
+    stage_samples(t, pcm + clip * row_stride, n, f0 * hop, kFft + (nf - 1) * hop, stage);
+    __syncthreads();
+    float best = -INFINITY;
+    for (int f = 0; f < nf; ++f) {
+        fft_first(t, stage + f * hop, win, zr, zi);
+        __syncthreads();
+        for (int s = 1; s <= 4; ++s) {
+            fft_stage(t, s, tw, zr, zi);
+            __syncthreads();
+        }
+        power(t, tw, zr, zi, pw);
+        __syncthreads();                                                   // zr / zi are free again after this barrier
+        best = fmaxf(best, mel_db(t, pw, meta, weights, n_mels, amin, f, tile));
+        // pw is next written after the following frame's five FFT barriers
+    }
+    __syncthreads();
+    float* out = D + clip * int64_t(n_mels) * frames + f0;
+    for (int i = t; i < n_mels * kRunFrames; i += kThreads) {
+        const int b = i / kRunFrames, f = i % kRunFrames;
+        if (f < nf) out[int64_t(b) * frames + f] = tile[i];
+    }
+    zr[t] = best;                                                          // block maximum: zr is dead here
+    __syncthreads();
+    for (int s = kThreads / 2; s > 0; s >>= 1) {
+        if (t < s) zr[t] = fmaxf(zr[t], zr[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) partial[blockIdx.x] = zr[0];
+}
+
+__global__ __launch_bounds__(256) void melspec_images_kernel(const float* __restrict__ D, const float* __restrict__ partial, int runs,
+                                                             int n_mels, int frames, int n_images, int image_w, int stride,
+                                                             float top_db, int blocks_per_clip, float* __restrict__ out) {
+    __shared__ float red[256];
+    const int t = threadIdx.x;
+    const int64_t clip = blockIdx.x / blocks_per_clip;
+    const int part = int(blockIdx.x - clip * blocks_per_clip);
+    float m = -INFINITY;
+    for (int i = t; i < runs; i += 256) m = fmaxf(m, partial[clip * runs + i]);
+    red[t] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] = fmaxf(red[t], red[t + s]);
+        __syncthreads();
+    }
+    const float lo = red[0] - top_db;
+    const int64_t per_clip = int64_t(n_images) * n_mels * image_w;
+    const float* src = D + clip * int64_t(n_mels) * frames;
+    float* dst = out + clip * per_clip;
+    for (int64_t i = int64_t(part) * 256 + t; i < per_clip; i += int64_t(blocks_per_clip) * 256) {
+        const int x = int(i % image_w);
+        const int64_t r = i / image_w;
+        const int b = int(r % n_mels), img = int(r / n_mels);
+        dst[i] = fmaxf(src[int64_t(b) * frames + int64_t(img) * stride + x], lo);
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t mla_melspec_frames(int64_t n_samples, int64_t hop) {
+    if (n_samples < 0 || hop < 1) return -1;
+    return 1 + n_samples / hop;
+}
+
+extern "C" int64_t mla_melspec_table_floats(double sr, int64_t n_mels) { return melspec::table_floats(sr, n_mels); }
+
+extern "C" int mla_melspec_build_tables(double sr, int64_t n_mels, float* host_out) {
+    MLA_REQUIRE(host_out, MLA_E_ARG, "null melspec table buffer");
+    MLA_REQUIRE(melspec::valid_config(sr, n_mels), MLA_E_ARG, "melspec tables need sr > 0 and 1 <= n_mels <= %d (got sr %g, n_mels %lld)",
+                kMaxMels, sr, (long long)n_mels);
+    return melspec::build_tables(sr, n_mels, host_out) == 0 ? MLA_OK : ::mla::fail(MLA_E_ARG, "melspec tables could not be built");
+}
+
+namespace {
+int check_signal(int64_t n_samples, int64_t hop, int64_t n_mels) {
+    MLA_REQUIRE(hop >= 1, MLA_E_ARG, "melspec hop %lld < 1", (long long)hop);
+    MLA_REQUIRE(n_mels >= 1 && n_mels <= kMaxMels, MLA_E_ARG, "melspec n_mels %lld outside [1, %d]", (long long)n_mels, kMaxMels);
+    MLA_REQUIRE(n_samples >= kMinSamples, MLA_E_SHORT, "melspec needs at least %d samples per clip for reflect padding by %d (got %lld)",
+                kMinSamples, kPad, (long long)n_samples);
+    MLA_REQUIRE(n_samples <= (1 << 30), MLA_E_SHAPE, "melspec clips longer than 2^30 samples are not supported (got %lld)", (long long)n_samples);
+    return MLA_OK;
+}
+int64_t runs_of(int64_t n_samples, int64_t hop) {
+    const int64_t frames = 1 + n_samples / hop, per = run_frames(hop);
+    return (frames + per - 1) / per;
+}
+}  // namespace
+
+extern "C" int64_t mla_melspec_workspace_bytes(int64_t clips, int64_t n_samples, int64_t hop) {
+    if (clips < 0 || n_samples < 0 || hop < 1) return -1;
+    return clips * runs_of(n_samples, hop) * int64_t(sizeof(float));
+}
+
+extern "C" int mla_melspec_db(const float* pcm, int64_t clips, int64_t n_samples, int64_t clip_stride, int64_t hop, int64_t n_mels,
+                              float amin, const float* tables, float* out_db, float* workspace, mla_stream_t stream) {
+    MLA_REQUIRE(clips >= 0, MLA_E_ARG, "melspec clips %lld < 0", (long long)clips);
+    if (int rc = check_signal(n_samples, hop, n_mels)) return rc;
+    MLA_REQUIRE(clip_stride >= n_samples, MLA_E_ARG, "melspec clip stride %lld < n_samples %lld", (long long)clip_stride, (long long)n_samples);
+    MLA_REQUIRE(amin > 0.f, MLA_E_ARG, "melspec amin must be positive (got %g)", double(amin));
+    if (clips == 0) return MLA_OK;
+    MLA_REQUIRE(pcm && tables && out_db && workspace, MLA_E_ARG, "null melspec argument");
+    const int64_t frames = 1 + n_samples / hop, per = run_frames(hop), runs = runs_of(n_samples, hop);
+    MLA_REQUIRE(clips * runs <= 0x7fffffffll, MLA_E_SHAPE, "melspec grid of %lld workgroups is too large", (long long)(clips * runs));
+    const size_t lds = size_t(lds_floats(int(n_mels))) * sizeof(float);
+    MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(melspec_db_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    hipLaunchKernelGGL(melspec_db_kernel, dim3(unsigned(clips * runs)), dim3(kThreads), lds, static_cast<hipStream_t>(stream), pcm,
+                       clip_stride, int(n_samples), int(hop), int(frames), int(runs), int(per), tables, int(n_mels), amin, out_db, workspace);
+    MLA_LAUNCH_OK("melspec_db_kernel");
+    return MLA_OK;
+}
+
+extern "C" int mla_melspec_images(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
+                                  float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, float* out, mla_stream_t stream) {
+    MLA_REQUIRE(clips >= 0, MLA_E_ARG, "melspec clips %lld < 0", (long long)clips);
+    if (int rc = check_signal(n_samples, hop, n_mels)) return rc;
+    MLA_REQUIRE(top_db >= 0.f, MLA_E_ARG, "melspec top_db must be non-negative (got %g)", double(top_db));
+    MLA_REQUIRE(n_images >= 1 && image_w >= 1 && image_stride >= 0, MLA_E_ARG, "bad melspec image arguments (%lld images of width %lld, stride %lld)",
+                (long long)n_images, (long long)image_w, (long long)image_stride);
+    const int64_t frames = 1 + n_samples / hop, runs = runs_of(n_samples, hop);
+    MLA_REQUIRE(image_w <= frames && image_stride <= frames && (n_images - 1) * image_stride + image_w <= frames, MLA_E_SHAPE,
+                "images leave the %lld-column spectrogram (%lld images of width %lld, stride %lld)", (long long)frames, (long long)n_images,
+                (long long)image_w, (long long)image_stride);
+    if (clips == 0) return MLA_OK;
+    MLA_REQUIRE(db && workspace && out, MLA_E_ARG, "null melspec argument");
+    const int64_t per_clip = n_images * n_mels * image_w;
+    int64_t bpc = (per_clip + 2047) / 2048;
+    bpc = bpc < 1 ? 1 : bpc > 1024 ? 1024 : bpc;
+    MLA_REQUIRE(clips * bpc <= 0x7fffffffll && n_images <= 0x7fffffffll, MLA_E_SHAPE, "melspec image grid is too large");
+    hipLaunchKernelGGL(melspec_images_kernel, dim3(unsigned(clips * bpc)), dim3(256), 0, static_cast<hipStream_t>(stream), db, workspace,
+                       int(runs), int(n_mels), int(frames), int(n_images), int(image_w), int(image_stride), top_db, int(bpc), out);
+    MLA_LAUNCH_OK("melspec_images_kernel");
+    return MLA_OK;
+}

@@ -139,6 +139,76 @@ def waveforms_to_examples(pcm, out_dtype=torch.float32, out=None):
     return out
 
 
+_melspec_tables = {}
+MELSPEC_AMIN = 1e-10      # librosa.power_to_db's default amin (ref = 1.0)
+
+
+def melspec_tables(device, sr, n_mels):
+    """Window, twiddles and the sparse Slaney mel basis for (sr, n_mels), built by the library in float64 and uploaded once."""
+    key = (str(device), float(sr), int(n_mels))
+    if key not in _melspec_tables:
+        L = _lib.lib()
+        n = int(L.mla_melspec_table_floats(float(sr), int(n_mels)))
+        if n < 0:
+            raise ValueError("melspectrogram_db needs sr > 0 and 1 <= n_mels <= 1024 (got sr=%r, n_mels=%r)" % (sr, n_mels))
+        host = np.zeros(n, dtype=np.float32)
+        _lib.check(L.mla_melspec_build_tables(float(sr), int(n_mels), host.ctypes.data_as(ctypes.c_void_p)))
+        _melspec_tables[key] = torch.from_numpy(host).to(device)
+    return _melspec_tables[key]
+
+
+def melspec_frames(n_samples, hop_length):
+    return int(_lib.lib().mla_melspec_frames(int(n_samples), int(hop_length)))
+
+
+def melspec_db_unclipped(pcm, sr, n_mels, hop_length):
+    """(clips, n) device PCM -> ((clips, n_mels, frames) dB values before the top_db clip, the workspace of per-clip partial
+    maxima that melspec_images reads). Kernel 1 of the ResNet branch's front-end (csrc/melspec.hip)."""
+    assert pcm.dim() == 2 and pcm.is_cuda and pcm.dtype == torch.float32 and (pcm.shape[1] <= 1 or pcm.stride(1) == 1)
+    clips, n = pcm.shape
+    L = _lib.lib()
+    tab = melspec_tables(pcm.device, sr, n_mels)
+    ws_bytes = int(L.mla_melspec_workspace_bytes(clips, n, int(hop_length)))
+    frames = melspec_frames(n, hop_length)
+    if ws_bytes < 0 or frames < 0:
+        raise ValueError("hop_length must be a positive integer (got %r)" % (hop_length,))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=pcm.device)
+    db = torch.empty((clips, int(n_mels), frames), dtype=torch.float32, device=pcm.device)
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_db", L.mla_melspec_db, vp(pcm.data_ptr()), clips, n, pcm.stride(0) if clips > 1 else n, int(hop_length),
+                          int(n_mels), MELSPEC_AMIN, vp(tab.data_ptr()), vp(db.data_ptr()), vp(ws.data_ptr()), _lib.stream_ptr()))
+    return db, ws
+
+
+def melspec_images(db, ws, n_samples, hop_length, top_db, n_images, image_w, image_stride):
+    """power_to_db's clip against the clip-wide maximum + split: (clips, n_mels, frames) -> (clips, n_images, 1, n_mels, image_w).
+    Kernel 2 of the ResNet branch's front-end: a select and a gather, bit-determined by `db`."""
+    clips, n_mels, _ = db.shape
+    out = torch.empty((clips, int(n_images), 1, n_mels, int(image_w)), dtype=torch.float32, device=db.device)
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_images", _lib.lib().mla_melspec_images, vp(db.data_ptr()), vp(ws.data_ptr()), clips, int(n_samples),
+                          int(hop_length), n_mels, float(top_db), int(n_images), int(image_w), int(image_stride), vp(out.data_ptr()),
+                          _lib.stream_ptr()))
+    return out
+
+
+def melspectrogram_db(pcm, sr, n_mels, hop_length, top_db=80.0):
+    """librosa.power_to_db(librosa.feature.melspectrogram(y, sr=sr, n_mels=n_mels, hop_length=hop_length), top_db=top_db) with
+    librosa's defaults (n_fft 2048, periodic Hann, centre reflect padding, power 2, Slaney mel basis; ref 1.0, amin 1e-10) for
+    every row of `pcm`: (clips, n) float32 device PCM -> (clips, n_mels, 1 + n // hop_length) float32. top_db=None skips the clip.
+    Clips shorter than 1025 samples raise ValueError (reflect padding by 1024 needs them)."""
+    if pcm.shape[1] < 1025:
+        raise ValueError("melspectrogram_db needs at least 1025 samples per clip (got %d)" % pcm.shape[1])
+    if top_db is not None and top_db < 0:
+        raise ValueError("top_db must be non-negative")
+    db, ws = melspec_db_unclipped(pcm, sr, n_mels, hop_length)
+    if top_db is None:
+        return db
+    return melspec_images(db, ws, pcm.shape[1], hop_length, top_db, 1, db.shape[2], 0)[:, 0, 0]
+
+
 def _as_device_signal(signal):
     dev = _device()
     if isinstance(signal, np.ndarray):

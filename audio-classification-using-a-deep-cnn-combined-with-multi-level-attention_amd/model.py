@@ -108,7 +108,8 @@ class Ensemble(nn.Module):
     def _waveforms_only_vggish(self):
         if self.cnn_type != "vggish":
             raise NotImplementedError("the waveform paths feed VGGish log-mel examples; cnn_type 'resnet' takes 224 x 224 "
-                                      "spectrogram images (dataset.py:175-178 of the reference) through forward()")
+                                      "spectrogram images (dataset.py:175-178 of the reference) through forward(), or 4 s clips "
+                                      "of 22 050 Hz PCM through forward_clips()")
 
     def forward_waveforms(self, pcm):
         """Fused online path of the north star: (B, n_samples) 16 kHz PCM on the device (float32
@@ -127,6 +128,16 @@ class Ensemble(nn.Module):
         assert ex.shape[0] == pcm.shape[0] * T, "each waveform must yield exactly T examples"
         features = self.cnn(ex)
         return self.mla(features.reshape(-1, T, self.emb_input_size))
+
+    def forward_clips(self, pcm, overlap=True):
+        """The ResNet branch's wave -> scores entry: (B, SAMPLES_NUM_RESNET) float32 PCM at 22 050 Hz on the device -> the
+        (B, T, 1, 224, 224) mel-dB images of dataset.clips_to_images (two HIP kernels) -> forward(). input_conf, precision and
+        just_bottlenecks act as in forward()."""
+        if self.cnn_type != "resnet":
+            raise NotImplementedError("forward_clips feeds the ResNet branch's mel-dB images; cnn_type 'vggish' takes 16 kHz PCM "
+                                      "through forward_waveforms()")
+        from . import dataset
+        return self.forward(dataset.clips_to_images(pcm, overlap))
 
     def stream_waveforms(self, host_batches):
         """Host-resident PCM: iterate over (B, n_samples) float32 / int16 tensors in PINNED host memory and yield the

@@ -24,3 +24,8 @@ BATCH_SIZE = 8
 NUM_EPOCHS = 25
 FEATURE_EXTRACT = True
 LR = 0.001
+
+# the ResNet branch's audio constants (params.py:8, :11-12 of the reference)
+MAX_SECONDS = 4
+SR_RESNET = 22_050
+SAMPLES_NUM_RESNET = SR_RESNET * MAX_SECONDS

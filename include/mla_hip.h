@@ -110,6 +110,36 @@ int mla_mono_mix(const void* pcm, int pcm_dtype, int64_t n_samples, int channels
  * spec_c is the (64, 384) concatenation of the clip's <= 4 transposed examples, zero-padded. */
 int mla_dataset_frames(const float* examples, int64_t clips, int ex_per_clip, int n_frames, int frame_len,
                        int stride, float* out, mla_stream_t stream);
+/* ---- ResNet branch front-end: dataset.create_spec(cnn_type="resnet") + split (dataset.py:309-316, :329-363) ----
+ * librosa.feature.melspectrogram(y, sr, n_mels=n_mels, hop_length=hop) with its defaults (n_fft = win_length = 2048,
+ * periodic Hann, center=True, pad_mode="reflect", power 2, Slaney mel basis over 0..sr/2, norm="slaney") followed by
+ * librosa.power_to_db(S, ref=1.0, amin, top_db), for a batch of clips. n_fft is fixed at 2048 (the reference never
+ * passes another); 1 <= n_mels <= 1024; clips of at least 1025 samples (one reflection must cover the 1024-sample
+ * padding; shorter clips return MLA_E_SHORT). */
+
+/* Spectrogram columns of a clip: 1 + n_samples / hop (host; -1 for n_samples < 0 or hop < 1). */
+int64_t mla_melspec_frames(int64_t n_samples, int64_t hop);
+/* Constant tables (periodic Hann, FFT twiddles, the Slaney filterbank in sparse form: per band the first bin, the bin
+ * count and the offset of its packed weights), computed in double precision on the host and rounded once.
+ * `host_out` receives mla_melspec_table_floats(sr, n_mels) floats (-1 for an invalid configuration); the caller
+ * uploads them once per (sr, n_mels) and passes the device copy to mla_melspec_db. */
+int64_t mla_melspec_table_floats(double sr, int64_t n_mels);
+int     mla_melspec_build_tables(double sr, int64_t n_mels, float* host_out);
+/* Bytes of the per-clip partial maxima mla_melspec_db writes and mla_melspec_images reads (-1 for bad arguments). */
+int64_t mla_melspec_workspace_bytes(int64_t clips, int64_t n_samples, int64_t hop);
+/* pcm[clips][clip_stride] f32 (the first n_samples of each row are used) -> out_db[clips][n_mels][frames],
+ * 10 log10(max(amin, S)) WITHOUT the top_db clip, frames = mla_melspec_frames(n_samples, hop), and the workspace of
+ * partial maxima. A clip's values depend on its own samples only (fixed summation order, no atomics). */
+int mla_melspec_db(const float* pcm, int64_t clips, int64_t n_samples, int64_t clip_stride, int64_t hop, int64_t n_mels,
+                   float amin, const float* tables, float* out_db, float* workspace, mla_stream_t stream);
+/* power_to_db's clip + split: out[clips][n_images][1][n_mels][image_w] with
+ * out[c][t][0][b][x] = max(db[c][b][t * image_stride + x], max(db[c]) - top_db); the maximum is taken over the clip's
+ * whole spectrogram (from `workspace`, as mla_melspec_db left it for the same clips, n_samples and hop). Images
+ * that leave the spectrogram ((n_images - 1) * image_stride + image_w > frames) are MLA_E_SHAPE.
+ * n_images = 1, image_w = frames gives the clipped spectrogram itself. */
+int mla_melspec_images(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
+                       float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, float* out, mla_stream_t stream);
+
 /* vggish.Postprocessor.postprocess (vggish.py:62-102): PCA, clamp to [-2, 2], 8-bit quantisation
  * (as float). embeddings (rows, 128), pca_eigen_vectors (128, 128), pca_means (128). */
 int mla_postprocess(const float* embeddings, const float* pca_eigen_vectors, const float* pca_means, int64_t rows,

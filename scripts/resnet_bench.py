@@ -3,7 +3,7 @@
 5 120 images, the frozen training step (TrainStep) at 8 and 64 bags, and -- as a yardstick only -- the same network built
 from torch.nn.functional.conv2d in channels-last bf16 (MIOpen). Prints one JSON line.
 
-    python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank [--finetune]] [--finetune]
+    python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank [--finetune]] [--finetune] [--from-waveforms]
 
 --per-conv: instead, each distinct bf16 conv (and the stem) timed alone at 80 images against its own roofline.
 --dp-one-rank: instead, the cost of the trunk's SyncBN on one GPU: the frozen bf16 step (eager) at 8 and 64 bags without a
@@ -17,6 +17,10 @@ session on one device; writes profiles/resnet_dp_finetune_one_rank.json. More th
 --finetune: instead, the trunk-finetuning step (cnn_trainable=True with the HIP trunk backward on, TrainStep, default graph
 mode) in bf16 and f32 at 8 and 64 bags next to the frozen bf16 step, and torch autograd's forward + backward of the restated
 ResNet-50 trunk (channels-last bf16, MIOpen, train mode) as the yardstick; writes profiles/resnet_finetune.json.
+--from-waveforms: instead, the mel-dB front-end's share of the eval forward from audio: Ensemble.forward_clips on (bags, 88 200)
+PCM against Ensemble.forward on the pre-made (bags, 10, 1, 224, 224) images, bf16 and f32 at 8 and 512 bags, the two timed
+alternately round by round in one session; and the two front-end kernels timed alone by device events, with the bytes and
+flops they need (counted from the shapes) over that time. Writes profiles/resnet_from_waveforms.json.
 """
 
 import importlib
@@ -265,6 +269,68 @@ def finetune(sd):
     print(json.dumps(res))
 
 
+def melspec_counts(bags, n=88200, hop=98, n_mels=224, n_images=10, width=224):
+    """Bytes each front-end kernel must move and the flops of kernel 1, from the shapes alone."""
+    frames = 1 + n // hop
+    nnz = 2050                                                        # non-zero mel weights at (22 050 Hz, 224 bands)
+    db_bytes = bags * (n * 4 + n_mels * frames * 4)                   # PCM in once, D out once
+    img_bytes = bags * (n_mels * frames * 4 + n_images * n_mels * width * 4)
+    # per frame: window 2048, five radix-4 stages of 256 butterflies (3 complex multiplies = 18 flops, 16 complex adds = 32 flops;
+    # the first stage has no multiplies), the split to 1025 powers (about 17 flops each), 2 flops per mel weight
+    flops = bags * frames * (2048 + 256 * (32 + 4 * 50) + 1025 * 17 + 2 * nnz)
+    return db_bytes, img_bytes, flops
+
+
+def from_waveforms(sd, quick):
+    DS = importlib.import_module(PKG + ".dataset")
+    OPS = importlib.import_module(PKG + ".ops")
+    dev = torch.device("cuda")
+    res = {"metric": "resnet50_from_waveforms", "device": torch.cuda.get_device_name(0), "rounds": 5}
+    for prec in ("bf16", "f32"):
+        ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision=prec)
+        ens.load_state_dict(sd)
+        ens.cuda().eval()
+        for bags in ((8,) if quick else (8, 512)):
+            pcm = torch.rand(bags, 88200, device=dev) - 0.5           # timing only: the seeded statistics do not fit dB inputs
+            iters = 3 if bags > 100 else 20
+            with torch.no_grad():
+                images = DS.clips_to_images(pcm)
+                t_img, t_wav = [], []
+                for _ in range(res["rounds"]):                         # alternate the two, so that drift hits both alike
+                    t_img.append(timeit(lambda: ens(images), 1, iters))
+                    t_wav.append(timeit(lambda: ens.forward_clips(pcm), 1, iters))
+            t_img, t_wav = sorted(t_img)[len(t_img) // 2], sorted(t_wav)[len(t_wav) // 2]
+            key = "%s_%d_bags" % (prec, bags)
+            res[key + "_forward_images_ms"] = round(t_img * 1e3, 3)
+            res[key + "_forward_clips_ms"] = round(t_wav * 1e3, 3)
+            res[key + "_front_end_share"] = round((t_wav - t_img) / t_wav, 4)
+        del ens
+    for bags in ((8,) if quick else (8, 512)):                         # the two kernels alone, by device events
+        pcm = torch.rand(bags, 88200, device=dev) - 0.5
+        DS.clips_to_images(pcm)
+        torch.cuda.synchronize()
+        OPS.reserve_events(4 * 20)
+        OPS.profile = []
+        for _ in range(20):
+            DS.clips_to_images(pcm)
+        torch.cuda.synchronize()
+        times = {}
+        for name, e0, e1 in OPS.profile:
+            times.setdefault(name, []).append(e0.elapsed_time(e1))
+        OPS.profile = None
+        db_bytes, img_bytes, flops = melspec_counts(bags)
+        t_db, t_im = (sorted(times[k])[len(times[k]) // 2] * 1e-3 for k in ("melspec_db", "melspec_images"))
+        res["kernels_%d_bags" % bags] = {
+            "melspec_db_us": round(t_db * 1e6, 1), "melspec_db_GB_per_s": round(db_bytes / t_db / 1e9, 1),
+            "melspec_db_GFLOP_per_s": round(flops / t_db / 1e9, 1),
+            "melspec_images_us": round(t_im * 1e6, 1), "melspec_images_GB_per_s": round(img_bytes / t_im / 1e9, 1)}
+    print(json.dumps(res))
+    out = os.path.join(ROOT, "profiles", "resnet_from_waveforms.json")
+    if not quick:
+        with open(out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+
+
 def main():
     quick = "--quick" in sys.argv
     dev = torch.device("cuda")
@@ -273,6 +339,8 @@ def main():
         return dp_finetune_one_rank(sd) if "--finetune" in sys.argv else dp_one_rank(sd)
     if "--finetune" in sys.argv:
         return finetune(sd)
+    if "--from-waveforms" in sys.argv:
+        return from_waveforms(sd, quick)
     if "--per-conv" in sys.argv:
         ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
         ens.load_state_dict(sd)
