@@ -122,6 +122,9 @@ def lib():
         L.mla_resample_length.restype = i64
         L.mla_resample_length.argtypes = [i64, cd, cd]
         L.mla_resample.argtypes = [vp, i64, cd, cd, vp, vp, ci, ci, vp, i64, vp]
+        L.mla_clips_lds_bytes.restype = i64
+        L.mla_clips_lds_bytes.argtypes = [vp, i64, cd, ci, ci]
+        L.mla_clips_prepare.argtypes = [vp, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cd, i64, vp, i64, ci, ci, vp, vp]
         u64 = ctypes.c_uint64
         L.mla_dropout_mask.argtypes = [vp, i64, u64, u64, u64, cf, vp]
         L.mla_dropout_mask_dev.argtypes = [vp, i64, u64, u64, vp, u64, cf, vp]

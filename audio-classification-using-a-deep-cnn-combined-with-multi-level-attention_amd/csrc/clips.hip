@@ -1,0 +1,148 @@
+// clips.hip -- recordings -> the ResNet branch's clips in ONE launch (reference: dataset.py:232-237, librosa.load(path, sr=22050)
+// = channel mean + resampy 'kaiser_best', then the cut at 4 s and the zero fill). Per-output arithmetic: resample_core.h.
+//
+// clips_kernel: a workgroup of 256 threads owns 256 consecutive outputs of one clip (grid = clips * ceil(samples_num / 256)).
+// It finds the input frames its outputs need (the positions of its first and last output, one filter wing to each side,
+// clamped to [0, n_in) of ITS clip: nothing outside the clip is read), mixes them to mono while staging them in LDS with
+// coalesced reads of the interleaved PCM, and every lane then runs its two wing loops on LDS: neighbouring lanes share all but
+// about 1 / ratio samples. The filter taps are gathered from the clip's table (L2-resident, 512 KB, (win, delta) pairs).
+// Workgroups past min(n_res, samples_num) only store zeros; a clip already at sr_out is copied (its mono mix), not filtered.
+// Every element of `out` is written: no memset precedes the launch.
+#include "common.h"
+#include "resample_core.h"
+
+namespace {
+
+using namespace resample_core;
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void clips_kernel(const T* __restrict__ packed, const int64_t* __restrict__ offsets,
+                                                         const int64_t* __restrict__ frames, const int* __restrict__ channels,
+                                                         const double* __restrict__ rates, const int* __restrict__ table_index,
+                                                         double sr_out, int samples_num, int tiles, const double* __restrict__ tables,
+                                                         int nwin, int num_table, int capacity, double pcm_scale,
+                                                         float* __restrict__ out) {
+    extern __shared__ float stage[];
+    const int64_t clip = blockIdx.x / tiles;
+    const int t0 = int(blockIdx.x - clip * tiles) * kThreads, t = t0 + int(threadIdx.x);
+    const int64_t n_in = frames[clip];
+    const int ch = channels[clip];
+    const double rate = rates[clip];
+    const T* src = packed + offsets[clip];
+    float* row = out + clip * samples_num;
+    if (rate == sr_out) {                                      // librosa does not resample an equal rate; the filter is no identity
+        if (t < samples_num) row[t] = t < n_in ? mono_mix(src + int64_t(t) * ch, ch, pcm_scale) : 0.f;
+        return;
+    }
+    const double ratio = sr_out / rate;
+    const int64_t n_res = resampled_length(n_in, ratio);
+    const int n_valid = n_res < samples_num ? int(n_res) : samples_num;
+    if (t0 >= n_valid) {                                       // uniform over the workgroup: no barrier is skipped by part of it
+        if (t < samples_num) row[t] = 0.f;
+        return;
+    }
+    const int index_step = index_step_of(ratio, num_table);
+    const int t_last = t0 + kThreads - 1 < n_valid - 1 ? t0 + kThreads - 1 : n_valid - 1;
+    int64_t first;
+    int count;
+    span(t0, t_last, ratio, wing_taps(nwin, index_step), n_in, &first, &count);
+    if (count > capacity) count = capacity;                    // never taken (span_capacity bounds it); keeps the stores inside LDS
+    stage_span(int(threadIdx.x), src, ch, pcm_scale, first, count, stage);
+    __syncthreads();
+    if (t >= samples_num) return;
+    float v = 0.f;
+    if (t < n_valid) {
+        const Setup s = setup(t, ratio, num_table);
+        v = float(wings(s, stage, first, n_in, tables + int64_t(table_index[clip]) * 2 * nwin, nwin, index_step));
+    }
+    row[t] = v;
+}
+
+// validates one clip's rate; *floats receives the LDS floats its workgroups stage (0 for an equal rate)
+int clip_lds_floats(int64_t i, double rate, double sr_out, int nwin, int num_table, int64_t* floats) {
+    MLA_REQUIRE(rate > 0.0, MLA_E_ARG, "clip %lld: rate %g is not positive", (long long)i, rate);
+    *floats = 0;
+    if (rate == sr_out) return MLA_OK;
+    const double ratio = sr_out / rate;
+    const int step = index_step_of(ratio, num_table);
+    MLA_REQUIRE(step >= 1, MLA_E_SHAPE, "clip %lld: ratio %g is below the filter table's resolution", (long long)i, ratio);
+    MLA_REQUIRE(rate <= double(kMaxRateFactor) * sr_out, MLA_E_SHAPE, "clip %lld: rate %g is above %d x the output rate %g", (long long)i,
+                rate, kMaxRateFactor, sr_out);
+    *floats = span_capacity(ratio, wing_taps(nwin, step));
+    return MLA_OK;
+}
+
+constexpr int64_t kMaxLdsBytes = 64 * 1024;
+
+}  // namespace
+
+extern "C" int64_t mla_clips_lds_bytes(const double* host_rates, int64_t clips, double sr_out, int nwin, int num_table) {
+    MLA_REQUIRE(clips >= 0 && sr_out > 0.0 && nwin > 1 && num_table > 0, MLA_E_ARG, "bad clips arguments (clips %lld, sr_out %g, nwin %d, num_table %d)",
+                (long long)clips, sr_out, nwin, num_table);
+    MLA_REQUIRE(host_rates || clips == 0, MLA_E_ARG, "null host_rates");
+    int64_t most = 0;
+    for (int64_t i = 0; i < clips; ++i) {
+        int64_t f;
+        if (int rc = clip_lds_floats(i, host_rates[i], sr_out, nwin, num_table, &f)) return rc;
+        most = f > most ? f : most;
+    }
+    MLA_REQUIRE(most * 4 <= kMaxLdsBytes, MLA_E_SHAPE, "a workgroup would stage %lld floats, more than %lld bytes of LDS", (long long)most,
+                (long long)kMaxLdsBytes);
+    return most * int64_t(sizeof(float));
+}
+
+extern "C" int mla_clips_prepare(const void* packed, int pcm_dtype, int64_t packed_elems, int64_t clips, const int64_t* offsets,
+                                 const int64_t* frames, const int32_t* channels, const double* rates, const int32_t* table_index,
+                                 const int64_t* host_offsets, const int64_t* host_frames, const int32_t* host_channels,
+                                 const double* host_rates, const int32_t* host_table_index, double sr_out, int64_t samples_num,
+                                 const double* tables, int64_t n_tables, int nwin, int num_table, float* out, mla_stream_t stream) {
+    MLA_REQUIRE(clips >= 0 && samples_num >= 0 && packed_elems >= 0 && n_tables >= 0, MLA_E_ARG,
+                "negative size (clips %lld, samples_num %lld, packed_elems %lld, n_tables %lld)", (long long)clips, (long long)samples_num,
+                (long long)packed_elems, (long long)n_tables);
+    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_ARG, "pcm_dtype %d is neither MLA_F32 nor MLA_I16", pcm_dtype);
+    MLA_REQUIRE(sr_out > 0.0, MLA_E_ARG, "sr_out %g is not positive", sr_out);
+    MLA_REQUIRE(nwin > 1 && num_table > 0, MLA_E_ARG, "bad filter table (nwin %d, num_table %d)", nwin, num_table);
+    if (clips == 0) return MLA_OK;
+    MLA_REQUIRE(host_offsets && host_frames && host_channels && host_rates && host_table_index, MLA_E_ARG, "null host descriptor");
+    MLA_REQUIRE(offsets && frames && channels && rates && table_index, MLA_E_ARG, "null device descriptor");
+    MLA_REQUIRE(out || samples_num == 0, MLA_E_ARG, "null out");
+    MLA_REQUIRE(samples_num <= 0x7fffffffll - kThreads, MLA_E_SHAPE, "samples_num %lld is too large", (long long)samples_num);
+    int64_t most = 0;
+    for (int64_t i = 0; i < clips; ++i) {
+        const int64_t n = host_frames[i], off = host_offsets[i];
+        MLA_REQUIRE(n >= 0 && host_channels[i] >= 1, MLA_E_ARG, "clip %lld: %lld frames of %d channels", (long long)i, (long long)n,
+                    int(host_channels[i]));
+        int64_t f;
+        if (int rc = clip_lds_floats(i, host_rates[i], sr_out, nwin, num_table, &f)) return rc;
+        most = f > most ? f : most;
+        MLA_REQUIRE(n <= (int64_t(1) << 40) / host_channels[i], MLA_E_SHAPE, "clip %lld is too long (%lld frames)", (long long)i, (long long)n);
+        MLA_REQUIRE(off >= 0 && off <= packed_elems && n * host_channels[i] <= packed_elems - off, MLA_E_ARG,
+                    "clip %lld: elements [%lld, %lld) leave the packed buffer of %lld", (long long)i, (long long)off,
+                    (long long)(off + n * host_channels[i]), (long long)packed_elems);
+        if (f > 0) {
+            MLA_REQUIRE(host_table_index[i] >= 0 && host_table_index[i] < n_tables, MLA_E_ARG, "clip %lld: table %d of %lld", (long long)i,
+                        int(host_table_index[i]), (long long)n_tables);
+            MLA_REQUIRE(resampled_length(n, sr_out / host_rates[i]) >= 1, MLA_E_SHORT,
+                        "clip %lld: input of %lld samples is too short to resample from %g to %g Hz", (long long)i, (long long)n, host_rates[i], sr_out);
+        }
+    }
+    MLA_REQUIRE(most * 4 <= kMaxLdsBytes, MLA_E_SHAPE, "a workgroup would stage %lld floats, more than %lld bytes of LDS", (long long)most,
+                (long long)kMaxLdsBytes);
+    if (samples_num == 0) return MLA_OK;
+    MLA_REQUIRE(packed || packed_elems == 0, MLA_E_ARG, "null packed buffer");
+    MLA_REQUIRE(tables || most == 0, MLA_E_ARG, "null filter tables");
+    const int64_t tiles = (samples_num + kThreads - 1) / kThreads;
+    MLA_REQUIRE(clips * tiles <= 0x7fffffffll, MLA_E_SHAPE, "clips grid of %lld workgroups is too large", (long long)(clips * tiles));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid{unsigned(clips * tiles)}, block{unsigned(kThreads)};
+    const size_t lds = size_t(most) * sizeof(float);
+    if (pcm_dtype == MLA_F32) {
+        hipLaunchKernelGGL(clips_kernel<float>, grid, block, lds, s, static_cast<const float*>(packed), offsets, frames, channels, rates,
+                           table_index, sr_out, int(samples_num), int(tiles), tables, nwin, num_table, int(most), 1.0, out);
+    } else {
+        hipLaunchKernelGGL(clips_kernel<int16_t>, grid, block, lds, s, static_cast<const int16_t*>(packed), offsets, frames, channels, rates,
+                           table_index, sr_out, int(samples_num), int(tiles), tables, nwin, num_table, int(most), 1.0 / 32768.0, out);
+    }
+    MLA_LAUNCH_OK("clips_kernel");
+    return MLA_OK;
+}

@@ -1,0 +1,124 @@
+// resample_core.h -- per-output arithmetic of the batched "recordings -> clips" kernel (csrc/clips.hip): the mono mix of
+// mla_mono_mix and the band-limited sinc interpolation of resample_kernel (csrc/stft_generic.hip; resampy/interpn.py,
+// filter 'kaiser_best'), written so that the SAME source runs (a) inside clips.hip on gfx950 and (b) on the host,
+// workgroup by workgroup, in csrc/clips_hostsim.cpp (built with g++ by the CPU tests) with a plain array standing in for LDS.
+//
+// Output sample t of a clip resampled by ratio = sr_out / sr_in sits at input time t / ratio:
+//   position   n = int(t * (1 / ratio)), the fractional part scaled to table entries gives (offset, eta) of each wing
+//   wings      left  wing: sum_i (win[off_l + i * step] + eta_l * delta[..]) * mono[n - i],      i < min(n + 1, (nwin - off_l) / step)
+//              right wing: sum_k (win[off_r + k * step] + eta_r * delta[..]) * mono[n + k + 1],  k < min(n_in - n - 1, (nwin - off_r) / step)
+//              one double accumulator, left wing first, one rounding to float32 by the caller
+//   mono_mix   mean over the channels of one frame in double, times the PCM scale, rounded once
+//
+// BIT-IDENTITY with resample_kernel. That kernel is compiled with the device compiler's default floating-point contraction,
+// which fuses exactly three of its expressions: t * inv - n, win + eta * delta and acc + w * x. Here contraction is switched
+// off and those three are spelled fma(), so that the bits do not depend on what a compiler decides for this translation unit;
+// the host build (g++ -ffp-contract=off, correctly rounded fma from libm) then computes the same values as the device.
+// tests/test_clips_gpu.py compares the two kernels with torch.equal.
+//
+// The filter table is read as (win, delta) PAIRS, tab[2 * idx] and tab[2 * idx + 1]: one 16-byte gather per tap.
+#ifndef MLA_RESAMPLE_CORE_H
+#define MLA_RESAMPLE_CORE_H
+
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define MLA_RS_HD __host__ __device__ __forceinline__
+#else
+#define MLA_RS_HD inline
+#endif
+#if defined(__clang__)
+#define MLA_RS_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define MLA_RS_NO_CONTRACT
+#endif
+
+namespace resample_core {
+
+constexpr int kThreads = 256;              // outputs per workgroup
+constexpr int kMaxRateFactor = 16;         // input rates up to 16 * sr_out are staged; faster ones are refused
+
+MLA_RS_HD double scale_of(double ratio) { return ratio < 1.0 ? ratio : 1.0; }
+MLA_RS_HD int index_step_of(double ratio, int num_table) { return int(scale_of(ratio) * num_table); }
+// most taps a wing can have: (nwin - offset) / index_step with offset >= 0
+MLA_RS_HD int wing_taps(int nwin, int index_step) { return nwin / index_step; }
+MLA_RS_HD int64_t resampled_length(int64_t n_in, double ratio) { return int64_t(double(n_in) * ratio); }
+
+struct Setup {
+    int64_t n;                 // input sample at or left of the output's position
+    int off_l, off_r;          // first table entry of each wing
+    double eta_l, eta_r;       // its distance to the next entry, in entries
+};
+
+// input sample left of output t: monotone in t, so a workgroup's first and last outputs bound its span
+MLA_RS_HD int64_t position(int64_t t, double ratio) {
+    MLA_RS_NO_CONTRACT
+    return int64_t(double(t) * (1.0 / ratio));
+}
+
+MLA_RS_HD Setup setup(int64_t t, double ratio, int num_table) {
+    MLA_RS_NO_CONTRACT
+    Setup s;
+    const double scale = scale_of(ratio), inv = 1.0 / ratio, nt = double(num_table);
+    s.n = int64_t(double(t) * inv);
+    const double frac_l = scale * fma(inv, double(t), -double(s.n));
+    const double if_l = frac_l * nt;
+    s.off_l = int(if_l);
+    s.eta_l = if_l - double(s.off_l);
+    const double frac_r = scale - frac_l;
+    const double if_r = frac_r * nt;
+    s.off_r = int(if_r);
+    s.eta_r = if_r - double(s.off_r);
+    return s;
+}
+
+// x[j - x0] is mono[j] for every j the wings touch: [max(0, n - taps + 1), min(n_in - 1, n + taps)]
+MLA_RS_HD double wings(const Setup& s, const float* x, int64_t x0, int64_t n_in, const double* tab, int nwin, int index_step) {
+    MLA_RS_NO_CONTRACT
+    double acc = 0.0;
+    const float* xc = x + (s.n - x0);
+    int64_t i_max = (nwin - s.off_l) / index_step;
+    if (s.n + 1 < i_max) i_max = s.n + 1;
+    for (int i = 0; i < int(i_max); ++i) {
+        const int idx = s.off_l + i * index_step;
+        acc = fma(fma(s.eta_l, tab[2 * idx + 1], tab[2 * idx]), double(xc[-i]), acc);
+    }
+    int64_t k_max = (nwin - s.off_r) / index_step;
+    if (n_in - s.n - 1 < k_max) k_max = n_in - s.n - 1;
+    for (int k = 0; k < int(k_max); ++k) {
+        const int idx = s.off_r + k * index_step;
+        acc = fma(fma(s.eta_r, tab[2 * idx + 1], tab[2 * idx]), double(xc[k + 1]), acc);
+    }
+    return acc;
+}
+
+// one frame of interleaved PCM -> mono float32 (mla_mono_mix's arithmetic; scale 1/32768 for int16, 1 for float32)
+template <typename T>
+MLA_RS_HD float mono_mix(const T* frame, int channels, double scale) {
+    MLA_RS_NO_CONTRACT
+    double acc = 0.0;
+    for (int c = 0; c < channels; ++c) acc += double(frame[c]);
+    return float(acc / double(channels) * scale);
+}
+
+// Input frames [*first, *first + count) that outputs t_first..t_last of a clip need, clamped to the clip.
+MLA_RS_HD void span(int64_t t_first, int64_t t_last, double ratio, int taps, int64_t n_in, int64_t* first, int* count) {
+    const int64_t lo = position(t_first, ratio) - taps + 1, hi = position(t_last, ratio) + taps;
+    const int64_t a = lo < 0 ? 0 : lo, b = hi > n_in - 1 ? n_in - 1 : hi;
+    *first = a;
+    *count = b >= a ? int(b - a + 1) : 0;
+}
+
+// Upper bound of span()'s count for any 256 consecutive outputs: the positions of the first and the last are at most
+// 255 / ratio + 1 apart (+ 2 for the roundings of 1 / ratio and of the product).
+MLA_RS_HD int64_t span_capacity(double ratio, int taps) { return int64_t(double(kThreads - 1) / ratio) + 3 + 2 * int64_t(taps); }
+
+// thread `lane` of the workgroup: mono-mix frames first + lane, first + lane + 256, ... into stage[0 .. count)
+template <typename T>
+MLA_RS_HD void stage_span(int lane, const T* clip, int channels, double scale, int64_t first, int count, float* stage) {
+    for (int i = lane; i < count; i += kThreads) stage[i] = mono_mix(clip + (first + i) * channels, channels, scale);
+}
+
+}  // namespace resample_core
+#endif

@@ -93,3 +93,72 @@ def clips_to_images(pcm, overlap=True):
     step = (width - x_size) // (T - 1) if overlap else x_size
     db, ws = frontend.melspec_db_unclipped(pcm, SR_RESNET, y_size, hop)
     return frontend.melspec_images(db, ws, SAMPLES_NUM_RESNET, hop, 80.0, T, x_size, step)
+
+
+def _host_recording(x, index):
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[1] < 1):
+        raise ValueError("recording %d: expected (n,) or (n, channels), got shape %r" % (index, tuple(x.shape)))
+    if x.dtype != np.int16:
+        if not np.issubdtype(x.dtype, np.floating):
+            raise TypeError("recording %d: int16 or floating samples expected, got %s" % (index, x.dtype))
+        x = x.astype(np.float32, copy=False)               # float64 is rounded once, as frontend.as_device_mono does
+    return x
+
+
+def recordings_to_clips(recordings, rates, sr=SR_RESNET, samples_num=SAMPLES_NUM_RESNET):
+    """Recordings as they are decoded -> the (B, samples_num) float32 device tensor clips_to_images and Ensemble.forward_clips
+    take: librosa.load(path, sr=sr) (channel mean, resampy 'kaiser_best'; no resampling at an equal rate), the cut at
+    samples_num and the zero fill of dataset.py:232-237, for the whole batch in one launch (frontend.prepare_clips).
+
+    recordings: a sequence of host arrays or tensors, each (n,) or (n, channels) with interleaved channels as `wave` and
+    `soundfile` deliver them; all int16 (scaled by 1/32768) or all floating. rates: one rate in Hz per recording, or one number.
+    The WHOLE recording is resampled and the cut comes afterwards, as in the reference. The samples travel through one packed
+    pinned host buffer and one copy, the descriptors through another. ValueError (naming the recording) where resampy raises,
+    before anything is copied or launched. An empty sequence gives a (0, samples_num) tensor."""
+    recs = [_host_recording(x, i) for i, x in enumerate(recordings)]
+    B = len(recs)
+    rates = [rates] * B if np.isscalar(rates) else list(rates)
+    if len(rates) != B:
+        raise ValueError("%d recordings but %d rates" % (B, len(rates)))
+    if sr <= 0:
+        raise ValueError("Invalid sample rate: sr_new=%r" % (sr,))
+    if len({x.dtype == np.int16 for x in recs}) > 1:
+        raise TypeError("recordings must be all int16 or all floating, not a mixture")
+    for i, (x, r) in enumerate(zip(recs, rates)):
+        if r <= 0:
+            raise ValueError("recording %d: Invalid sample rate: sr_orig=%r" % (i, r))
+        if float(r) != float(sr) and int(x.shape[0] * (float(sr) / float(r))) < 1:
+            raise ValueError("recording %d: Input signal length=%d is too small to resample from %s->%s" % (i, x.shape[0], r, sr))
+    if B == 0:
+        return torch.empty((0, int(samples_num)), dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu")
+    dev = frontend._device()
+    frames = np.array([x.shape[0] for x in recs], dtype=np.int64)
+    channels = np.array([1 if x.ndim == 1 else x.shape[1] for x in recs], dtype=np.int32)
+    sizes = frames * channels
+    offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    host = torch.empty(int(sizes.sum()), dtype=torch.int16 if recs[0].dtype == np.int16 else torch.float32, pin_memory=True)
+    flat = host.numpy()
+    for x, o, s in zip(recs, offsets, sizes):
+        flat[o:o + s] = x.reshape(-1)
+    return frontend.prepare_clips(host.to(dev, non_blocking=True), offsets, frames, channels, np.array(rates, dtype=np.float64), sr,
+                                  samples_num)
+
+
+def read_wav16(path):
+    """16-bit RIFF file -> ((frames,) or (frames, channels) int16 array, rate), with the stdlib `wave` module and the refusal of
+    vggish_input.wavfile_to_examples for any other sample width."""
+    import wave
+    with wave.open(path, "rb") as wf:
+        assert wf.getsampwidth() == 2, "Bad sample type: %r" % wf.getsampwidth()
+        sr, ch = wf.getframerate(), wf.getnchannels()
+        pcm = np.frombuffer(wf.readframes(wf.getnframes()), dtype=np.int16)
+    return (pcm.reshape(-1, ch) if ch > 1 else pcm), sr
+
+
+def wavfiles_to_clips(paths, sr=SR_RESNET, samples_num=SAMPLES_NUM_RESNET):
+    """16-bit WAV files -> (B, samples_num) clips: read_wav16 on every path, then recordings_to_clips."""
+    decoded = [read_wav16(str(p)) for p in paths]
+    return recordings_to_clips([d[0] for d in decoded], [d[1] for d in decoded], sr, samples_num)

@@ -86,6 +86,25 @@ def kaiser_best_filter():
     return np.kaiser(2 * n + 1, beta)[n:] * sinc_win, num_bits
 
 
+_resample_filters = {}
+
+
+def _resample_filter(ratio, gain=1.0):
+    """The interpolation filter as the kernels read it, on the host in float64: 'kaiser_best' scaled by the ratio where it is < 1
+    (resampy/core.py) and by `gain`, its first difference, entries per zero crossing. One per distinct (scale, gain): `resample`
+    and `prepare_clips` upload the SAME values, which is what makes their outputs agree bit for bit."""
+    key = (ratio if ratio < 1 else 1.0, float(gain))
+    if key not in _resample_filters:
+        win, num_table = kaiser_best_filter()
+        if ratio < 1:
+            win = win * ratio
+        win = win * float(gain)
+        delta = np.zeros_like(win)
+        delta[:-1] = np.diff(win)
+        _resample_filters[key] = (win, delta, num_table)
+    return _resample_filters[key]
+
+
 def resample(wave, sr_orig, sr_new, gain=1.0):
     """resampy.resample(wave, sr_orig, sr_new) (vggish_input.py:52-53) for a 1-D device waveform -> float32 device tensor of
     int(n * sr_new / sr_orig) samples, by the HIP kernel mla_resample (`gain` scales the filter table: the operation is linear).
@@ -103,18 +122,94 @@ def resample(wave, sr_orig, sr_new, gain=1.0):
         raise ValueError("Input signal length=%d is too small to resample from %s->%s" % (wave.shape[0], sr_orig, sr_new))
     key = (str(wave.device), ratio if ratio < 1 else 1.0, float(gain))
     if key not in _resample_tables:
-        win, num_table = kaiser_best_filter()
-        if ratio < 1:
-            win = win * ratio
-        win = win * float(gain)
-        delta = np.zeros_like(win)
-        delta[:-1] = np.diff(win)
+        win, delta, num_table = _resample_filter(ratio, gain)
         _resample_tables[key] = (torch.from_numpy(win).to(wave.device), torch.from_numpy(delta).to(wave.device), num_table)
     win, delta, num_table = _resample_tables[key]
     out = torch.empty(n_out, dtype=torch.float32, device=wave.device)
     vp = ctypes.c_void_p
     _lib.check(L.mla_resample(vp(wave.data_ptr()), wave.shape[0], float(sr_orig), float(sr_new), vp(win.data_ptr()), vp(delta.data_ptr()),
                               win.shape[0], num_table, vp(out.data_ptr()), n_out, _lib.stream_ptr()))
+    return out
+
+
+_clips_tables = {}
+
+
+def _host_array(a, dtype):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()           # a device tensor is read back (one synchronisation); host arrays cost nothing
+    return np.ascontiguousarray(np.asarray(a), dtype=dtype).reshape(-1)
+
+
+def clips_table_index(rates, sr_out):
+    """(the distinct filter scales of a batch in order of first use, each recording's index into them). A recording at sr_out
+    is not filtered and keeps index 0; a rate <= 0 is left for the library to refuse."""
+    scales, tab = [], np.zeros(len(rates), dtype=np.int32)
+    for i, r in enumerate(rates):
+        if r > 0 and r != sr_out:
+            ratio = float(sr_out) / float(r)
+            key = ratio if ratio < 1 else 1.0
+            if key not in scales:
+                scales.append(key)
+            tab[i] = scales.index(key)
+    return tuple(scales), tab
+
+
+def clips_tables_host(scales):
+    """The filter tables of `scales` back to back as mla_clips_prepare reads them: per table nwin (win, delta) pairs, float64."""
+    if not scales:
+        return np.zeros(0, dtype=np.float64)
+    return np.concatenate([np.stack(_resample_filter(k)[:2], axis=1).reshape(-1) for k in scales])
+
+
+def prepare_clips(packed, offsets, frames, channels, rates, sr_out, samples_num, out=None):
+    """A batch of ragged recordings -> (B, samples_num) float32 clips at `sr_out` in ONE launch of csrc/clips.hip: channel mean,
+    resampy 'kaiser_best' resampling of the whole recording (a copy where the rate already is sr_out), cut at samples_num and
+    zero fill -- librosa.load(path, sr=sr_out) followed by dataset.py:233-237 of the reference.
+
+    packed: 1-D device tensor, int16 (scaled by 1/32768) or float32, the recordings' interleaved frames back to back.
+    offsets / frames / channels / rates: per recording, the element index of its first sample in `packed`, its frames, its
+    channel count and its rate in Hz. They are needed on BOTH sides (the library validates and sizes LDS on the host, the
+    kernel reads them on the device): pass host arrays where you have them (dataset.recordings_to_clips does); device tensors
+    are read back first. They travel to the device in one pinned buffer and one copy. Every row depends on its own recording
+    only and equals `resample(as_device_mono(x), rate, sr_out)` cut and zero-filled, bit for bit. `out`, when given, is
+    overwritten completely."""
+    assert packed.is_cuda and packed.dim() == 1 and packed.is_contiguous() and packed.dtype in (torch.int16, torch.float32)
+    dev = packed.device
+    off, fr = _host_array(offsets, np.int64), _host_array(frames, np.int64)
+    ch, rt = _host_array(channels, np.int32), _host_array(rates, np.float64)
+    B = fr.shape[0]
+    assert off.shape[0] == B and ch.shape[0] == B and rt.shape[0] == B, "one descriptor entry per recording"
+    sr_out, samples_num = float(sr_out), int(samples_num)
+    if out is None:
+        out = torch.empty((B, samples_num), dtype=torch.float32, device=dev)
+    else:
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, samples_num)
+    if B == 0:
+        return out
+    scales, tab = clips_table_index(rt, sr_out)
+    nwin, num_table = _resample_filter(1.0)[0].shape[0], _resample_filter(1.0)[2]
+    tkey = (str(dev), scales)
+    if tkey not in _clips_tables:
+        _clips_tables[tkey] = torch.from_numpy(clips_tables_host(scales)).to(dev)
+    tables = _clips_tables[tkey]
+    desc = torch.empty(B * 32, dtype=torch.uint8, pin_memory=True)       # offsets | frames | rates | channels | table index
+    h = desc.numpy()
+    h[:8 * B].view(np.int64)[:] = off
+    h[8 * B:16 * B].view(np.int64)[:] = fr
+    h[16 * B:24 * B].view(np.float64)[:] = rt
+    h[24 * B:28 * B].view(np.int32)[:] = ch
+    h[28 * B:].view(np.int32)[:] = tab
+    d = desc.to(dev, non_blocking=True)
+    vp = ctypes.c_void_p
+    base = d.data_ptr()
+    hp = lambda a: a.ctypes.data_as(vp)
+    code = _lib.I16 if packed.dtype == torch.int16 else _lib.F32
+    from . import ops
+    _lib.check(ops._timed("clips_prepare", _lib.lib().mla_clips_prepare, vp(packed.data_ptr()), code, packed.shape[0], B,
+                          vp(base), vp(base + 8 * B), vp(base + 24 * B), vp(base + 16 * B), vp(base + 28 * B),
+                          hp(off), hp(fr), hp(ch), hp(rt), hp(tab), sr_out, samples_num,
+                          vp(tables.data_ptr()) if scales else None, len(scales), nwin, num_table, vp(out.data_ptr()), _lib.stream_ptr()))
     return out
 
 

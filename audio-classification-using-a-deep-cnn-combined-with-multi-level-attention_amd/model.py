@@ -139,6 +139,26 @@ class Ensemble(nn.Module):
         from . import dataset
         return self.forward(dataset.clips_to_images(pcm, overlap))
 
+    def _recordings_only_resnet(self, what):
+        if self.cnn_type != "resnet":
+            raise NotImplementedError("%s cuts and zero-fills 4 s clips for the ResNet branch; cnn_type 'vggish' does not zero-fill "
+                                      "the waveform (its native path pads missing 0.96 s slots of the spectrogram with 0.0) and "
+                                      "takes 16 kHz PCM through forward_waveforms()" % what)
+
+    def forward_recordings(self, recordings, rates, overlap=True):
+        """The ResNet branch from recordings as they are decoded: a sequence of host arrays, (n,) or (n, channels), int16 or
+        floating, of any rates and lengths -> dataset.recordings_to_clips (one HIP launch: channel mean, resampling to 22 050 Hz,
+        cut at 4 s, zero fill) -> forward_clips() -> (B, K) scores."""
+        self._recordings_only_resnet("forward_recordings")
+        from . import dataset
+        return self.forward_clips(dataset.recordings_to_clips(recordings, rates), overlap)
+
+    def forward_wavfiles(self, paths, overlap=True):
+        """forward_recordings for 16-bit WAV files (dataset.wavfiles_to_clips)."""
+        self._recordings_only_resnet("forward_wavfiles")
+        from . import dataset
+        return self.forward_clips(dataset.wavfiles_to_clips(paths), overlap)
+
     def stream_waveforms(self, host_batches):
         """Host-resident PCM: iterate over (B, n_samples) float32 / int16 tensors in PINNED host memory and yield the
         (B, K) scores of each. The copy of batch i+1 runs on its own HIP stream while batch i computes (two device

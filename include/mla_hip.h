@@ -410,6 +410,32 @@ int64_t mla_resample_length(int64_t n_in, double sr_in, double sr_out);
 int mla_resample(const float* x, int64_t n_in, double sr_in, double sr_out, const double* win, const double* delta, int nwin,
                  int num_table, float* y, int64_t n_out, mla_stream_t stream);
 
+/* ---- recordings -> the ResNet branch's clips (dataset.py:232-237: librosa.load(path, sr=22050), cut at 4 s, zero fill) ----
+ * ONE launch turns a batch of ragged recordings of any rate and channel count into out[clips][samples_num] float32 at sr_out.
+ * packed: DEVICE buffer of packed_elems int16 or float32 elements (pcm_dtype MLA_I16: scaled by 1/32768; MLA_F32), the
+ * recordings' interleaved frames back to back (gaps are allowed and never read). Per-clip descriptors, DEVICE arrays of
+ * `clips` entries: offsets (element index of the clip's first sample), frames, channels (>= 1), rates (Hz), table_index.
+ * The host_* arrays are HOST copies of the same values: every error is decided from them before any launch, and the
+ * dynamic LDS is sized from their largest rate.
+ *   mono[j] = float(mean over channels in double * scale)                       (mla_mono_mix's arithmetic)
+ *   rate == sr_out: out[c][t] = mono[t], t < min(frames, samples_num)           (a copy: the filter is no identity)
+ *   otherwise: ratio = sr_out / rate, out[c][t] = resample(mono)[t], t < min(int(frames * ratio), samples_num), bit for bit
+ *   what mla_resample computes for the WHOLE recording (the cut comes after the filter); every other element is 0.0f.
+ * Every element of out is written. tables: DEVICE, n_tables filter tables back to back, each nwin (win, delta) PAIRS of
+ * doubles (win already scaled by the ratio where it is < 1, as for mla_resample); table_index selects a clip's table and is
+ * ignored for clips at sr_out. MLA_E_ARG: null pointer with clips > 0, negative size, channels < 1, rate <= 0, unknown
+ * pcm_dtype, a clip that leaves the packed buffer, a table index outside [0, n_tables). MLA_E_SHAPE: a rate above
+ * 16 * sr_out (a workgroup stages its input span in LDS), a ratio below the table's resolution (int(ratio * num_table) < 1).
+ * MLA_E_SHORT: int(frames * ratio) < 1 (resampy raises ValueError). clips == 0 returns MLA_OK and touches nothing.
+ * mla_clips_lds_bytes: the dynamic LDS the launch takes for these rates (host; a negative MLA_E_* code for the rate errors
+ * above). */
+int64_t mla_clips_lds_bytes(const double* host_rates, int64_t clips, double sr_out, int nwin, int num_table);
+int mla_clips_prepare(const void* packed, int pcm_dtype, int64_t packed_elems, int64_t clips, const int64_t* offsets,
+                      const int64_t* frames, const int32_t* channels, const double* rates, const int32_t* table_index,
+                      const int64_t* host_offsets, const int64_t* host_frames, const int32_t* host_channels,
+                      const double* host_rates, const int32_t* host_table_index, double sr_out, int64_t samples_num,
+                      const double* tables, int64_t n_tables, int nwin, int num_table, float* out, mla_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Data-parallel exchange (the reference is single-process, train.py:119-142: these entry
  * points are what makes its step run sharded over the GPUs of a node) and the dropout masks of the step.

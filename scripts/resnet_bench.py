@@ -4,6 +4,7 @@
 from torch.nn.functional.conv2d in channels-last bf16 (MIOpen). Prints one JSON line.
 
     python scripts/resnet_bench.py [--quick] [--per-conv] [--dp-one-rank [--finetune]] [--finetune] [--from-waveforms]
+                                   [--from-recordings]
 
 --per-conv: instead, each distinct bf16 conv (and the stem) timed alone at 80 images against its own roofline.
 --dp-one-rank: instead, the cost of the trunk's SyncBN on one GPU: the frozen bf16 step (eager) at 8 and 64 bags without a
@@ -21,6 +22,11 @@ ResNet-50 trunk (channels-last bf16, MIOpen, train mode) as the yardstick; write
 PCM against Ensemble.forward on the pre-made (bags, 10, 1, 224, 224) images, bf16 and f32 at 8 and 512 bags, the two timed
 alternately round by round in one session; and the two front-end kernels timed alone by device events, with the bytes and
 flops they need (counted from the shapes) over that time. Writes profiles/resnet_from_waveforms.json.
+--from-recordings: instead, the step from decoded recordings to clips, on 4 s stereo int16 recordings at 44.1 kHz in host memory, bf16,
+at 8 and 512 bags: Ensemble.forward_recordings, Ensemble.forward_clips on the ready clips, dataset.recordings_to_clips alone (host
+packing, two copies, one launch), and the per-recording loop it replaces (frontend.as_device_mono(pcm16=True) -> frontend.resample ->
+cut and zero fill, four launches per recording), medians of five rounds in which the four alternate; and the clips kernel alone by
+device events with the bytes and flops it needs (counted from the shapes). Writes profiles/resnet_from_recordings.json.
 """
 
 import importlib
@@ -331,6 +337,67 @@ def from_waveforms(sd, quick):
             f.write(json.dumps(res) + "\n")
 
 
+def from_recordings(sd, quick):
+    import numpy as np
+    DS = importlib.import_module(PKG + ".dataset")
+    FE = importlib.import_module(PKG + ".frontend")
+    OPS = importlib.import_module(PKG + ".ops")
+    dev = torch.device("cuda")
+    sr_in, n_in, n_out = 44100, 176400, 88200
+    res = {"metric": "resnet50_from_recordings", "device": torch.cuda.get_device_name(0), "rounds": 5, "precision": "bf16",
+           "recordings": "4 s stereo int16 at 44.1 kHz, host memory"}
+    ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
+    ens.load_state_dict(sd)
+    ens.cuda().eval()
+    rng = np.random.default_rng(0)
+    pool = [rng.integers(-16000, 16001, size=(n_in, 2)).astype(np.int16) for _ in range(8)]
+
+    def loop(recs):
+        """Today's calls, once per recording: mono mix (scaled), resampling, slice, copy into zeros."""
+        out = torch.zeros((len(recs), n_out), dtype=torch.float32, device=dev)
+        for i, x in enumerate(recs):
+            y = FE.resample(FE.as_device_mono(x, pcm16=True), sr_in, 22050)
+            k = min(y.shape[0], n_out)
+            out[i, :k] = y[:k]
+        return out
+
+    for bags in ((8,) if quick else (8, 512)):
+        recs = [pool[i % len(pool)] for i in range(bags)]
+        iters = 3 if bags > 100 else 20
+        with torch.no_grad():
+            clips = DS.recordings_to_clips(recs, sr_in)
+            res["%d_bags_batched_equals_loop" % bags] = bool(torch.equal(clips, loop(recs)))
+            t = {"forward_recordings": [], "forward_clips": [], "recordings_to_clips": [], "per_recording_loop": []}
+            for _ in range(res["rounds"]):                             # alternate, so that drift hits all alike
+                t["forward_recordings"].append(timeit(lambda: ens.forward_recordings(recs, sr_in), 1, iters))
+                t["forward_clips"].append(timeit(lambda: ens.forward_clips(clips), 1, iters))
+                t["recordings_to_clips"].append(timeit(lambda: DS.recordings_to_clips(recs, sr_in), 1, iters))
+                t["per_recording_loop"].append(timeit(lambda: loop(recs), 1, iters))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        for k, v in med.items():
+            res["%d_bags_%s_ms" % (bags, k)] = round(v * 1e3, 3)
+        res["%d_bags_step_share_of_forward_recordings" % bags] = round(med["recordings_to_clips"] / med["forward_recordings"], 4)
+        res["%d_bags_loop_over_batched" % bags] = round(med["per_recording_loop"] / med["recordings_to_clips"], 2)
+        # the kernel alone, by device events
+        OPS.reserve_events(2 * 20)
+        OPS.profile = []
+        for _ in range(20):
+            DS.recordings_to_clips(recs, sr_in)
+        torch.cuda.synchronize()
+        us = sorted(e0.elapsed_time(e1) * 1e3 for name, e0, e1 in OPS.profile if name == "clips_prepare")
+        OPS.profile = None
+        t_k = us[len(us) // 2] * 1e-6
+        byts = bags * (n_in * 2 * 2 + n_out * 4)                       # PCM in once, clips out once (the 512 KB table stays in L2)
+        flops = bags * n_out * (2 * 128 * 4 + 3)                       # two wings of 128 taps, two double fma each; the mix is staged
+        res["%d_bags_clips_kernel_us" % bags] = round(t_k * 1e6, 1)
+        res["%d_bags_clips_kernel_GB_per_s" % bags] = round(byts / t_k / 1e9, 1)
+        res["%d_bags_clips_kernel_GFLOP_per_s_f64" % bags] = round(flops / t_k / 1e9, 1)
+    print(json.dumps(res))
+    if not quick:
+        with open(os.path.join(ROOT, "profiles", "resnet_from_recordings.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+
+
 def main():
     quick = "--quick" in sys.argv
     dev = torch.device("cuda")
@@ -341,6 +408,8 @@ def main():
         return finetune(sd)
     if "--from-waveforms" in sys.argv:
         return from_waveforms(sd, quick)
+    if "--from-recordings" in sys.argv:
+        return from_recordings(sd, quick)
     if "--per-conv" in sys.argv:
         ens = M.Ensemble("repeat", CONF, [2, 1], dev, precision="bf16")
         ens.load_state_dict(sd)
