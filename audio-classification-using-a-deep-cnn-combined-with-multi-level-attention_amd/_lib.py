@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MLA_HIP_LIB") or os.path.join(HERE, "libmla_hip.so")   # MLA_HIP_LIB: an alternative build (A/B measurements)
 HEADER = os.path.join(os.path.dirname(HERE), "include", "mla_hip.h")
 
-F32, BF16, I16, BF16X3, F64, I32 = 0, 1, 2, 3, 4, 5
+F32, BF16, I16, BF16X3, F64, I32, U8, I24 = 0, 1, 2, 3, 4, 5, 6, 7
 E_SHORT = -3
 
 _lib = None
@@ -125,6 +125,7 @@ def lib():
         L.mla_clips_lds_bytes.restype = i64
         L.mla_clips_lds_bytes.argtypes = [vp, i64, cd, ci, ci]
         L.mla_clips_prepare.argtypes = [vp, ci, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cd, i64, vp, i64, ci, ci, vp, vp]
+        L.mla_clips_prepare_raw.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cd, i64, vp, i64, ci, ci, vp, vp]
         u64 = ctypes.c_uint64
         L.mla_dropout_mask.argtypes = [vp, i64, u64, u64, u64, cf, vp]
         L.mla_dropout_mask_dev.argtypes = [vp, i64, u64, u64, vp, u64, cf, vp]

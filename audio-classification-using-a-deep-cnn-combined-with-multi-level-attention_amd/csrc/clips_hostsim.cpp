@@ -1,8 +1,9 @@
-// clips_hostsim.cpp -- TEST HARNESS (never part of libmla_hip.so): runs resample_core.h on the host exactly as clips_kernel
-// orders it, workgroup by workgroup (all 256 lanes stage, then all 256 lanes run their wings), with a plain array of
+// clips_hostsim.cpp -- TEST HARNESS (never part of libmla_hip.so): runs resample_core.h on the host exactly as clips_kernel and
+// clips_raw_kernel order it, workgroup by workgroup (all 256 lanes stage, then all 256 lanes run their wings), with a plain array of
 // `capacity` floats standing in for LDS. Built with g++ -ffp-contract=off by tests/test_clips_cpu.py to check the span, staging
 // and tap index arithmetic against the float64 restatement without a GPU. The stage array is refilled with NaN before every
-// workgroup, so a tap read outside the staged span shows in the output.
+// workgroup, so a tap read outside the staged span shows in the output. The two kernels differ in their source only: a Source
+// gives the mono mix of one frame of a clip and stages a span of it, as the kernel's lanes do.
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -13,9 +14,31 @@ using namespace resample_core;
 
 namespace {
 template <typename T>
-int64_t run(const T* packed, int64_t clips, const int64_t* offsets, const int64_t* frames, const int32_t* channels, const double* rates,
-            const int32_t* table_index, double sr_out, int64_t samples_num, const double* tables, int nwin, int num_table,
-            double pcm_scale, float* out) {
+struct TypedSource {                       // clips_kernel<T>: elements of T, offsets in elements
+    const T* packed;
+    const int64_t* offsets;
+    const int32_t* channels;
+    double pcm_scale;
+    float mix(int64_t c, int64_t frame) const { return mono_mix(packed + offsets[c] + frame * channels[c], channels[c], pcm_scale); }
+    void stage(int lane, int64_t c, int64_t first, int count, float* dst) const {
+        stage_span(lane, packed + offsets[c], channels[c], pcm_scale, first, count, dst);
+    }
+};
+
+struct RawSource {                         // clips_raw_kernel: bytes, offsets in bytes, a format code per clip
+    const unsigned char* packed;
+    const int64_t* offsets;
+    const int32_t* channels;
+    const int32_t* formats;
+    float mix(int64_t c, int64_t frame) const { return mono_mix_raw(packed + offsets[c], frame, channels[c], formats[c]); }
+    void stage(int lane, int64_t c, int64_t first, int count, float* dst) const {
+        stage_span_raw(lane, packed + offsets[c], channels[c], formats[c], first, count, dst);
+    }
+};
+
+template <typename Source>
+int64_t run(const Source& source, int64_t clips, const int64_t* frames, const int32_t* channels, const double* rates,
+            const int32_t* table_index, double sr_out, int64_t samples_num, const double* tables, int nwin, int num_table, float* out) {
     int64_t capacity = 0;
     for (int64_t c = 0; c < clips; ++c) {
         if (!(rates[c] > 0.0) || channels[c] < 1 || frames[c] < 0) return -1;
@@ -30,13 +53,11 @@ int64_t run(const T* packed, int64_t clips, const int64_t* offsets, const int64_
     const int64_t tiles = (samples_num + kThreads - 1) / kThreads;
     for (int64_t c = 0; c < clips; ++c) {
         const int64_t n_in = frames[c];
-        const int ch = channels[c];
-        const T* src = packed + offsets[c];
         float* row = out + c * samples_num;
         for (int64_t tile = 0; tile < tiles; ++tile) {
             const int t0 = int(tile) * kThreads;
             if (rates[c] == sr_out) {
-                for (int t = t0; t < t0 + kThreads && t < samples_num; ++t) row[t] = t < n_in ? mono_mix(src + int64_t(t) * ch, ch, pcm_scale) : 0.f;
+                for (int t = t0; t < t0 + kThreads && t < samples_num; ++t) row[t] = t < n_in ? source.mix(c, t) : 0.f;
                 continue;
             }
             const double ratio = sr_out / rates[c];
@@ -53,7 +74,7 @@ int64_t run(const T* packed, int64_t clips, const int64_t* offsets, const int64_
             span(t0, t_last, ratio, wing_taps(nwin, index_step), n_in, &first, &count);
             if (count > capacity) return -3;                       // the bound the launch sizes LDS from does not hold
             for (auto& v : stage) v = NAN;
-            for (int lane = 0; lane < kThreads; ++lane) stage_span(lane, src, ch, pcm_scale, first, count, stage.data());
+            for (int lane = 0; lane < kThreads; ++lane) source.stage(lane, c, first, count, stage.data());
             for (int t = t0; t < t0 + kThreads && t < samples_num; ++t) {
                 float v = 0.f;
                 if (t < n_valid) {
@@ -74,10 +95,22 @@ extern "C" int64_t hostsim_clips_prepare(const void* packed, int pcm_dtype, int6
                                          const int32_t* channels, const double* rates, const int32_t* table_index, double sr_out,
                                          int64_t samples_num, const double* tables, int nwin, int num_table, float* out) {
     if (pcm_dtype == 0)
-        return run(static_cast<const float*>(packed), clips, offsets, frames, channels, rates, table_index, sr_out, samples_num, tables, nwin,
-                   num_table, 1.0, out);
+        return run(TypedSource<float>{static_cast<const float*>(packed), offsets, channels, 1.0}, clips, frames, channels, rates, table_index,
+                   sr_out, samples_num, tables, nwin, num_table, out);
     if (pcm_dtype == 2)
-        return run(static_cast<const int16_t*>(packed), clips, offsets, frames, channels, rates, table_index, sr_out, samples_num, tables,
-                   nwin, num_table, 1.0 / 32768.0, out);
+        return run(TypedSource<int16_t>{static_cast<const int16_t*>(packed), offsets, channels, 1.0 / 32768.0}, clips, frames, channels, rates,
+                   table_index, sr_out, samples_num, tables, nwin, num_table, out);
     return -1;
+}
+
+// clips_raw_kernel: `packed` holds bytes, offsets are byte offsets, formats the MLA_* sample format codes (include/mla_hip.h).
+// Returns as above; -1 also for an unknown format and for an offset that is no multiple of the clip's sample size.
+extern "C" int64_t hostsim_clips_prepare_raw(const void* packed, int64_t clips, const int64_t* offsets, const int64_t* frames,
+                                             const int32_t* channels, const int32_t* formats, const double* rates, const int32_t* table_index,
+                                             double sr_out, int64_t samples_num, const double* tables, int nwin, int num_table, float* out) {
+    for (int64_t c = 0; c < clips; ++c) {
+        if (sample_bytes(formats[c]) == 0 || offsets[c] < 0 || offsets[c] % sample_align(formats[c]) != 0) return -1;
+    }
+    return run(RawSource{static_cast<const unsigned char*>(packed), offsets, channels, formats}, clips, frames, channels, rates, table_index,
+               sr_out, samples_num, tables, nwin, num_table, out);
 }

@@ -9,6 +9,12 @@
 //              right wing: sum_k (win[off_r + k * step] + eta_r * delta[..]) * mono[n + k + 1],  k < min(n_in - n - 1, (nwin - off_r) / step)
 //              one double accumulator, left wing first, one rounding to float32 by the caller
 //   mono_mix   mean over the channels of one frame in double, times the PCM scale, rounded once
+//   load_sample_as / mono_mix_raw / stage_span_raw: the same mix for clips_raw_kernel, whose source is the BYTES of a file's data
+//              chunk (8/16/24/32-bit PCM, float32, float64; the codes are include/mla_hip.h's MLA_*). The integers of a frame are
+//              summed exactly in double and scaled by a power of two after the mean, so a row equals mono_mix's on the samples
+//              decoded to float32 first wherever those are exact (every format but multi-channel 32-bit PCM). No byte outside
+//              [clip, clip + frames * channels * bytes_per_sample) is read: 24-bit samples are assembled from their three bytes,
+//              the 2/4/8-byte formats use naturally aligned loads (the clip starts on a multiple of its sample size).
 //
 // BIT-IDENTITY with resample_kernel. That kernel is compiled with the device compiler's default floating-point contraction,
 // which fuses exactly three of its expressions: t * inv - n, win + eta * delta and acc + w * x. Here contraction is switched
@@ -118,6 +124,88 @@ MLA_RS_HD int64_t span_capacity(double ratio, int taps) { return int64_t(double(
 template <typename T>
 MLA_RS_HD void stage_span(int lane, const T* clip, int channels, double scale, int64_t first, int count, float* stage) {
     for (int i = lane; i < count; i += kThreads) stage[i] = mono_mix(clip + (first + i) * channels, channels, scale);
+}
+
+// ---- clips whose source is a file's data chunk as it sits in the file (little endian) ----
+enum : int { kF32 = 0, kI16 = 2, kF64 = 4, kI32 = 5, kU8 = 6, kI24 = 7 };        // MLA_F32, MLA_I16, MLA_F64, MLA_I32, MLA_U8, MLA_I24
+
+// bytes per sample of a format code, 0 for a code that is no sample format
+MLA_RS_HD int sample_bytes(int fmt) {
+    switch (fmt) {
+        case kU8: return 1;
+        case kI16: return 2;
+        case kI24: return 3;
+        case kI32: case kF32: return 4;
+        case kF64: return 8;
+        default: return 0;
+    }
+}
+
+// what a clip's first byte has to be a multiple of: the sample size of the formats read with aligned loads, 1 for bytes
+MLA_RS_HD int sample_align(int fmt) { return fmt == kI24 ? 1 : sample_bytes(fmt); }
+
+// what the mean of a frame's load_sample_as() values is multiplied by: full scale of the integer formats -> 1.0
+MLA_RS_HD double sample_scale(int fmt) {
+    switch (fmt) {
+        case kU8: return 1.0 / 128.0;
+        case kI16: return 1.0 / 32768.0;
+        case kI24: return 1.0 / 8388608.0;
+        case kI32: return 1.0 / 2147483648.0;
+        default: return 1.0;
+    }
+}
+
+// sample `elem` of a clip that starts at `clip` (a multiple of the sample size for the 2/4/8-byte formats): bytes
+// [elem * sample_bytes, (elem + 1) * sample_bytes) of the clip and no others
+template <int FMT>
+MLA_RS_HD double load_sample_as(const unsigned char* clip, int64_t elem) {
+    if constexpr (FMT == kU8) return double(int(clip[elem]) - 128);
+    if constexpr (FMT == kI16) return double(reinterpret_cast<const int16_t*>(clip)[elem]);
+    if constexpr (FMT == kI24) {
+        const unsigned char* b = clip + 3 * elem;
+        const uint32_t v = uint32_t(b[0]) | uint32_t(b[1]) << 8 | uint32_t(b[2]) << 16;
+        return double(int32_t(v << 8) >> 8);                                      // sign extension of bit 23
+    }
+    if constexpr (FMT == kI32) return double(reinterpret_cast<const int32_t*>(clip)[elem]);
+    if constexpr (FMT == kF32) return double(reinterpret_cast<const float*>(clip)[elem]);
+    return double(float(reinterpret_cast<const double*>(clip)[elem]));            // kF64: rounded to float32 per sample, as a float read
+}
+
+// mono_mix for frame `frame` of a raw clip: the integers are summed exactly, the power-of-two scale follows the mean
+template <int FMT>
+MLA_RS_HD float mono_mix_as(const unsigned char* clip, int64_t frame, int channels) {
+    MLA_RS_NO_CONTRACT
+    double acc = 0.0;
+    for (int c = 0; c < channels; ++c) acc += load_sample_as<FMT>(clip, frame * channels + c);
+    return float(acc / double(channels) * sample_scale(FMT));
+}
+
+MLA_RS_HD float mono_mix_raw(const unsigned char* clip, int64_t frame, int channels, int fmt) {
+    switch (fmt) {
+        case kU8: return mono_mix_as<kU8>(clip, frame, channels);
+        case kI16: return mono_mix_as<kI16>(clip, frame, channels);
+        case kI24: return mono_mix_as<kI24>(clip, frame, channels);
+        case kI32: return mono_mix_as<kI32>(clip, frame, channels);
+        case kF32: return mono_mix_as<kF32>(clip, frame, channels);
+        default: return mono_mix_as<kF64>(clip, frame, channels);
+    }
+}
+
+template <int FMT>
+MLA_RS_HD void stage_span_as(int lane, const unsigned char* clip, int channels, int64_t first, int count, float* stage) {
+    for (int i = lane; i < count; i += kThreads) stage[i] = mono_mix_as<FMT>(clip, first + i, channels);
+}
+
+// stage_span for a raw clip: the format is uniform over the workgroup, so it is dispatched once, outside the loop
+MLA_RS_HD void stage_span_raw(int lane, const unsigned char* clip, int channels, int fmt, int64_t first, int count, float* stage) {
+    switch (fmt) {
+        case kU8: return stage_span_as<kU8>(lane, clip, channels, first, count, stage);
+        case kI16: return stage_span_as<kI16>(lane, clip, channels, first, count, stage);
+        case kI24: return stage_span_as<kI24>(lane, clip, channels, first, count, stage);
+        case kI32: return stage_span_as<kI32>(lane, clip, channels, first, count, stage);
+        case kF32: return stage_span_as<kF32>(lane, clip, channels, first, count, stage);
+        default: return stage_span_as<kF64>(lane, clip, channels, first, count, stage);
+    }
 }
 
 }  // namespace resample_core

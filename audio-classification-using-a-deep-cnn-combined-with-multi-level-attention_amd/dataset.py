@@ -12,6 +12,7 @@ model.py:98-99 (a reshape, not a transpose -- reproduced as is). ``clips_to_imag
 PCM of many clips -> (clips, T, 1, 224, 224) in two kernels (mel-dB spectrogram + clip-and-split gather)."""
 
 import ctypes
+import struct
 
 import numpy as np
 import torch
@@ -162,3 +163,111 @@ def wavfiles_to_clips(paths, sr=SR_RESNET, samples_num=SAMPLES_NUM_RESNET):
     """16-bit WAV files -> (B, samples_num) clips: read_wav16 on every path, then recordings_to_clips."""
     decoded = [read_wav16(str(p)) for p in paths]
     return recordings_to_clips([d[0] for d in decoded], [d[1] for d in decoded], sr, samples_num)
+
+
+# WAVE format tags read_audiofile refuses by name (everything but PCM, IEEE float and their extensible form is refused)
+_WAVE_TAGS = {0x0002: "MS ADPCM", 0x0006: "A-law", 0x0007: "mu-law", 0x0011: "IMA ADPCM", 0x0055: "MP3"}
+_PCM_FORMATS = {8: _lib.U8, 16: _lib.I16, 24: _lib.I24, 32: _lib.I32}
+_FLOAT_FORMATS = {32: _lib.F32, 64: _lib.F64}
+
+
+def read_audiofile(path):
+    """RIFF/WAVE file -> (the data chunk's bytes as a 1-D uint8 array, (format code, channels, rate, frames)), without converting
+    a sample: what librosa.load reads through libsndfile (dataset.py:232 of the reference) for PCM of 8, 16, 24 or 32 bits and
+    IEEE float of 32 or 64 bits, plain or WAVE_FORMAT_EXTENSIBLE (the container width counts: samples are left-justified). The
+    format code is _lib.U8 / I16 / I24 / I32 / F32 / F64, as frontend.prepare_clips_raw takes it. Chunks are walked in file
+    order (word-aligned; unknown ones are skipped). frames = min(declared data size, bytes present) // block align: a truncated
+    file or a trailing partial frame loses the incomplete part only, as with libsndfile. ValueError, naming the path, for
+    anything else: no RIFF/WAVE header (RIFX and RF64 included), no `fmt ` before `data`, no `data`, another tag or width, zero
+    channels or rate, a block align that is not channels * bits / 8."""
+    path = str(path)
+    with open(path, "rb") as f:
+        raw = f.read()
+
+    def bad(reason):
+        return ValueError("%s: %s" % (path, reason))
+
+    if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
+        raise bad("not a RIFF/WAVE file (header %r)" % (raw[:4] + raw[8:12],))
+    fmt, pos = None, 12
+    while pos + 8 <= len(raw):
+        cid, size = struct.unpack_from("<4sI", raw, pos)
+        pos += 8
+        if cid == b"fmt ":
+            if size < 16 or pos + size > len(raw):
+                raise bad("fmt chunk of %d bytes is too short" % min(size, len(raw) - pos))
+            tag, ch, rate, _, align, bits = struct.unpack_from("<HHIIHH", raw, pos)
+            if tag == 0xFFFE:
+                if size < 40:
+                    raise bad("extensible fmt chunk of %d bytes is too short" % size)
+                tag = struct.unpack_from("<H", raw, pos + 24)[0]             # first two bytes of the sub-format GUID
+            if tag not in (1, 3):
+                raise bad("format tag 0x%04x (%s) is not supported: PCM or IEEE float only" % (tag, _WAVE_TAGS.get(tag, "unknown")))
+            code = (_PCM_FORMATS if tag == 1 else _FLOAT_FORMATS).get(bits)
+            if code is None:
+                raise bad("%d-bit %s samples are not supported" % (bits, "PCM" if tag == 1 else "float"))
+            if ch < 1:
+                raise bad("zero channels")
+            if rate < 1:
+                raise bad("a rate of zero")
+            if align != ch * bits // 8:
+                raise bad("block align %d is not %d channels * %d bits / 8" % (align, ch, bits))
+            fmt = (code, ch, rate, align)
+        elif cid == b"data":
+            if fmt is None:
+                raise bad("no fmt chunk before the data chunk")
+            code, ch, rate, align = fmt
+            frames = min(size, len(raw) - pos) // align
+            return np.frombuffer(raw, dtype=np.uint8, count=frames * align, offset=pos), (code, ch, rate, frames)
+        pos += size + (size & 1)
+    raise bad("no data chunk")
+
+
+_SAMPLE_DTYPES = {_lib.U8: "u1", _lib.I16: "<i2", _lib.I32: "<i4", _lib.F32: "<f4", _lib.F64: "<f8"}
+
+
+def decode_audiofile(path):
+    """RIFF/WAVE file -> ((frames,) or (frames, channels) float32 array, rate): read_audiofile's bytes decoded on the host with
+    numpy, PCM scaled to [-1, 1) (8-bit: (x - 128) / 128; n-bit: x / 2**(n - 1)), float64 rounded to float32 -- what
+    soundfile.read(path, dtype="float32") returns. For callers who want arrays; the batched path decodes on the device."""
+    data, (code, ch, rate, frames) = read_audiofile(path)
+    if code == _lib.I24:
+        b = data.reshape(-1, 3).astype(np.int32)
+        x = ((b[:, 0] | b[:, 1] << 8 | b[:, 2] << 16) << 8 >> 8).astype(np.float32) / np.float32(8388608.0)
+    else:
+        x = data.view(_SAMPLE_DTYPES[code])
+        if code == _lib.U8:
+            x = (x.astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
+        elif code == _lib.I16:
+            x = x.astype(np.float32) / np.float32(32768.0)
+        elif code == _lib.I32:
+            x = (x.astype(np.float64) / 2147483648.0).astype(np.float32)          # one rounding per sample
+        else:
+            x = x.astype(np.float32)
+    return (x.reshape(frames, ch) if ch > 1 else x), rate
+
+
+def audiofiles_to_clips(paths, sr=SR_RESNET, samples_num=SAMPLES_NUM_RESNET):
+    """WAV files of any mixture of encodings read_audiofile accepts -> (B, samples_num) clips, as recordings_to_clips makes them:
+    the data chunks go back to back (each on a multiple of 8 bytes) into one pinned byte buffer as they sit in the files, travel
+    in one copy and are decoded, mixed, resampled, cut and zero-filled in one launch (frontend.prepare_clips_raw). The first
+    unreadable file raises, naming it; the checks and messages of recordings_to_clips come before anything is copied."""
+    files = [read_audiofile(p) for p in paths]
+    if sr <= 0:
+        raise ValueError("Invalid sample rate: sr_new=%r" % (sr,))
+    for i, (_, (_, _, r, n)) in enumerate(files):
+        if float(r) != float(sr) and int(n * (float(sr) / float(r))) < 1:
+            raise ValueError("recording %d: Input signal length=%d is too small to resample from %s->%s" % (i, n, r, sr))
+    if not files:
+        return torch.empty((0, int(samples_num)), dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu")
+    dev = frontend._device()
+    sizes = np.array([d.shape[0] for d, _ in files], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum((sizes + 7) // 8 * 8)[:-1]]).astype(np.int64)
+    host = torch.empty(int(offsets[-1] + sizes[-1]), dtype=torch.uint8, pin_memory=True)
+    flat = host.numpy()
+    for (d, _), o, s in zip(files, offsets, sizes):
+        flat[o:o + s] = d
+    code, ch, rate, frames = zip(*(desc for _, desc in files))
+    return frontend.prepare_clips_raw(host.to(dev, non_blocking=True), offsets, np.array(frames, dtype=np.int64),
+                                      np.array(ch, dtype=np.int32), np.array(rate, dtype=np.float64), np.array(code, dtype=np.int32),
+                                      sr, samples_num)

@@ -162,6 +162,23 @@ def clips_tables_host(scales):
     return np.concatenate([np.stack(_resample_filter(k)[:2], axis=1).reshape(-1) for k in scales])
 
 
+def _clips_out(out, B, samples_num, dev):
+    if out is None:
+        return torch.empty((B, samples_num), dtype=torch.float32, device=dev)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, samples_num)
+    return out
+
+
+def _clips_filters(rates, sr_out, dev):
+    """(scales, table index per recording, the device tables of these scales (cached), nwin, num_table) of one batch."""
+    scales, tab = clips_table_index(rates, sr_out)
+    nwin, num_table = _resample_filter(1.0)[0].shape[0], _resample_filter(1.0)[2]
+    tkey = (str(dev), scales)
+    if tkey not in _clips_tables:
+        _clips_tables[tkey] = torch.from_numpy(clips_tables_host(scales)).to(dev)
+    return scales, tab, _clips_tables[tkey], nwin, num_table
+
+
 def prepare_clips(packed, offsets, frames, channels, rates, sr_out, samples_num, out=None):
     """A batch of ragged recordings -> (B, samples_num) float32 clips at `sr_out` in ONE launch of csrc/clips.hip: channel mean,
     resampy 'kaiser_best' resampling of the whole recording (a copy where the rate already is sr_out), cut at samples_num and
@@ -181,18 +198,10 @@ def prepare_clips(packed, offsets, frames, channels, rates, sr_out, samples_num,
     B = fr.shape[0]
     assert off.shape[0] == B and ch.shape[0] == B and rt.shape[0] == B, "one descriptor entry per recording"
     sr_out, samples_num = float(sr_out), int(samples_num)
-    if out is None:
-        out = torch.empty((B, samples_num), dtype=torch.float32, device=dev)
-    else:
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, samples_num)
+    out = _clips_out(out, B, samples_num, dev)
     if B == 0:
         return out
-    scales, tab = clips_table_index(rt, sr_out)
-    nwin, num_table = _resample_filter(1.0)[0].shape[0], _resample_filter(1.0)[2]
-    tkey = (str(dev), scales)
-    if tkey not in _clips_tables:
-        _clips_tables[tkey] = torch.from_numpy(clips_tables_host(scales)).to(dev)
-    tables = _clips_tables[tkey]
+    scales, tab, tables, nwin, num_table = _clips_filters(rt, sr_out, dev)
     desc = torch.empty(B * 32, dtype=torch.uint8, pin_memory=True)       # offsets | frames | rates | channels | table index
     h = desc.numpy()
     h[:8 * B].view(np.int64)[:] = off
@@ -209,6 +218,47 @@ def prepare_clips(packed, offsets, frames, channels, rates, sr_out, samples_num,
     _lib.check(ops._timed("clips_prepare", _lib.lib().mla_clips_prepare, vp(packed.data_ptr()), code, packed.shape[0], B,
                           vp(base), vp(base + 8 * B), vp(base + 24 * B), vp(base + 16 * B), vp(base + 28 * B),
                           hp(off), hp(fr), hp(ch), hp(rt), hp(tab), sr_out, samples_num,
+                          vp(tables.data_ptr()) if scales else None, len(scales), nwin, num_table, vp(out.data_ptr()), _lib.stream_ptr()))
+    return out
+
+
+def prepare_clips_raw(packed_bytes, byte_offsets, frames, channels, rates, formats, sr_out, samples_num, out=None):
+    """prepare_clips for recordings that still are the bytes of their files' data chunks: the samples are decoded in the same
+    ONE launch (csrc/clips.hip, clips_raw_kernel), so a batch of mixed encodings is uploaded as it sits on disk.
+
+    packed_bytes: 1-D uint8 device tensor, the data chunks (little endian, interleaved frames). byte_offsets: where each
+    recording starts, a multiple of its sample size. formats: one code per recording, _lib.U8 / I16 / I24 / I32 (PCM, scaled
+    to [-1, 1)) or _lib.F32 / F64 (float64 samples are rounded to float32 one by one). The other arguments, the descriptor
+    traffic and the cached filter tables are prepare_clips's. A row equals prepare_clips's on the recording decoded to float32
+    first, bit for bit, for every format but multi-channel 32-bit PCM, whose integers are summed exactly and rounded once. No byte
+    outside a recording's own range is read. `out`, when given, is overwritten completely."""
+    assert packed_bytes.is_cuda and packed_bytes.dim() == 1 and packed_bytes.is_contiguous() and packed_bytes.dtype == torch.uint8
+    dev = packed_bytes.device
+    off, fr = _host_array(byte_offsets, np.int64), _host_array(frames, np.int64)
+    ch, rt, fm = _host_array(channels, np.int32), _host_array(rates, np.float64), _host_array(formats, np.int32)
+    B = fr.shape[0]
+    assert off.shape[0] == B and ch.shape[0] == B and rt.shape[0] == B and fm.shape[0] == B, "one descriptor entry per recording"
+    sr_out, samples_num = float(sr_out), int(samples_num)
+    out = _clips_out(out, B, samples_num, dev)
+    if B == 0:
+        return out
+    scales, tab, tables, nwin, num_table = _clips_filters(rt, sr_out, dev)
+    desc = torch.empty(B * 36, dtype=torch.uint8, pin_memory=True)       # offsets | frames | rates | channels | table index | formats
+    h = desc.numpy()
+    h[:8 * B].view(np.int64)[:] = off
+    h[8 * B:16 * B].view(np.int64)[:] = fr
+    h[16 * B:24 * B].view(np.float64)[:] = rt
+    h[24 * B:28 * B].view(np.int32)[:] = ch
+    h[28 * B:32 * B].view(np.int32)[:] = tab
+    h[32 * B:].view(np.int32)[:] = fm
+    d = desc.to(dev, non_blocking=True)
+    vp = ctypes.c_void_p
+    base = d.data_ptr()
+    hp = lambda a: a.ctypes.data_as(vp)
+    from . import ops
+    _lib.check(ops._timed("clips_prepare_raw", _lib.lib().mla_clips_prepare_raw, vp(packed_bytes.data_ptr()), packed_bytes.shape[0], B,
+                          vp(base), vp(base + 8 * B), vp(base + 24 * B), vp(base + 16 * B), vp(base + 28 * B), vp(base + 32 * B),
+                          hp(off), hp(fr), hp(ch), hp(rt), hp(tab), hp(fm), sr_out, samples_num,
                           vp(tables.data_ptr()) if scales else None, len(scales), nwin, num_table, vp(out.data_ptr()), _lib.stream_ptr()))
     return out
 

@@ -159,6 +159,13 @@ class Ensemble(nn.Module):
         from . import dataset
         return self.forward_clips(dataset.wavfiles_to_clips(paths), overlap)
 
+    def forward_audiofiles(self, paths, overlap=True):
+        """forward_recordings for WAV files of any PCM width or IEEE float, mixed in one batch: dataset.audiofiles_to_clips uploads
+        the files' bytes and decodes them in the clips launch."""
+        self._recordings_only_resnet("forward_audiofiles")
+        from . import dataset
+        return self.forward_clips(dataset.audiofiles_to_clips(paths), overlap)
+
     def stream_waveforms(self, host_batches):
         """Host-resident PCM: iterate over (B, n_samples) float32 / int16 tensors in PINNED host memory and yield the
         (B, K) scores of each. The copy of batch i+1 runs on its own HIP stream while batch i computes (two device

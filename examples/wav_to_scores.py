@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""WAV files -> class scores with the ResNet branch: a ragged batch of 16-bit recordings of any rate and channel count becomes
-the (B, 88 200) clips of 22 050 Hz PCM in one HIP launch, then mel-dB images, the ResNet-50 trunk and the attention head.
+"""WAV files -> class scores with the ResNet branch: a ragged batch of recordings of any rate, channel count and encoding (8/16/24/32-bit
+PCM, float32, float64) becomes the (B, 88 200) clips of 22 050 Hz PCM in one HIP launch, then mel-dB images, the ResNet-50 trunk and the attention head.
 
     python examples/wav_to_scores.py [checkpoint.pt] a.wav b.wav ...
 
@@ -58,13 +58,13 @@ def main():
             if not checkpoint:
                 # seeded running statistics describe unit-scale inputs, not dB images: the eval-mode attention would underflow to
                 # 0 / 0. A trained checkpoint's statistics describe its data; here thirty train-mode passes stand in for that.
-                images = dataset.clips_to_images(dataset.wavfiles_to_clips(paths))
+                images = dataset.clips_to_images(dataset.audiofiles_to_clips(paths))
                 clf.train()
                 for _ in range(30):
                     clf(images)
                 clf.eval()
-            clips = dataset.wavfiles_to_clips(paths)                 # (B, 88200) float32 on the GPU, one launch
-            scores = clf.forward_clips(clips)                        # the same as clf.forward_wavfiles(paths)
+            clips = dataset.audiofiles_to_clips(paths)               # (B, 88200) float32 on the GPU, decoded in one launch
+            scores = clf.forward_clips(clips)                        # the same as clf.forward_audiofiles(paths)
     for path, clip, row in zip(paths, clips, scores):
         print("%s: %d of 88200 samples non-zero, scores %s" % (os.path.basename(path), int((clip != 0).sum()),
                                                                 np.array2string(row.float().cpu().numpy(), precision=3)))

@@ -42,8 +42,10 @@ extern "C" {
 #define MLA_F32   0
 #define MLA_BF16  1
 #define MLA_I16   2
-#define MLA_F64   4  /* mla_allreduce_flat only (the BatchNorm sums travel in double precision) */
-#define MLA_I32   5  /* mla_allreduce_flat only (n_correct)                                        */
+#define MLA_F64   4  /* mla_allreduce_flat (the BatchNorm sums travel in double precision); sample format of mla_clips_prepare_raw */
+#define MLA_I32   5  /* mla_allreduce_flat (n_correct); sample format of mla_clips_prepare_raw                                    */
+#define MLA_U8    6  /* unsigned 8-bit PCM: sample format of mla_clips_prepare_raw only                                          */
+#define MLA_I24   7  /* signed 24-bit PCM, three packed little-endian bytes: sample format of mla_clips_prepare_raw only         */
 #define MLA_BF16X3 3  /* "split" bf16: x = hi + lo, two bf16 planes [hi(C) | lo(C)] per row / pixel; three bf16 MFMA
                         * products per term (hi*hi + hi*lo + lo*hi) with f32 accumulation: f32-grade results (2^-18
                         * relative per product) at a third of the bf16 rate. Accepted by mla_vggish_conv1 (output),
@@ -435,6 +437,29 @@ int mla_clips_prepare(const void* packed, int pcm_dtype, int64_t packed_elems, i
                       const int64_t* host_offsets, const int64_t* host_frames, const int32_t* host_channels,
                       const double* host_rates, const int32_t* host_table_index, double sr_out, int64_t samples_num,
                       const double* tables, int64_t n_tables, int nwin, int num_table, float* out, mla_stream_t stream);
+/* mla_clips_prepare for recordings that still are the BYTES of their files' data chunks (little endian, interleaved), so that
+ * a batch of 8/16/24/32-bit PCM, float32 and float64 files is uploaded as it sits on disk and decoded in the same ONE launch.
+ * packed: DEVICE buffer of packed_bytes bytes, aligned to 8. offsets are BYTE offsets; formats (DEVICE) / host_formats hold a
+ * sample format code per clip; everything else is mla_clips_prepare's, argument for argument.
+ *   code      file encoding                  value summed over the channels            scale after the mean
+ *   MLA_U8    unsigned 8-bit                 x - 128                                   1 / 128
+ *   MLA_I16   signed 16-bit                  x                                         1 / 32768
+ *   MLA_I24   signed 24-bit, 3 packed bytes  x, sign-extended                          1 / 8388608
+ *   MLA_I32   signed 32-bit                  x                                         1 / 2147483648
+ *   MLA_F32   IEEE float32                   x                                         1
+ *   MLA_F64   IEEE float64                   double(float(x)): rounded per sample      1
+ *   mono[j] = float(sum in double / channels * scale): mla_clips_prepare's mix. MLA_I16 and MLA_F32 clips give its rows bit for
+ *   bit, and every format gives its rows on the samples decoded to float32 first wherever those are exact (all but
+ *   multi-channel MLA_I32, whose integers are summed exactly and rounded once).
+ * No byte outside [offset, offset + frames * channels * bytes_per_sample) of a clip is read: 24-bit samples are assembled from
+ * their bytes, the 2/4/8-byte formats use naturally aligned loads. MLA_E_ARG in addition to mla_clips_prepare's: an unknown
+ * format code, an offset that is no multiple of the clip's sample size, a packed pointer that is not aligned to 8 bytes. */
+int mla_clips_prepare_raw(const void* packed, int64_t packed_bytes, int64_t clips, const int64_t* offsets, const int64_t* frames,
+                          const int32_t* channels, const double* rates, const int32_t* table_index, const int32_t* formats,
+                          const int64_t* host_offsets, const int64_t* host_frames, const int32_t* host_channels,
+                          const double* host_rates, const int32_t* host_table_index, const int32_t* host_formats, double sr_out,
+                          int64_t samples_num, const double* tables, int64_t n_tables, int nwin, int num_table, float* out,
+                          mla_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Data-parallel exchange (the reference is single-process, train.py:119-142: these entry
