@@ -34,6 +34,7 @@
 
 #include "common.h"
 #include "conv1_core.h"
+#include "logmel_bags_core.h"
 #include "logmel_core.h"
 #include "logmel_tables.h"
 
@@ -81,6 +82,7 @@ __device__ __forceinline__ void group_sync() {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // value held by lane (16 - j) & 15 of the same 16-lane row: DPP row_mirror (j -> 15 - j) followed by
 // row_ror:1 -- two VALU moves, no LDS round trip (verified on hardware: 0 15 14 ... 1)
@@ -118,10 +120,15 @@ template <> struct Samples<int16_t> {
         u[kU - 1] = 0u;
         if (j < 8) u[kU - 1] = VEC ? *reinterpret_cast<const uint32_t*>(p + 32 * (kU - 1)) : (p[32 * (kU - 1)] | (uint32_t(p[32 * (kU - 1) + 1]) << 16));
     }
-    // int16 -> float in [-1, 1): x / 32768 exactly (vggish_input.py:98)
+    // int16 -> float in [-1, 1): x / 32768 exactly (vggish_input.py:98). The result passes through an empty asm so that the
+    // arithmetic after it is compiled as it is for float samples taken from registers: without it hipcc contracts the window
+    // product of THIS instantiation into the first butterflies' FMAs (24 more FMAs per frame pair than the float kernel) and int16
+    // PCM does not give the bits of the same samples / 32768 as float32.
     __device__ __forceinline__ f32x2 pair(int m) const {
         constexpr float k = 1.0f / 32768.0f;
-        return f32x2{k * float(int16_t(u[m] & 0xFFFFu)), k * float(int16_t(u[m] >> 16))};
+        f32x2 v = f32x2{k * float(int16_t(u[m] & 0xFFFFu)), k * float(int16_t(u[m] >> 16))};
+        asm("" : "+v"(v));
+        return v;
     }
 };
 
@@ -229,6 +236,16 @@ struct RowsToStaged {
     __device__ __forceinline__ void operator()(int j, f32x4 va, f32x4 vb) const {
         one(row, j, va);
         one(row + conv1::kPitch, j, vb);
+    }
+};
+
+// ColsToStage: the wave's 8 finished rows (= 8 columns of the clip's spectrogram) side by side in its first (dead) exchange buffer,
+// stage[column][band]: 16-byte pieces on write, and lane = band reads its 8 columns back conflict-free (logmel_bags_kernel).
+struct ColsToStage {
+    float* cols;                                                 // column of row A; row B is the next column
+    __device__ __forceinline__ void operator()(int j, f32x4 va, f32x4 vb) const {
+        *reinterpret_cast<f32x4*>(cols + 4 * j) = va;
+        *reinterpret_cast<f32x4*>(cols + kBands + 4 * j) = vb;
     }
 };
 
@@ -410,6 +427,103 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_dyn_kernel(const InT* _
 #endif
 }
 
+// Ragged bags (dataset.py:318-324 create_spec's native path + :329-363 split, for a batch): rows of 16 kHz PCM holding counts[c] <= 4
+// whole examples each -> out[c][t][band][x] = spec_c[band][t * stride + x], where spec_c is the clip's (64, 384) spectrogram with
+// 0.0 in the slots it lacks. The dynamic kernel's schedule over 48 items per clip (logmel_bags_core.h): an item of a slot the clip
+// has runs pair_step, any other only stores zeros; the branch is wave-uniform. The wave's 8 columns are staged column-major in its
+// first (dead) exchange buffer, then lane = band stores its 8 consecutive x (32 B of f32, 16 B of bf16) into each of the <= 3
+// windows that hold the columns. Every element of `out` is written exactly once: no memset, no atomics on global memory.
+static_assert(logmel_bags::kItemCols == kItemFrames && logmel_bags::kItemCols * kBands <= kXchFloats, "one item = one wave-iteration, staged in one buffer");
+
+template <typename OutT>
+__device__ __forceinline__ void store_cols(OutT* dst, f32x4 lo, f32x4 hi) {
+    if constexpr (sizeof(OutT) == 4) {
+        *reinterpret_cast<f32x4*>(dst) = lo;
+        *reinterpret_cast<f32x4*>(dst + 4) = hi;
+    } else {
+        const u32x2 a = pack_piece(lo), b = pack_piece(hi);
+        *reinterpret_cast<u32x4*>(dst) = u32x4{a.x, a.y, b.x, b.y};
+    }
+}
+
+template <typename InT, typename OutT, bool VEC>
+__global__ __launch_bounds__(kThreadsDyn, 1) void logmel_bags_kernel(const InT* __restrict__ pcm, int64_t row_stride,
+                                                                     const int32_t* __restrict__ counts, int n_items, int n_frames,
+                                                                     int stride, const float* __restrict__ tab, OutT* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* s_xch = smem;
+    float* s_mel = s_xch + (kThreadsDyn / 16) * kPair * kXchFloats;
+    float* s_pw = s_mel + 16 * kMelRow;
+    float* s_win = s_pw + 16 * kPwPitch;
+    int* s_next = reinterpret_cast<int*>(s_win + kWinFloats);
+
+    const int t = threadIdx.x, g = t >> 4, gl = g & 3, j = t & 15, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    float* xa = s_xch + (kPair * g) * kXchFloats;
+    float* xb = xa + kXchFloats;
+    float* stage = s_xch + (kItemFrames * wv) * kXchFloats;      // the wave's first exchange buffer: 8 columns x 64 bands
+
+    LaneConsts c;
+    load_consts(c, tab, j);
+    for (int i = t; i < 16 * kMelRow; i += kThreadsDyn) s_mel[i] = tab[kTabMelW + i];
+    for (int i = t; i < 16 * kPwRow; i += kThreadsDyn) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
+    for (int i = t; i < kWinFloats; i += kThreadsDyn) s_win[i] = tab[kTabWindow + i];
+    // this workgroup's contiguous share of the items
+    const int lo = int(int64_t(n_items) * int64_t(blockIdx.x) / int64_t(gridDim.x)), hi = int(int64_t(n_items) * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
+    if (t == 0) *s_next = lo;
+    const float* melw = s_mel + kMelRow * j;
+    const float* pw = s_pw + kPwPitch * j;
+    __syncthreads();                        // the only workgroup barrier: tables and the counter visible
+
+    auto pull = [&]() {                      // wave-uniform: one lane takes the next item of the workgroup's share
+        int v = 0;
+        if (lane == 0) v = atomicAdd(s_next, 1);
+        return __builtin_amdgcn_readfirstlane(v);
+    };
+    const int lane_frame = kPair * gl;                        // this group's frame pair inside the item
+    // wave-uniform: the first sample of this group's pair in `item`, or null where the clip lacks the item's slot (or past the share)
+    auto item_frame = [&](int item, int& clip, int& col) -> const InT* {
+        if (item >= hi) return nullptr;
+        int slot, frame;
+        logmel_bags::item_locate(item, &clip, &slot, &frame);
+        col = logmel_bags::item_column(slot, frame);
+        if (slot >= counts[clip]) return nullptr;
+        return pcm + int64_t(clip) * row_stride + logmel_bags::frame_sample(slot, frame + lane_frame);
+    };
+    auto wave_fence = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    Samples<InT> smp;
+    int cur = pull(), clip = 0, col = 0;
+    const InT* frame = item_frame(cur, clip, col);
+    bool fetched = false;                                      // smp holds `frame`'s samples (prefetched by the item before)
+    while (cur < hi) {
+        const int nxt = pull();
+        int nclip = 0, ncol = 0;
+        const InT* next_frame = item_frame(nxt, nclip, ncol);
+        f32x4 v_lo = {0.f, 0.f, 0.f, 0.f}, v_hi = {0.f, 0.f, 0.f, 0.f};
+        if (frame) {
+            // after a zero item, or at the start, nothing has been prefetched for this one
+            if (!fetched) smp.template fetch<VEC>(frame, j);
+            pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, ColsToStage{stage + lane_frame * kBands});
+            _Pragma("unroll") for (int x = 0; x < 4; ++x) {
+                v_lo[x] = stage[x * kBands + lane];
+                v_hi[x] = stage[(4 + x) * kBands + lane];
+            }
+            wave_fence();                   // the stage is rewritten by the next FFT
+        }
+        fetched = frame && next_frame;
+        int t_lo, t_hi;
+        logmel_bags::column_windows(col, n_frames, stride, &t_lo, &t_hi);
+        for (int w = t_lo; w <= t_hi; ++w) store_cols<OutT>(out + logmel_bags::out_offset(clip, n_frames, stride, w, lane, col), v_lo, v_hi);
+        cur = nxt;
+        frame = next_frame;
+        clip = nclip;
+        col = ncol;
+    }
+}
+
 // Fused front (bf16 inference): PCM -> conv1's pooled NHWC output in one kernel; the bf16 examples never exist in memory. The
 // stand-alone pair is bound by different things -- logmel_dyn_kernel by vector issue and LDS, conv1_patch_kernel by the store
 // path -- so here conv1's non-temporal stores drain while other waves run FFTs.
@@ -561,6 +675,24 @@ int launch_fused(const void* pcm, int64_t n_wave, int64_t wave_stride, int64_t e
 }
 
 template <typename InT, typename OutT>
+int launch_bags(const void* pcm, int64_t clips, int64_t row_stride, const int32_t* counts, int n_frames, int stride, const float* tables,
+                void* out, hipStream_t stream) {
+    const int64_t n_items = clips * logmel_bags::kClipItems;
+    const bool vec = mla::aligned(pcm, 2 * sizeof(InT)) && (row_stride % 2 == 0);
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t wgs = (n_items + 7) / 8 < cus ? (n_items + 7) / 8 : cus;
+    auto go = [&](auto kern) -> int {
+        MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesDyn));
+        hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(kThreadsDyn), kLdsBytesDyn, stream, static_cast<const InT*>(pcm), row_stride,
+                           counts, int(n_items), n_frames, stride, tables, static_cast<OutT*>(out));
+        MLA_LAUNCH_OK("logmel_bags_kernel");
+        return MLA_OK;
+    };
+    return vec ? go(logmel_bags_kernel<InT, OutT, true>) : go(logmel_bags_kernel<InT, OutT, false>);
+}
+
+template <typename InT, typename OutT>
 int launch(const void* pcm, int64_t n_wave, int64_t wave_stride, int64_t examples, const float* tables,
            void* out, bool wave_sync, bool static_wave, hipStream_t stream) {
     const int64_t n_chunks = n_wave * examples * (kExFrames / kChunk);
@@ -660,6 +792,37 @@ extern "C" int mla_logmel_examples(const void* pcm, int pcm_dtype, int64_t n_wav
     }
     return out_dtype == MLA_F32 ? launch<int16_t, float>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s)
                                 : launch<int16_t, __hip_bfloat16>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s);
+}
+
+extern "C" int mla_logmel_bags(const void* pcm, int pcm_dtype, int64_t clips, int64_t n_samples, int64_t row_stride,
+                               const int32_t* counts, const int32_t* host_counts, int n_frames, int stride, const float* tables,
+                               void* out, int out_dtype, mla_stream_t stream) {
+    MLA_REQUIRE(clips >= 0 && n_samples >= 0 && row_stride >= n_samples, MLA_E_ARG, "bad clips %lld / stride %lld < n_samples %lld",
+                (long long)clips, (long long)row_stride, (long long)n_samples);
+    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d is neither MLA_F32 nor MLA_I16", pcm_dtype);
+    MLA_REQUIRE(out_dtype == MLA_F32 || out_dtype == MLA_BF16, MLA_E_DTYPE, "out_dtype %d is neither MLA_F32 nor MLA_BF16", out_dtype);
+    MLA_REQUIRE(logmel_bags::config_ok(n_frames, stride), MLA_E_SHAPE,
+                "%d frames at stride %d: only (10, 32) and (4, 96) are compiled (dataset.py:352-361)", n_frames, stride);
+    if (clips == 0) return MLA_OK;
+    MLA_REQUIRE(pcm && counts && host_counts && tables && out, MLA_E_ARG, "null pcm/counts/host_counts/tables/out");
+    MLA_REQUIRE(mla::aligned(out, 16), MLA_E_ARG, "out must be 16-byte aligned");
+    MLA_REQUIRE(mla::aligned(tables, 4) && mla::aligned(counts, 4), MLA_E_ARG, "tables and counts must be 4-byte aligned");
+    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
+    MLA_REQUIRE(clips <= 0x7fffffff / logmel_bags::kClipItems, MLA_E_SHAPE, "too many clips for one launch (%lld)", (long long)clips);
+    for (int64_t i = 0; i < clips; ++i) {
+        const int n = host_counts[i];
+        MLA_REQUIRE(n >= 0 && n <= logmel_bags::kSlots, MLA_E_ARG, "clip %lld: %d examples do not fit the 4 slots (dataset.py:321-322)",
+                    (long long)i, n);
+        MLA_REQUIRE(logmel_bags::samples_read(n) <= n_samples, MLA_E_SHAPE, "clip %lld: %d examples read %lld samples, the rows hold %lld",
+                    (long long)i, n, (long long)logmel_bags::samples_read(n), (long long)n_samples);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (pcm_dtype == MLA_F32) {
+        return out_dtype == MLA_F32 ? launch_bags<float, float>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s)
+                                    : launch_bags<float, __hip_bfloat16>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s);
+    }
+    return out_dtype == MLA_F32 ? launch_bags<int16_t, float>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s)
+                                : launch_bags<int16_t, __hip_bfloat16>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s);
 }
 
 extern "C" int mla_logmel_conv1(const void* pcm, int pcm_dtype, int64_t n_wave, int64_t n_samples, int64_t wave_stride,

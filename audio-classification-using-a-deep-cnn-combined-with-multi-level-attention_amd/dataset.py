@@ -119,6 +119,12 @@ def recordings_to_clips(recordings, rates, sr=SR_RESNET, samples_num=SAMPLES_NUM
     The WHOLE recording is resampled and the cut comes afterwards, as in the reference. The samples travel through one packed
     pinned host buffer and one copy, the descriptors through another. ValueError (naming the recording) where resampy raises,
     before anything is copied or launched. An empty sequence gives a (0, samples_num) tensor."""
+    recs, rates = _checked_recordings(recordings, rates, sr)
+    return _pack_recordings(recs, rates, sr, samples_num)
+
+
+def _checked_recordings(recordings, rates, sr):
+    """recordings_to_clips' checks, all before anything is copied or launched -> (host arrays, one rate per recording)."""
     recs = [_host_recording(x, i) for i, x in enumerate(recordings)]
     B = len(recs)
     rates = [rates] * B if np.isscalar(rates) else list(rates)
@@ -133,7 +139,11 @@ def recordings_to_clips(recordings, rates, sr=SR_RESNET, samples_num=SAMPLES_NUM
             raise ValueError("recording %d: Invalid sample rate: sr_orig=%r" % (i, r))
         if float(r) != float(sr) and int(x.shape[0] * (float(sr) / float(r))) < 1:
             raise ValueError("recording %d: Input signal length=%d is too small to resample from %s->%s" % (i, x.shape[0], r, sr))
-    if B == 0:
+    return recs, rates
+
+
+def _pack_recordings(recs, rates, sr, samples_num):
+    if not recs:
         return torch.empty((0, int(samples_num)), dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu")
     dev = frontend._device()
     frames = np.array([x.shape[0] for x in recs], dtype=np.int64)
@@ -252,12 +262,20 @@ def audiofiles_to_clips(paths, sr=SR_RESNET, samples_num=SAMPLES_NUM_RESNET):
     the data chunks go back to back (each on a multiple of 8 bytes) into one pinned byte buffer as they sit in the files, travel
     in one copy and are decoded, mixed, resampled, cut and zero-filled in one launch (frontend.prepare_clips_raw). The first
     unreadable file raises, naming it; the checks and messages of recordings_to_clips come before anything is copied."""
+    return _pack_audiofiles(_checked_audiofiles(paths, sr), sr, samples_num)
+
+
+def _checked_audiofiles(paths, sr):
     files = [read_audiofile(p) for p in paths]
     if sr <= 0:
         raise ValueError("Invalid sample rate: sr_new=%r" % (sr,))
     for i, (_, (_, _, r, n)) in enumerate(files):
         if float(r) != float(sr) and int(n * (float(sr) / float(r))) < 1:
             raise ValueError("recording %d: Input signal length=%d is too small to resample from %s->%s" % (i, n, r, sr))
+    return files
+
+
+def _pack_audiofiles(files, sr, samples_num):
     if not files:
         return torch.empty((0, int(samples_num)), dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu")
     dev = frontend._device()
@@ -271,3 +289,63 @@ def audiofiles_to_clips(paths, sr=SR_RESNET, samples_num=SAMPLES_NUM_RESNET):
     return frontend.prepare_clips_raw(host.to(dev, non_blocking=True), offsets, np.array(frames, dtype=np.int64),
                                       np.array(ch, dtype=np.int32), np.array(rate, dtype=np.float64), np.array(code, dtype=np.int32),
                                       sr, samples_num)
+
+
+# ---- the VGGish branch from recordings: load_hdf5(cnn_type="vggish", use_librosa=False), dataset.py:239-254 -----------------------
+SR_VGGISH = 16000
+SAMPLES_NUM_VGGISH = 15600 + 3 * 15360          # 61 680: all that four 0.96 s examples read
+
+
+def _bag_counts(frames, rates):
+    """Whole 0.96 s examples of every recording once it is at 16 kHz: n_res from the library's resampled length (the frames
+    themselves at 16 kHz), examples from mla_logmel_counts. ValueError, naming the recording, where the reference raises: fewer
+    than 240 samples (mel_features.py:42-45) or more than the 4 slots of create_spec (dataset.py:321-322)."""
+    L = _lib.lib()
+    counts = np.zeros(len(frames), dtype=np.int32)
+    for i, (n, r) in enumerate(zip(frames, rates)):
+        n_res = int(n) if float(r) == float(SR_VGGISH) else int(L.mla_resample_length(int(n), float(r), float(SR_VGGISH)))
+        try:
+            counts[i] = frontend.counts(n_res)[1]
+        except ValueError as e:
+            raise ValueError("recording %d: %s (%d samples at 16 kHz)" % (i, e, n_res)) from None
+        if counts[i] > 4:
+            raise ValueError("recording %d: could not broadcast input array from shape (%d,96,64) into shape (4,96,64)" % (i, counts[i]))
+    return counts
+
+
+def _bags(clips, counts, overlap, out_dtype):
+    n = T if overlap else 4
+    if clips.shape[0] == 0:
+        return torch.empty((0, n, 1, 64, 96), dtype=out_dtype, device=clips.device)
+    return frontend.logmel_bags(clips, counts, n, (384 - 96) // (T - 1) if overlap else 96, out_dtype)
+
+
+def recordings_to_frames(recordings, rates, overlap=True, out_dtype=torch.float32):
+    """Recordings as they are decoded -> the (B, T, 1, 64, 96) bag tensor load_hdf5(cnn_type="vggish", use_librosa=False) stores
+    (dataset.py:239-254) and Ensemble consumes, in TWO launches whatever B is: recordings_to_clips at 16 kHz (channel mean, resampy
+    'kaiser_best' resampling of the whole recording) into rows of 61 680 samples, then frontend.logmel_bags with the number of
+    whole 0.96 s examples of each recording. As in the reference the waveform is not zero-filled: a trailing partial example is
+    dropped and the slots a recording lacks are 0.0 (a recording shorter than 0.975 s gives an all-zero bag). overlap=False gives
+    4 frames per bag (contiguous_split). out_dtype: torch.float32 or torch.bfloat16 (one rounding of the float32 value).
+    recordings / rates: as recordings_to_clips takes them, with its errors; further ValueErrors, naming the recording, where the
+    reference raises: fewer than 240 samples at 16 kHz ("negative dimensions are not allowed") and more than 4 examples
+    (77 040 samples or more). All of them come before anything is copied or launched. An empty sequence gives (0, T, 1, 64, 96)."""
+    recs, rates = _checked_recordings(recordings, rates, SR_VGGISH)
+    counts = _bag_counts([x.shape[0] for x in recs], rates)
+    return _bags(_pack_recordings(recs, rates, SR_VGGISH, SAMPLES_NUM_VGGISH), counts, overlap, out_dtype)
+
+
+def wavfiles_to_frames(paths, overlap=True, out_dtype=torch.float32):
+    """16-bit WAV files -> (B, T, 1, 64, 96) bags: read_wav16 on every path (other widths are refused), then recordings_to_frames."""
+    decoded = [read_wav16(str(p)) for p in paths]
+    return recordings_to_frames([d[0] for d in decoded], [d[1] for d in decoded], overlap, out_dtype)
+
+
+def audiofiles_to_frames(paths, overlap=True, out_dtype=torch.float32):
+    """WAV files of any mixture of encodings read_audiofile accepts -> (B, T, 1, 64, 96) bags, in two launches: the files' bytes
+    are decoded, mixed and resampled to 16 kHz by frontend.prepare_clips_raw, then frontend.logmel_bags. Bit-identical to
+    wavfiles_to_frames for 16-bit files; other encodings are decoded at full precision (the reference's sf.read(dtype="int16")
+    quantises them to int16 first: DESIGN.md section 7)."""
+    files = _checked_audiofiles(paths, SR_VGGISH)
+    counts = _bag_counts([d[1][3] for d in files], [d[1][2] for d in files])
+    return _bags(_pack_audiofiles(files, SR_VGGISH, SAMPLES_NUM_VGGISH), counts, overlap, out_dtype)

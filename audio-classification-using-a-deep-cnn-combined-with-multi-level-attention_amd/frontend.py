@@ -284,6 +284,39 @@ def waveforms_to_examples(pcm, out_dtype=torch.float32, out=None):
     return out
 
 
+def logmel_bags(pcm, counts, n_frames=10, stride=32, out_dtype=torch.float32, out=None):
+    """(B, n) device rows of 16 kHz mono PCM (float32 or int16) holding counts[c] <= 4 whole 0.96 s examples each -> the
+    (B, n_frames, 1, 64, 96) bag tensor of the reference's native VGGish dataset path (dataset.py:318-324 create_spec + :329-363
+    split) in ONE launch of csrc/logmel.hip (logmel_bags_kernel): log-mel of the examples a row has, 0.0 in the slots it lacks, cut
+    into n_frames windows of 96 columns at `stride` -- (10, 32) with overlap, (4, 96) without. Written directly in `out_dtype`
+    (float32 or bfloat16). counts: host integers (a device tensor is read back first); they travel in one pinned buffer and one
+    copy. Row c equals mla_logmel_examples + mla_dataset_frames on its first 15 600 + 15 360 (counts[c] - 1) samples, bit for bit;
+    nothing beyond them is read. `out`, when given, is overwritten completely."""
+    assert pcm.dim() == 2 and pcm.is_cuda and (pcm.shape[1] <= 1 or pcm.stride(1) == 1) and pcm.dtype in (torch.float32, torch.int16)
+    B, n = pcm.shape
+    cnt = _host_array(counts, np.int32)
+    assert cnt.shape[0] == B, "one count per row"
+    n_frames, stride = int(n_frames), int(stride)
+    if out is None:
+        out = torch.empty((B, n_frames, 1, 64, 96), dtype=out_dtype, device=pcm.device)
+    else:
+        assert out.is_cuda and out.is_contiguous() and out.dtype == out_dtype and tuple(out.shape) == (B, n_frames, 1, 64, 96)
+    if B == 0:
+        return out
+    pcm_code = {torch.float32: _lib.F32, torch.int16: _lib.I16}[pcm.dtype]
+    out_code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}[out_dtype]
+    tab = device_tables(pcm.device)
+    host = torch.empty(B, dtype=torch.int32, pin_memory=True)
+    host.numpy()[:] = cnt
+    d = host.to(pcm.device, non_blocking=True)
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("logmel_bags", _lib.lib().mla_logmel_bags, vp(pcm.data_ptr()), pcm_code, B, n, pcm.stride(0) if B > 1 else n,
+                          vp(d.data_ptr()), cnt.ctypes.data_as(vp), n_frames, stride, vp(tab.data_ptr()), vp(out.data_ptr()), out_code,
+                          _lib.stream_ptr()))
+    return out
+
+
 _melspec_tables = {}
 MELSPEC_AMIN = 1e-10      # librosa.power_to_db's default amin (ref = 1.0)
 

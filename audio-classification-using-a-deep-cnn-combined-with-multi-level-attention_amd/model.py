@@ -142,8 +142,8 @@ class Ensemble(nn.Module):
     def _recordings_only_resnet(self, what):
         if self.cnn_type != "resnet":
             raise NotImplementedError("%s cuts and zero-fills 4 s clips for the ResNet branch; cnn_type 'vggish' does not zero-fill "
-                                      "the waveform (its native path pads missing 0.96 s slots of the spectrogram with 0.0) and "
-                                      "takes 16 kHz PCM through forward_waveforms()" % what)
+                                      "the waveform (its native path pads missing 0.96 s slots of the spectrogram with 0.0): use "
+                                      "%s_native(), or forward_waveforms() for 16 kHz PCM" % (what, what))
 
     def forward_recordings(self, recordings, rates, overlap=True):
         """The ResNet branch from recordings as they are decoded: a sequence of host arrays, (n,) or (n, channels), int16 or
@@ -165,6 +165,38 @@ class Ensemble(nn.Module):
         self._recordings_only_resnet("forward_audiofiles")
         from . import dataset
         return self.forward_clips(dataset.audiofiles_to_clips(paths), overlap)
+
+    def _native_bags(self, what, frames_fn, source, overlap):
+        """The VGGish branch from recordings: the reference's native dataset path (load_hdf5(cnn_type="vggish", use_librosa=False),
+        mnemonic vggish_native_10_s) in two launches, the bags written in the CNN's compute dtype, then the CNN and the head as
+        forward_waveforms runs them."""
+        if self.cnn_type != "vggish":
+            raise NotImplementedError("%s builds the VGGish branch's log-mel bags (the reference's native dataset path); cnn_type "
+                                      "'resnet' always takes the librosa path (dataset.py:176-178): use %s()"
+                                      % (what, what[:-len("_native")]))
+        if not overlap:
+            raise ValueError("%s: overlap=False gives 4 frames per bag, the model takes T = %d; the dataset functions "
+                             "(dataset.recordings_to_frames, ...) support it" % (what, T))
+        dtype = torch.bfloat16 if self.cnn.precision == "bf16" else torch.float32
+        frames = frames_fn(*source, overlap=True, out_dtype=dtype)
+        features = self.cnn(frames.view(frames.shape[0] * T, S_VGGISH_SHAPE[0], S_VGGISH_SHAPE[1]))        # Input's reshape (model.py:98-99), not a transpose
+        return self.mla(features.reshape(-1, T, self.emb_input_size))
+
+    def forward_recordings_native(self, recordings, rates, overlap=True):
+        """The VGGish branch from recordings as they are decoded (host arrays, (n,) or (n, channels), int16 or floating, any rates,
+        at most 4 whole 0.96 s examples each) -> dataset.recordings_to_frames -> (B, K) scores."""
+        from . import dataset
+        return self._native_bags("forward_recordings_native", dataset.recordings_to_frames, (recordings, rates), overlap)
+
+    def forward_wavfiles_native(self, paths, overlap=True):
+        """forward_recordings_native for 16-bit WAV files (dataset.wavfiles_to_frames)."""
+        from . import dataset
+        return self._native_bags("forward_wavfiles_native", dataset.wavfiles_to_frames, (paths,), overlap)
+
+    def forward_audiofiles_native(self, paths, overlap=True):
+        """forward_recordings_native for WAV files of any PCM width or IEEE float (dataset.audiofiles_to_frames)."""
+        from . import dataset
+        return self._native_bags("forward_audiofiles_native", dataset.audiofiles_to_frames, (paths,), overlap)
 
     def stream_waveforms(self, host_batches):
         """Host-resident PCM: iterate over (B, n_samples) float32 / int16 tensors in PINNED host memory and yield the

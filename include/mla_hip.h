@@ -112,6 +112,21 @@ int mla_mono_mix(const void* pcm, int pcm_dtype, int64_t n_samples, int channels
  * spec_c is the (64, 384) concatenation of the clip's <= 4 transposed examples, zero-padded. */
 int mla_dataset_frames(const float* examples, int64_t clips, int ex_per_clip, int n_frames, int frame_len,
                        int stride, float* out, mla_stream_t stream);
+/* dataset.create_spec (native path, dataset.py:318-324) + split (dataset.py:329-363) for a RAGGED batch, log-mel included: one
+ * launch from rows of 16 kHz mono PCM to the bag tensor load_hdf5(cnn_type="vggish", use_librosa=False) stores.
+ * pcm[clips][row_stride] (MLA_F32, or MLA_I16 scaled by 1/32768; the first n_samples of a row are valid input); counts[clips]
+ * (DEVICE, int32) says how many whole 0.96 s examples row c holds, 0..4; host_counts is the same array on the HOST, read for
+ * validation before anything is launched. (n_frames, stride) is (10, 32) (overlapping_split) or (4, 96) (contiguous_split).
+ * out[clips][n_frames][64][96], MLA_F32 or MLA_BF16 (one rounding of the f32 value), 16-byte aligned:
+ *   out[c][t][b][x] = spec_c[b][t * stride + x],  spec_c[b][96 s + f] = log-mel of band b, frame f of example s for s < counts[c],
+ * exactly 0.0 for s >= counts[c] (the reference pads missing slots of the spectrogram with 0.0, not ln 0.01) -- the bits
+ * mla_logmel_examples + mla_dataset_frames give for the same samples. Every element of out is written exactly once; no spectrum
+ * is computed for an absent slot and no sample beyond 15 600 + 15 360 (counts[c] - 1) of a row is read.
+ * Errors, all before any launch: null pointer, count outside 0..4 -> MLA_E_ARG; a count whose samples exceed n_samples, another
+ * (n_frames, stride) -> MLA_E_SHAPE; dtype codes -> MLA_E_DTYPE. clips == 0 returns MLA_OK and touches nothing. */
+int mla_logmel_bags(const void* pcm, int pcm_dtype, int64_t clips, int64_t n_samples, int64_t row_stride, const int32_t* counts,
+                    const int32_t* host_counts, int n_frames, int stride, const float* tables, void* out, int out_dtype,
+                    mla_stream_t stream);
 /* ---- ResNet branch front-end: dataset.create_spec(cnn_type="resnet") + split (dataset.py:309-316, :329-363) ----
  * librosa.feature.melspectrogram(y, sr, n_mels=n_mels, hop_length=hop) with its defaults (n_fft = win_length = 2048,
  * periodic Hann, center=True, pad_mode="reflect", power 2, Slaney mel basis over 0..sr/2, norm="slaney") followed by
