@@ -5,6 +5,7 @@
 // full argument space on the GPU. They are simple (one workgroup per frame, radix-2 FFT in LDS,
 // dense mel product) and not tuned.
 #include "common.h"
+#include "resample_core.h"
 
 namespace {
 
@@ -140,15 +141,11 @@ __global__ __launch_bounds__(128) void postprocess_kernel(const float* __restric
 }
 }  // namespace
 
-template <typename T>
-__global__ __launch_bounds__(256) void mono_mix_kernel(const T* __restrict__ pcm, int64_t n, int channels, double scale,
-                                                        float* __restrict__ out) {
+// one lane per frame: the channel mean of resample_core.h (sum in double, exact for int16; scale; one rounding)
+template <int FMT>
+__global__ __launch_bounds__(256) void mono_mix_kernel(const unsigned char* __restrict__ pcm, int64_t n, int channels, float* __restrict__ out) {
     const int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-    if (i >= n) return;
-    const T* p = pcm + i * channels;
-    double acc = 0.0;                       // numpy's pairwise order is irrelevant: exact for int16, < 1 ulp of f64 for float
-    for (int c = 0; c < channels; ++c) acc += double(p[c]);
-    out[i] = float(acc / double(channels) * scale);
+    if (i < n) out[i] = resample_core::mono_mix_as<FMT>(pcm, i, channels);
 }
 
 // ---- resampling to 16 kHz (vggish_input.py:52-53: resampy.resample(data, sample_rate, 16000), filter 'kaiser_best') ----
@@ -156,41 +153,18 @@ __global__ __launch_bounds__(256) void mono_mix_kernel(const T* __restrict__ pcm
 // t / ratio; it is the inner product of the input with the Kaiser-windowed sinc centred there, the filter read from a table of
 // `num_table` entries per zero crossing with linear interpolation between entries (win + eta * delta), left wing over
 // x[n], x[n-1], ..., right wing over x[n+1], x[n+2], ...; for ratio < 1 the table is stepped by int(ratio * num_table) entries per
-// input sample (the time-stretched, gain-scaled low-pass). One lane per output sample; the ~2 * 64 / min(1, ratio) taps of a
-// lane read consecutive input samples (L1/L2-resident: neighbouring lanes share all but one) and a table that fits L2 (512 KB
-// in double precision). Double accumulation like the reference's float64 arrays; latency-bound, not a roofline kernel
-// (a 10 s clip at 44.1 kHz is 160 000 outputs x 354 taps = 57 MFMA-free MFLOP).
+// input sample (the time-stretched, gain-scaled low-pass). The arithmetic is resample_core.h's setup() and wings(), shared with
+// the clips kernel. One lane per output sample; the ~2 * 64 / min(1, ratio) taps of a lane read consecutive input samples
+// (L1/L2-resident: neighbouring lanes share all but one) and a table that fits L2 (512 KB in double precision). Double
+// accumulation like the reference's float64 arrays; latency-bound, not a roofline kernel (a 10 s clip at 44.1 kHz is
+// 160 000 outputs x 354 taps = 57 MFMA-free MFLOP).
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, int64_t n_in, const double* __restrict__ win,
                                                        const double* __restrict__ delta, int nwin, int num_table, double ratio,
                                                        float* __restrict__ y, int64_t n_out) {
+    using namespace resample_core;
     const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (t >= n_out) return;
-    const double scale = ratio < 1.0 ? ratio : 1.0;
-    const int index_step = int(scale * num_table);
-    const double treg = double(t) * (1.0 / ratio);
-    const int64_t n = int64_t(treg);
-    double acc = 0.0;
-    double frac = scale * (treg - double(n));
-    double index_frac = frac * num_table;
-    int offset = int(index_frac);
-    double eta = index_frac - offset;
-    int64_t i_max = (nwin - offset) / index_step;
-    if (n + 1 < i_max) i_max = n + 1;
-    for (int64_t i = 0; i < i_max; ++i) {
-        const int idx = offset + int(i) * index_step;
-        acc += (win[idx] + eta * delta[idx]) * double(x[n - i]);
-    }
-    frac = scale - frac;
-    index_frac = frac * num_table;
-    offset = int(index_frac);
-    eta = index_frac - offset;
-    int64_t k_max = (nwin - offset) / index_step;
-    if (n_in - n - 1 < k_max) k_max = n_in - n - 1;
-    for (int64_t k = 0; k < k_max; ++k) {
-        const int idx = offset + int(k) * index_step;
-        acc += (win[idx] + eta * delta[idx]) * double(x[n + k + 1]);
-    }
-    y[t] = float(acc);
+    y[t] = float(wings(setup(t, ratio, num_table), x, 0, n_in, SplitTable{win, delta}, nwin, index_step_of(ratio, num_table)));
 }
 
 extern "C" int64_t mla_resample_length(int64_t n_in, double sr_in, double sr_out) {
@@ -205,7 +179,7 @@ extern "C" int mla_resample(const float* x, int64_t n_in, double sr_in, double s
                 (long long)n_out, (long long)mla_resample_length(n_in, sr_in, sr_out));
     MLA_REQUIRE(n_out >= 1, MLA_E_SHORT, "input of %lld samples is too short to resample from %g to %g Hz", (long long)n_in, sr_in, sr_out);
     const double ratio = sr_out / sr_in;
-    MLA_REQUIRE(int((ratio < 1.0 ? ratio : 1.0) * num_table) >= 1, MLA_E_SHAPE, "ratio %g is below the filter table's resolution", ratio);
+    MLA_REQUIRE(resample_core::index_step_of(ratio, num_table) >= 1, MLA_E_SHAPE, "ratio %g is below the filter table's resolution", ratio);
     MLA_REQUIRE(x && win && delta && y, MLA_E_ARG, "null resample buffers");
     hipLaunchKernelGGL(resample_kernel, dim3(unsigned((n_out + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, n_in, win,
                        delta, nwin, num_table, ratio, y, n_out);
@@ -220,12 +194,8 @@ extern "C" int mla_mono_mix(const void* pcm, int pcm_dtype, int64_t n_samples, i
     MLA_REQUIRE(pcm && out, MLA_E_ARG, "null pcm/out");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned grid = unsigned((n_samples + 255) / 256);
-    if (pcm_dtype == MLA_F32) {
-        hipLaunchKernelGGL(mono_mix_kernel<float>, dim3(grid), dim3(256), 0, s, static_cast<const float*>(pcm), n_samples, channels, 1.0, out);
-    } else {
-        hipLaunchKernelGGL(mono_mix_kernel<int16_t>, dim3(grid), dim3(256), 0, s, static_cast<const int16_t*>(pcm), n_samples, channels,
-                           1.0 / 32768.0, out);
-    }
+    const auto kernel = pcm_dtype == MLA_F32 ? mono_mix_kernel<resample_core::kF32> : mono_mix_kernel<resample_core::kI16>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, static_cast<const unsigned char*>(pcm), n_samples, channels, out);
     MLA_LAUNCH_OK("mono_mix_kernel");
     return MLA_OK;
 }

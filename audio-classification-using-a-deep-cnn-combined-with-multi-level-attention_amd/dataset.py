@@ -137,25 +137,36 @@ def _checked_recordings(recordings, rates, sr):
     for i, (x, r) in enumerate(zip(recs, rates)):
         if r <= 0:
             raise ValueError("recording %d: Invalid sample rate: sr_orig=%r" % (i, r))
-        if float(r) != float(sr) and int(x.shape[0] * (float(sr) / float(r))) < 1:
-            raise ValueError("recording %d: Input signal length=%d is too small to resample from %s->%s" % (i, x.shape[0], r, sr))
+        _check_resamples(i, x.shape[0], r, sr)
     return recs, rates
+
+
+def _check_resamples(index, frames, rate, sr):
+    """resampy's refusal of an input whose resampled length is zero (a recording at `sr` already is not resampled)."""
+    if float(rate) != float(sr) and int(frames * (float(sr) / float(rate))) < 1:
+        raise ValueError("recording %d: Input signal length=%d is too small to resample from %s->%s" % (index, frames, rate, sr))
+
+
+def _packed_on_device(chunks, dtype, align=1):
+    """1-D host arrays -> (one device tensor holding them back to back, each starting on a multiple of `align` elements, the
+    element offset of each): one pinned buffer, one copy."""
+    dev = frontend._device()                                # no GPU: refused before any pinned memory is asked for
+    sizes = np.array([c.shape[0] for c in chunks], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum((sizes + align - 1) // align * align)[:-1]]).astype(np.int64)
+    host = torch.empty(int(offsets[-1] + sizes[-1]), dtype=dtype, pin_memory=True)
+    flat = host.numpy()
+    for c, o, s in zip(chunks, offsets, sizes):
+        flat[o:o + s] = c
+    return host.to(dev, non_blocking=True), offsets
 
 
 def _pack_recordings(recs, rates, sr, samples_num):
     if not recs:
         return torch.empty((0, int(samples_num)), dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu")
-    dev = frontend._device()
     frames = np.array([x.shape[0] for x in recs], dtype=np.int64)
     channels = np.array([1 if x.ndim == 1 else x.shape[1] for x in recs], dtype=np.int32)
-    sizes = frames * channels
-    offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    host = torch.empty(int(sizes.sum()), dtype=torch.int16 if recs[0].dtype == np.int16 else torch.float32, pin_memory=True)
-    flat = host.numpy()
-    for x, o, s in zip(recs, offsets, sizes):
-        flat[o:o + s] = x.reshape(-1)
-    return frontend.prepare_clips(host.to(dev, non_blocking=True), offsets, frames, channels, np.array(rates, dtype=np.float64), sr,
-                                  samples_num)
+    packed, offsets = _packed_on_device([x.reshape(-1) for x in recs], torch.int16 if recs[0].dtype == np.int16 else torch.float32)
+    return frontend.prepare_clips(packed, offsets, frames, channels, np.array(rates, dtype=np.float64), sr, samples_num)
 
 
 def read_wav16(path):
@@ -169,10 +180,15 @@ def read_wav16(path):
     return (pcm.reshape(-1, ch) if ch > 1 else pcm), sr
 
 
+def _read_wav16s(paths):
+    """read_wav16 on every path -> (recordings, rates)."""
+    decoded = [read_wav16(str(p)) for p in paths]
+    return [d[0] for d in decoded], [d[1] for d in decoded]
+
+
 def wavfiles_to_clips(paths, sr=SR_RESNET, samples_num=SAMPLES_NUM_RESNET):
     """16-bit WAV files -> (B, samples_num) clips: read_wav16 on every path, then recordings_to_clips."""
-    decoded = [read_wav16(str(p)) for p in paths]
-    return recordings_to_clips([d[0] for d in decoded], [d[1] for d in decoded], sr, samples_num)
+    return recordings_to_clips(*_read_wav16s(paths), sr, samples_num)
 
 
 # WAVE format tags read_audiofile refuses by name (everything but PCM, IEEE float and their extensible form is refused)
@@ -270,25 +286,17 @@ def _checked_audiofiles(paths, sr):
     if sr <= 0:
         raise ValueError("Invalid sample rate: sr_new=%r" % (sr,))
     for i, (_, (_, _, r, n)) in enumerate(files):
-        if float(r) != float(sr) and int(n * (float(sr) / float(r))) < 1:
-            raise ValueError("recording %d: Input signal length=%d is too small to resample from %s->%s" % (i, n, r, sr))
+        _check_resamples(i, n, r, sr)
     return files
 
 
 def _pack_audiofiles(files, sr, samples_num):
     if not files:
         return torch.empty((0, int(samples_num)), dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu")
-    dev = frontend._device()
-    sizes = np.array([d.shape[0] for d, _ in files], dtype=np.int64)
-    offsets = np.concatenate([[0], np.cumsum((sizes + 7) // 8 * 8)[:-1]]).astype(np.int64)
-    host = torch.empty(int(offsets[-1] + sizes[-1]), dtype=torch.uint8, pin_memory=True)
-    flat = host.numpy()
-    for (d, _), o, s in zip(files, offsets, sizes):
-        flat[o:o + s] = d
+    packed, offsets = _packed_on_device([d for d, _ in files], torch.uint8, align=8)
     code, ch, rate, frames = zip(*(desc for _, desc in files))
-    return frontend.prepare_clips_raw(host.to(dev, non_blocking=True), offsets, np.array(frames, dtype=np.int64),
-                                      np.array(ch, dtype=np.int32), np.array(rate, dtype=np.float64), np.array(code, dtype=np.int32),
-                                      sr, samples_num)
+    return frontend.prepare_clips_raw(packed, offsets, np.array(frames, dtype=np.int64), np.array(ch, dtype=np.int32),
+                                      np.array(rate, dtype=np.float64), np.array(code, dtype=np.int32), sr, samples_num)
 
 
 # ---- the VGGish branch from recordings: load_hdf5(cnn_type="vggish", use_librosa=False), dataset.py:239-254 -----------------------
@@ -337,8 +345,7 @@ def recordings_to_frames(recordings, rates, overlap=True, out_dtype=torch.float3
 
 def wavfiles_to_frames(paths, overlap=True, out_dtype=torch.float32):
     """16-bit WAV files -> (B, T, 1, 64, 96) bags: read_wav16 on every path (other widths are refused), then recordings_to_frames."""
-    decoded = [read_wav16(str(p)) for p in paths]
-    return recordings_to_frames([d[0] for d in decoded], [d[1] for d in decoded], overlap, out_dtype)
+    return recordings_to_frames(*_read_wav16s(paths), overlap, out_dtype)
 
 
 def audiofiles_to_frames(paths, overlap=True, out_dtype=torch.float32):

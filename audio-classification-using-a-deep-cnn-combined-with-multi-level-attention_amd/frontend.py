@@ -162,21 +162,43 @@ def clips_tables_host(scales):
     return np.concatenate([np.stack(_resample_filter(k)[:2], axis=1).reshape(-1) for k in scales])
 
 
-def _clips_out(out, B, samples_num, dev):
+def _clips_launch(label, packed, off, fr, ch, rt, fm, sr_out, samples_num, out):
+    """The launch behind prepare_clips (fm None: mla_clips_prepare, `off` in elements) and prepare_clips_raw (fm the format codes:
+    mla_clips_prepare_raw, `off` in bytes). The filter tables of the batch's scales are cached on the device; the descriptors
+    travel in one pinned buffer, offsets | frames | rates | channels | table index [| formats], and one copy."""
+    dev = packed.device
+    B = fr.shape[0]
+    assert all(a.shape[0] == B for a in (off, ch, rt) + (() if fm is None else (fm,))), "one descriptor entry per recording"
+    sr_out, samples_num = float(sr_out), int(samples_num)
     if out is None:
-        return torch.empty((B, samples_num), dtype=torch.float32, device=dev)
+        out = torch.empty((B, samples_num), dtype=torch.float32, device=dev)
     assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, samples_num)
-    return out
-
-
-def _clips_filters(rates, sr_out, dev):
-    """(scales, table index per recording, the device tables of these scales (cached), nwin, num_table) of one batch."""
-    scales, tab = clips_table_index(rates, sr_out)
+    if B == 0:
+        return out
+    scales, tab = clips_table_index(rt, sr_out)
     nwin, num_table = _resample_filter(1.0)[0].shape[0], _resample_filter(1.0)[2]
     tkey = (str(dev), scales)
     if tkey not in _clips_tables:
         _clips_tables[tkey] = torch.from_numpy(clips_tables_host(scales)).to(dev)
-    return scales, tab, _clips_tables[tkey], nwin, num_table
+    cols = [off, fr, ch, rt, tab] + ([] if fm is None else [fm])            # in the order the C entries take them
+    desc = torch.empty(sum(a.nbytes for a in cols), dtype=torch.uint8, pin_memory=True)
+    h, at, pos = desc.numpy(), [0] * len(cols), 0
+    for i in sorted(range(len(cols)), key=lambda i: -cols[i].itemsize):       # the 8-byte columns first, so every one is aligned
+        at[i] = pos
+        h[pos:pos + cols[i].nbytes].view(cols[i].dtype)[:] = cols[i]
+        pos += cols[i].nbytes
+    d = desc.to(dev, non_blocking=True)
+    vp = ctypes.c_void_p
+    L = _lib.lib()
+    if fm is None:
+        entry = (L.mla_clips_prepare, vp(packed.data_ptr()), _lib.I16 if packed.dtype == torch.int16 else _lib.F32, packed.shape[0])
+    else:
+        entry = (L.mla_clips_prepare_raw, vp(packed.data_ptr()), packed.shape[0])
+    from . import ops
+    _lib.check(ops._timed(label, *entry, B, *[vp(d.data_ptr() + o) for o in at], *[a.ctypes.data_as(vp) for a in cols], sr_out, samples_num,
+                          vp(_clips_tables[tkey].data_ptr()) if scales else None, len(scales), nwin, num_table, vp(out.data_ptr()),
+                          _lib.stream_ptr()))
+    return out
 
 
 def prepare_clips(packed, offsets, frames, channels, rates, sr_out, samples_num, out=None):
@@ -192,39 +214,13 @@ def prepare_clips(packed, offsets, frames, channels, rates, sr_out, samples_num,
     only and equals `resample(as_device_mono(x), rate, sr_out)` cut and zero-filled, bit for bit. `out`, when given, is
     overwritten completely."""
     assert packed.is_cuda and packed.dim() == 1 and packed.is_contiguous() and packed.dtype in (torch.int16, torch.float32)
-    dev = packed.device
-    off, fr = _host_array(offsets, np.int64), _host_array(frames, np.int64)
-    ch, rt = _host_array(channels, np.int32), _host_array(rates, np.float64)
-    B = fr.shape[0]
-    assert off.shape[0] == B and ch.shape[0] == B and rt.shape[0] == B, "one descriptor entry per recording"
-    sr_out, samples_num = float(sr_out), int(samples_num)
-    out = _clips_out(out, B, samples_num, dev)
-    if B == 0:
-        return out
-    scales, tab, tables, nwin, num_table = _clips_filters(rt, sr_out, dev)
-    desc = torch.empty(B * 32, dtype=torch.uint8, pin_memory=True)       # offsets | frames | rates | channels | table index
-    h = desc.numpy()
-    h[:8 * B].view(np.int64)[:] = off
-    h[8 * B:16 * B].view(np.int64)[:] = fr
-    h[16 * B:24 * B].view(np.float64)[:] = rt
-    h[24 * B:28 * B].view(np.int32)[:] = ch
-    h[28 * B:].view(np.int32)[:] = tab
-    d = desc.to(dev, non_blocking=True)
-    vp = ctypes.c_void_p
-    base = d.data_ptr()
-    hp = lambda a: a.ctypes.data_as(vp)
-    code = _lib.I16 if packed.dtype == torch.int16 else _lib.F32
-    from . import ops
-    _lib.check(ops._timed("clips_prepare", _lib.lib().mla_clips_prepare, vp(packed.data_ptr()), code, packed.shape[0], B,
-                          vp(base), vp(base + 8 * B), vp(base + 24 * B), vp(base + 16 * B), vp(base + 28 * B),
-                          hp(off), hp(fr), hp(ch), hp(rt), hp(tab), sr_out, samples_num,
-                          vp(tables.data_ptr()) if scales else None, len(scales), nwin, num_table, vp(out.data_ptr()), _lib.stream_ptr()))
-    return out
+    return _clips_launch("clips_prepare", packed, _host_array(offsets, np.int64), _host_array(frames, np.int64),
+                         _host_array(channels, np.int32), _host_array(rates, np.float64), None, sr_out, samples_num, out)
 
 
 def prepare_clips_raw(packed_bytes, byte_offsets, frames, channels, rates, formats, sr_out, samples_num, out=None):
     """prepare_clips for recordings that still are the bytes of their files' data chunks: the samples are decoded in the same
-    ONE launch (csrc/clips.hip, clips_raw_kernel), so a batch of mixed encodings is uploaded as it sits on disk.
+    ONE launch (csrc/clips.hip, the same clips_kernel), so a batch of mixed encodings is uploaded as it sits on disk.
 
     packed_bytes: 1-D uint8 device tensor, the data chunks (little endian, interleaved frames). byte_offsets: where each
     recording starts, a multiple of its sample size. formats: one code per recording, _lib.U8 / I16 / I24 / I32 (PCM, scaled
@@ -233,34 +229,9 @@ def prepare_clips_raw(packed_bytes, byte_offsets, frames, channels, rates, forma
     first, bit for bit, for every format but multi-channel 32-bit PCM, whose integers are summed exactly and rounded once. No byte
     outside a recording's own range is read. `out`, when given, is overwritten completely."""
     assert packed_bytes.is_cuda and packed_bytes.dim() == 1 and packed_bytes.is_contiguous() and packed_bytes.dtype == torch.uint8
-    dev = packed_bytes.device
-    off, fr = _host_array(byte_offsets, np.int64), _host_array(frames, np.int64)
-    ch, rt, fm = _host_array(channels, np.int32), _host_array(rates, np.float64), _host_array(formats, np.int32)
-    B = fr.shape[0]
-    assert off.shape[0] == B and ch.shape[0] == B and rt.shape[0] == B and fm.shape[0] == B, "one descriptor entry per recording"
-    sr_out, samples_num = float(sr_out), int(samples_num)
-    out = _clips_out(out, B, samples_num, dev)
-    if B == 0:
-        return out
-    scales, tab, tables, nwin, num_table = _clips_filters(rt, sr_out, dev)
-    desc = torch.empty(B * 36, dtype=torch.uint8, pin_memory=True)       # offsets | frames | rates | channels | table index | formats
-    h = desc.numpy()
-    h[:8 * B].view(np.int64)[:] = off
-    h[8 * B:16 * B].view(np.int64)[:] = fr
-    h[16 * B:24 * B].view(np.float64)[:] = rt
-    h[24 * B:28 * B].view(np.int32)[:] = ch
-    h[28 * B:32 * B].view(np.int32)[:] = tab
-    h[32 * B:].view(np.int32)[:] = fm
-    d = desc.to(dev, non_blocking=True)
-    vp = ctypes.c_void_p
-    base = d.data_ptr()
-    hp = lambda a: a.ctypes.data_as(vp)
-    from . import ops
-    _lib.check(ops._timed("clips_prepare_raw", _lib.lib().mla_clips_prepare_raw, vp(packed_bytes.data_ptr()), packed_bytes.shape[0], B,
-                          vp(base), vp(base + 8 * B), vp(base + 24 * B), vp(base + 16 * B), vp(base + 28 * B), vp(base + 32 * B),
-                          hp(off), hp(fr), hp(ch), hp(rt), hp(tab), hp(fm), sr_out, samples_num,
-                          vp(tables.data_ptr()) if scales else None, len(scales), nwin, num_table, vp(out.data_ptr()), _lib.stream_ptr()))
-    return out
+    return _clips_launch("clips_prepare_raw", packed_bytes, _host_array(byte_offsets, np.int64), _host_array(frames, np.int64),
+                         _host_array(channels, np.int32), _host_array(rates, np.float64), _host_array(formats, np.int32),
+                         sr_out, samples_num, out)
 
 
 def waveforms_to_examples(pcm, out_dtype=torch.float32, out=None):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What decoding WAV files on the device costs or buys (dataset.audiofiles_to_clips, csrc/clips.hip clips_raw_kernel): one batch of
+"""What decoding WAV files on the device costs or buys (dataset.audiofiles_to_clips, csrc/clips.hip clips_kernel on file bytes): one batch of
 four-second stereo files at 44.1 kHz, written once to a temporary directory as 16-bit PCM, 24-bit PCM and float32 copies of the same
 audio, and six ways from the first byte read to the (files, 88 200) clips tensor, timed alternately round by round in one process
 on one device (host clock around work that ends in a device synchronise; warm-up rounds first; median, minimum and maximum):

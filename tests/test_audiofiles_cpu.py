@@ -1,5 +1,5 @@
 """WAV files of any PCM width or IEEE float -> clips, without a GPU: the RIFF reader and the host decoder (dataset.read_audiofile,
-decode_audiofile) against scipy.io.wavfile, the refusals, the new kernel's arithmetic simulated on the host workgroup by workgroup
+decode_audiofile) against scipy.io.wavfile, the refusals, the kernel's decode of file bytes simulated on the host workgroup by workgroup
 (csrc/clips_hostsim.cpp, hostsim_clips_prepare_raw) on a batch of mixed encodings against the float64 chain of test_clips_cpu.py, the
 C ABI's argument errors, and the pins of the 16-bit-only entries.
 
@@ -11,14 +11,14 @@ import ctypes
 import importlib
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 from scipy.io import wavfile
 
-from conftest import PKG, ROOT
-from test_clips_cpu import CASES, PASSTHROUGH, SAMPLES_NUMS, SR_OUT, TOL, cut_and_fill, resampled_f64
+from conftest import PKG
+from test_clips_cpu import CASES, PASSTHROUGH, SAMPLES_NUMS, SR_OUT, TOL, cut_and_fill, resampled_f64, run_hostsim
+from test_clips_cpu import hostsim  # noqa: F401  (the fixture: one build of csrc/clips_hostsim.cpp for both modules' tests)
 
 F32, I16, F64, I32, U8, I24 = 0, 2, 4, 5, 6, 7
 BYTES = {U8: 1, I16: 2, I24: 3, I32: 4, F32: 4, F64: 8}
@@ -275,21 +275,7 @@ def test_python_errors_come_before_the_device_is_touched(ds, tmp_path):
     assert tuple(ds.audiofiles_to_clips([], samples_num=2000).shape) == (0, 2000)
 
 
-# ---- 3. the new kernel simulated on the host ----
-
-@pytest.fixture(scope="module")
-def hostsim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("clips_hostsim_raw") / "clips_hostsim.so")
-    src = os.path.join(ROOT, PKG, "csrc", "clips_hostsim.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, src], check=True)
-    lib = ctypes.CDLL(so)
-    vp, i64, ci, cd = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
-    lib.hostsim_clips_prepare.restype = i64
-    lib.hostsim_clips_prepare.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, cd, i64, vp, ci, ci, vp]
-    lib.hostsim_clips_prepare_raw.restype = i64
-    lib.hostsim_clips_prepare_raw.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, cd, i64, vp, ci, ci, vp]
-    return lib
-
+# ---- 3. the kernel on file bytes, simulated on the host ----
 
 def _tables(fe, rates):
     rates = np.array(rates, dtype=np.float64)
@@ -300,7 +286,7 @@ def _tables(fe, rates):
 
 def run_raw(hostsim, fe, ds, files, samples_num, guard):
     """Pack the files' data chunks (each on a multiple of 8 bytes, `guard` bytes of 0xFF before, between and after them: all-ones
-    bytes are NaN as float32 and as float64, and -1 or 255 as PCM) and run the simulated launch of clips_raw_kernel."""
+    bytes are NaN as float32 and as float64, and -1 or 255 as PCM) and run the simulated launch of mla_clips_prepare_raw."""
     read = [ds.read_audiofile(f[0]) for f in files]
     sizes = [d.shape[0] for d, _ in read]
     offsets, pos = [], guard
@@ -321,23 +307,6 @@ def run_raw(hostsim, fe, ds, files, samples_num, guard):
     return out, cap
 
 
-def run_typed(hostsim, fe, recordings, rates, samples_num):
-    """The existing simulated launch (hostsim_clips_prepare) on decoded recordings, all int16 or all float32."""
-    int16 = recordings[0].dtype == np.int16
-    frames = np.array([x.shape[0] for x in recordings], dtype=np.int64)
-    channels = np.array([1 if x.ndim == 1 else x.shape[1] for x in recordings], dtype=np.int32)
-    sizes = frames * channels
-    offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    packed = np.concatenate([x.reshape(-1) for x in recordings])
-    rates, tab, tables, nwin = _tables(fe, rates)
-    out = np.full((len(recordings), samples_num), np.nan, dtype=np.float32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    cap = hostsim.hostsim_clips_prepare(p(packed), 2 if int16 else 0, len(recordings), p(offsets), p(frames), p(channels), p(rates), p(tab),
-                                        float(SR_OUT), samples_num, p(tables), nwin, 512, p(out))
-    assert cap >= 0, cap
-    return out
-
-
 @pytest.mark.parametrize("samples_num", SAMPLES_NUMS)
 def test_raw_kernel_math_on_host(hostsim, fe, ds, batch_dir, samples_num):
     files = mixed_batch(batch_dir)
@@ -347,17 +316,17 @@ def test_raw_kernel_math_on_host(hostsim, fe, ds, batch_dir, samples_num):
     # (d) 0xFF guard bytes around every recording never reach an output
     guarded, _ = run_raw(hostsim, fe, ds, files, samples_num, guard=64)
     assert np.isfinite(guarded).all() and np.array_equal(guarded.view(np.uint32), got.view(np.uint32))
-    # (b) int16 and float32 recordings: the rows of the existing kernel on the same samples
+    # (b) int16 and float32 recordings: the rows of the element-offset entry on the same samples
     for code, dtype in ((I16, np.int16), (F32, np.float32)):
         rows = [i for i, f in enumerate(files) if f[1] == code]
         recs = [squeeze(wavfile.read(files[i][0])[1].reshape(files[i][4], -1)) for i in rows]
         assert rows and all(r.dtype == dtype for r in recs)
-        want = run_typed(hostsim, fe, recs, [files[i][2] for i in rows], samples_num)
+        want, _ = run_hostsim(hostsim, fe, recs, [files[i][2] for i in rows], samples_num)
         for k, i in enumerate(rows):
             assert np.array_equal(got[i].view(np.uint32), want[k].view(np.uint32)), files[i][0]
-    # every encoding but multi-channel 32-bit PCM: the rows of the existing kernel on the float32 decode
+    # every encoding but multi-channel 32-bit PCM: the rows of the element-offset entry on the float32 decode
     rows = [i for i in range(len(files)) if i != MULTI_I32]
-    want = run_typed(hostsim, fe, [ds.decode_audiofile(files[i][0])[0] for i in rows], [files[i][2] for i in rows], samples_num)
+    want, _ = run_hostsim(hostsim, fe, [ds.decode_audiofile(files[i][0])[0] for i in rows], [files[i][2] for i in rows], samples_num)
     for k, i in enumerate(rows):
         assert np.array_equal(got[i].view(np.uint32), want[k].view(np.uint32)), files[i][0]
     # a row depends on its own file only

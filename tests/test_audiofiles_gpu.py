@@ -1,5 +1,5 @@
-"""WAV files of any PCM width or IEEE float -> clips on the GPU (csrc/clips.hip, clips_raw_kernel): the mixed batch of
-tests/test_audiofiles_cpu.py against the float64 chain, the fully written output, bit-identity with the kernel it extends (the same files
+"""WAV files of any PCM width or IEEE float -> clips on the GPU (csrc/clips.hip, clips_kernel on file bytes): the mixed batch of
+tests/test_audiofiles_cpu.py against the float64 chain, the fully written output, bit-identity with the element-offset entry (the same files
 decoded to float32 on the host and sent through recordings_to_clips), rows that depend on their own file only, the last 24-bit sample
 of the buffer, and Ensemble.forward_audiofiles. The bound is test_clips_cpu.py's 2e-6 absolute."""
 

@@ -80,8 +80,18 @@ def fe():
     return importlib.import_module(PKG + ".frontend")
 
 
+_hostsim = {}
+
+
 @pytest.fixture(scope="module")
 def hostsim(tmp_path_factory):
+    """csrc/clips_hostsim.cpp as a ctypes library, built once per session; tests/test_audiofiles_cpu.py imports this fixture."""
+    if "lib" not in _hostsim:
+        _hostsim["lib"] = build_hostsim(tmp_path_factory)
+    return _hostsim["lib"]
+
+
+def build_hostsim(tmp_path_factory):
     so = str(tmp_path_factory.mktemp("clips_hostsim") / "clips_hostsim.so")
     src = os.path.join(ROOT, PKG, "csrc", "clips_hostsim.cpp")
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, src], check=True)
@@ -89,11 +99,14 @@ def hostsim(tmp_path_factory):
     vp, i64, ci, cd = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
     lib.hostsim_clips_prepare.restype = i64
     lib.hostsim_clips_prepare.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, cd, i64, vp, ci, ci, vp]
+    lib.hostsim_clips_prepare_raw.restype = i64
+    lib.hostsim_clips_prepare_raw.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, cd, i64, vp, ci, ci, vp]
     return lib
 
 
-def run_hostsim(hostsim, fe, recordings, rates, samples_num, guard=0):
-    """Pack `recordings` (with `guard` NaN elements between them for float input) and run the simulated launch."""
+def pack(recordings, guard=0):
+    """(packed, element offsets, frames, channels) of `recordings`, all int16 or all float32, back to back with `guard` elements
+    (NaN for float input, 0 for int16) before, between and after them."""
     int16 = recordings[0].dtype == np.int16
     frames = np.array([x.shape[0] for x in recordings], dtype=np.int64)
     channels = np.array([1 if x.ndim == 1 else x.shape[1] for x in recordings], dtype=np.int32)
@@ -102,14 +115,26 @@ def run_hostsim(hostsim, fe, recordings, rates, samples_num, guard=0):
     packed = np.full(int((sizes + guard).sum()) + guard, 0 if int16 else np.nan, dtype=np.int16 if int16 else np.float32)
     for x, o, s in zip(recordings, offsets, sizes):
         packed[o:o + s] = x.reshape(-1)
+    return packed, offsets, frames, channels
+
+
+def run_hostsim(hostsim, fe, recordings, rates, samples_num, guard=0, as_bytes=False):
+    """Pack `recordings` and run the simulated launch of mla_clips_prepare (element offsets) or, as_bytes, of mla_clips_prepare_raw
+    on the same buffer viewed as bytes: offsets x sample size, one format code for all."""
+    int16 = recordings[0].dtype == np.int16
+    packed, offsets, frames, channels = pack(recordings, guard)
     rates = np.array(rates, dtype=np.float64)
     scales, tab = fe.clips_table_index(rates, float(SR_OUT))
     tables = fe.clips_tables_host(scales)
     nwin = len(tables) // (2 * max(len(scales), 1))
     out = np.full((len(recordings), samples_num), np.nan, dtype=np.float32)
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    cap = hostsim.hostsim_clips_prepare(p(packed), 2 if int16 else 0, len(recordings), p(offsets), p(frames), p(channels), p(rates), p(tab),
-                                        float(SR_OUT), samples_num, p(tables), nwin if scales else 32769, 512, p(out))
+    code, tail = 2 if int16 else 0, (p(rates), p(tab), float(SR_OUT), samples_num, p(tables), nwin if scales else 32769, 512, p(out))
+    if as_bytes:
+        byte_offsets, formats = offsets * packed.itemsize, np.full(len(recordings), code, dtype=np.int32)
+        cap = hostsim.hostsim_clips_prepare_raw(p(packed), len(recordings), p(byte_offsets), p(frames), p(channels), p(formats), *tail)
+    else:
+        cap = hostsim.hostsim_clips_prepare(p(packed), code, len(recordings), p(offsets), p(frames), p(channels), *tail)
     assert cap >= 0, cap
     return out, cap
 
@@ -138,6 +163,19 @@ def test_kernel_math_on_host_matches_float64_chain(hostsim, fe, samples_num, int
     # 192 kHz: int(255 / ratio) + 3 + 2 * (32769 // 58) = 2220 + 3 + 1128 staged floats at the most
     assert cap == 3351
     check_rows(got, int16, samples_num, "host simulation")
+
+
+@pytest.mark.parametrize("int16", [False, True])
+def test_element_and_byte_offsets_give_the_same_rows(hostsim, fe, int16):
+    """One kernel serves both entries: the same packed buffer addressed in elements of one format and in bytes with a format code
+    per clip gives the same bits. 2000 is no multiple of the tile; the batch has odd element offsets (ALL_CASES)."""
+    recs = [make_recording(i, int16) for i in range(len(ALL_CASES))]
+    rates = [c[0] for c in ALL_CASES]
+    assert any(o % 2 for o in pack(recs)[1])
+    typed, cap = run_hostsim(hostsim, fe, recs, rates, 2000)
+    raw, cap_raw = run_hostsim(hostsim, fe, recs, rates, 2000, as_bytes=True)
+    assert cap == cap_raw == 3351 and np.isfinite(typed).all()
+    assert np.array_equal(typed.view(np.uint32), raw.view(np.uint32))
 
 
 def test_n_res_of_the_cases():

@@ -12,7 +12,7 @@ import torch
 
 import librosa_restated as R
 from conftest import PKG
-from test_clips_cpu import ALL_CASES, CASES, SAMPLES_NUMS, SR_OUT, TOL, check_rows, cut_and_fill, make_recording, resampled_f64
+from test_clips_cpu import ALL_CASES, CASES, SAMPLES_NUMS, SR_OUT, TOL, check_rows, cut_and_fill, make_recording, pack, resampled_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -53,6 +53,21 @@ def test_low_level_entry_writes_all_of_out(fe):
                                torch.tensor(RATES, dtype=torch.float64).cuda(), SR_OUT, samples_num, out=out)
         assert ret is out and not bool(torch.isnan(out).any())
         check_rows(out.cpu().numpy(), False, samples_num, "MI355X, prepare_clips")
+
+
+@pytest.mark.parametrize("int16", [False, True])
+def test_element_and_byte_offsets_give_the_same_rows(fe, int16):
+    """One kernel serves both entries: the same packed buffer through prepare_clips (element offsets) and through prepare_clips_raw
+    (viewed as bytes, offsets x sample size, one format code for all) gives the same bits."""
+    L = importlib.import_module(PKG + "._lib")
+    recs = [make_recording(i, int16) for i in range(len(ALL_CASES))]
+    host, offsets, frames, channels = pack(recs)
+    packed = torch.from_numpy(host).cuda()
+    typed = fe.prepare_clips(packed, offsets, frames, channels, RATES, SR_OUT, 2000)
+    formats = np.full(len(recs), L.I16 if int16 else L.F32, dtype=np.int32)
+    raw = fe.prepare_clips_raw(packed.view(torch.uint8), offsets * host.itemsize, frames, channels, RATES, formats, SR_OUT, 2000)
+    assert bool(torch.isfinite(typed).all())
+    assert torch.equal(typed.view(torch.int32), raw.view(torch.int32))
 
 
 def per_recording(fe, x, sr_in, samples_num):
