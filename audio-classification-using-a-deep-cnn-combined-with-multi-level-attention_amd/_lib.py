@@ -65,6 +65,16 @@ def lib():
         L.mla_melspec_workspace_bytes.argtypes = [i64, i64, i64]
         L.mla_melspec_db.argtypes = [vp, i64, i64, i64, i64, i64, cf, vp, vp, vp, vp]
         L.mla_melspec_images.argtypes = [vp, vp, i64, i64, i64, i64, cf, i64, i64, i64, vp, vp]
+        cd = ctypes.c_double
+        L.mla_melspec_band_table_floats.restype = i64
+        L.mla_melspec_band_table_floats.argtypes = [cd, i64, cd, cd, ci]
+        L.mla_melspec_build_band_tables.argtypes = [cd, i64, cd, cd, ci, vp]
+        L.mla_melspec_nopad_frames.restype = i64
+        L.mla_melspec_nopad_frames.argtypes = [i64, i64]
+        L.mla_melspec_nopad_workspace_bytes.restype = i64
+        L.mla_melspec_nopad_workspace_bytes.argtypes = [i64, i64, i64]
+        L.mla_melspec_nopad_db.argtypes = [vp, i64, i64, i64, i64, i64, cf, vp, i64, vp, vp, vp]
+        L.mla_melspec_nopad_bags.argtypes = [vp, vp, i64, i64, i64, i64, cf, i64, i64, i64, vp, ci, vp]
         L.mla_postprocess.argtypes = [vp, vp, vp, i64, vp, vp]
         L.mla_mono_mix.argtypes = [vp, ci, i64, ci, vp, vp]
         L.mla_split_bf16x3.argtypes = [vp, i64, i64, i64, vp, i64, i64, ci, vp]

@@ -11,10 +11,21 @@
 // A clip's result depends on nothing but its own samples: runs are cut per clip, never across the batch.
 //
 // melspec_images_kernel: reduces the clip's partial maxima (max is exact in any order), then a pure select + gather:
-// out[c][t][0][band][x] = max(D[c][band][t * stride + x], Dmax_c - top_db).
+// out[c][t][0][band][x] = max(D[c][band][t * stride + x], Dmax_c - top_db), written as float32 or as bfloat16 (one rounding).
+//
+// melspec_nopad_db_kernel: the same spectrogram of UNPADDED frames (center=False; the VGGish branch's librosa path,
+// dataset.py:305-307, :316, with the HTK basis of mla_melspec_build_band_tables). A workgroup still owns a run of
+// consecutive frames of one clip and stages its samples once, but each of its four waves owns a whole frame: its own FFT
+// buffer, 4 butterflies per lane and stage, the powers written over the FFT in place, one lane per band in the mel sum
+// (weights in LDS). Lanes of a wave exchange data through LDS behind wave-level fences only; the workgroup meets at three
+// barriers per run (after staging, before the tile flush, in the maximum), all outside the frame loop. Per-lane arithmetic:
+// melspec_wave_core.h. Nothing outside a row's first n samples is read.
+#include <hip/hip_bf16.h>
+
 #include "common.h"
 #include "melspec_core.h"
 #include "melspec_tables.h"
+#include "melspec_wave_core.h"
 
 namespace {
 
@@ -71,9 +82,76 @@ __global__ __launch_bounds__(kThreads) void melspec_db_kernel(const float* __res
     if (t == 0) partial[blockIdx.x] = zr[0];
 }
 
+// orders the LDS traffic of one wave's lanes among themselves: everything before it is visible to every lane after it
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(kThreads) void melspec_nopad_db_kernel(const float* __restrict__ pcm, int64_t row_stride, int hop, int frames,
+                                                                    int runs, int per_run, const float* __restrict__ tab, int n_mels,
+                                                                    int nnz, float amin, float* __restrict__ D,
+                                                                    float* __restrict__ partial) {
+    extern __shared__ float lds[];
+    const int t = threadIdx.x, lane = t & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(t / kWave);
+    float* win = lds + kLdsWin;
+    float* tw = lds + kLdsTw;
+    float* stage = lds + kLdsStage;
+    float* z = lds + kWLdsFft + wave * kWaveFft;
+    float* wts = lds + kWLdsWeights;
+    float* tile = lds + wave_lds_tile(nnz);
+    const int64_t clip = blockIdx.x / runs;
+    const int run = int(blockIdx.x - clip * runs);
+    const int f0 = run * per_run;
+    const int nf = frames - f0 < per_run ? frames - f0 : per_run;
+    const int* meta = reinterpret_cast<const int*>(tab + kTabMeta);
+
+    for (int i = t; i < kFft + 2 * kTw; i += kThreads) lds[i] = tab[i];
+    for (int i = t; i < nnz; i += kThreads) wts[i] = tab[tab_weights(n_mels) + i];
+    stage_plain(t, pcm + clip * row_stride, int64_t(f0) * hop, kFft + (nf - 1) * hop, stage);
+    __syncthreads();
+    float best = -INFINITY;
+    const int rounds = (per_run + kWaves - 1) / kWaves;      // from kernel arguments only; no workgroup barrier inside the loop
+    for (int r = 0; r < rounds; ++r) {
+        const int f = r * kWaves + wave;
+        if (f < nf) {                                        // wave-uniform: an idle frame of the clip's last run is skipped by the whole wave
+            wave_fft_first(lane, stage + f * hop, win, z);
+            wave_sync();
+            for (int s = 1; s <= 4; ++s) {
+                wave_fft_stage(lane, s, tw, z);
+                wave_sync();
+            }
+            power_in_place(lane, tw, z);
+            wave_sync();
+            best = fmaxf(best, wave_mel_db(lane, z, meta, wts, n_mels, amin, f, tile));
+            wave_sync();                                     // the next frame's first stage overwrites the powers
+        }
+    }
+    __syncthreads();
+    float* out = D + clip * int64_t(n_mels) * frames + f0;
+    for (int i = t; i < n_mels * kRunFrames; i += kThreads) {
+        const int b = i / kRunFrames, f = i % kRunFrames;
+        if (f < nf) out[int64_t(b) * frames + f] = tile[i];
+    }
+    float* red = lds + kWLdsFft;                             // block maximum: the FFT buffers are dead here
+    red[t] = best;
+    __syncthreads();
+    for (int s = kThreads / 2; s > 0; s >>= 1) {
+        if (t < s) red[t] = fmaxf(red[t], red[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) partial[blockIdx.x] = red[0];
+}
+
+__device__ __forceinline__ void store_db(float* p, float v) { *p = v; }
+__device__ __forceinline__ void store_db(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }     // round to nearest even
+
+template <typename OutT>
 __global__ __launch_bounds__(256) void melspec_images_kernel(const float* __restrict__ D, const float* __restrict__ partial, int runs,
                                                              int n_mels, int frames, int n_images, int image_w, int stride,
-                                                             float top_db, int blocks_per_clip, float* __restrict__ out) {
+                                                             float top_db, int blocks_per_clip, OutT* __restrict__ out) {
     __shared__ float red[256];
     const int t = threadIdx.x;
     const int64_t clip = blockIdx.x / blocks_per_clip;
@@ -89,12 +167,12 @@ __global__ __launch_bounds__(256) void melspec_images_kernel(const float* __rest
     const float lo = red[0] - top_db;
     const int64_t per_clip = int64_t(n_images) * n_mels * image_w;
     const float* src = D + clip * int64_t(n_mels) * frames;
-    float* dst = out + clip * per_clip;
+    OutT* dst = out + clip * per_clip;
     for (int64_t i = int64_t(part) * 256 + t; i < per_clip; i += int64_t(blocks_per_clip) * 256) {
         const int x = int(i % image_w);
         const int64_t r = i / image_w;
         const int b = int(r % n_mels), img = int(r / n_mels);
-        dst[i] = fmaxf(src[int64_t(b) * frames + int64_t(img) * stride + x], lo);
+        store_db(dst + i, fmaxf(src[int64_t(b) * frames + int64_t(img) * stride + x], lo));
     }
 }
 
@@ -152,25 +230,111 @@ extern "C" int mla_melspec_db(const float* pcm, int64_t clips, int64_t n_samples
     return MLA_OK;
 }
 
-extern "C" int mla_melspec_images(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
-                                  float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, float* out, mla_stream_t stream) {
-    MLA_REQUIRE(clips >= 0, MLA_E_ARG, "melspec clips %lld < 0", (long long)clips);
-    if (int rc = check_signal(n_samples, hop, n_mels)) return rc;
+namespace {
+int check_images(int64_t frames, float top_db, int64_t n_images, int64_t image_w, int64_t image_stride) {
     MLA_REQUIRE(top_db >= 0.f, MLA_E_ARG, "melspec top_db must be non-negative (got %g)", double(top_db));
     MLA_REQUIRE(n_images >= 1 && image_w >= 1 && image_stride >= 0, MLA_E_ARG, "bad melspec image arguments (%lld images of width %lld, stride %lld)",
                 (long long)n_images, (long long)image_w, (long long)image_stride);
-    const int64_t frames = 1 + n_samples / hop, runs = runs_of(n_samples, hop);
     MLA_REQUIRE(image_w <= frames && image_stride <= frames && (n_images - 1) * image_stride + image_w <= frames, MLA_E_SHAPE,
                 "images leave the %lld-column spectrogram (%lld images of width %lld, stride %lld)", (long long)frames, (long long)n_images,
                 (long long)image_w, (long long)image_stride);
-    if (clips == 0) return MLA_OK;
-    MLA_REQUIRE(db && workspace && out, MLA_E_ARG, "null melspec argument");
+    return MLA_OK;
+}
+template <typename OutT>
+int launch_images(const float* db, const float* workspace, int64_t clips, int64_t frames, int64_t runs, int64_t n_mels, float top_db,
+                  int64_t n_images, int64_t image_w, int64_t image_stride, OutT* out, mla_stream_t stream) {
     const int64_t per_clip = n_images * n_mels * image_w;
     int64_t bpc = (per_clip + 2047) / 2048;
     bpc = bpc < 1 ? 1 : bpc > 1024 ? 1024 : bpc;
     MLA_REQUIRE(clips * bpc <= 0x7fffffffll && n_images <= 0x7fffffffll, MLA_E_SHAPE, "melspec image grid is too large");
-    hipLaunchKernelGGL(melspec_images_kernel, dim3(unsigned(clips * bpc)), dim3(256), 0, static_cast<hipStream_t>(stream), db, workspace,
+    hipLaunchKernelGGL(melspec_images_kernel<OutT>, dim3(unsigned(clips * bpc)), dim3(256), 0, static_cast<hipStream_t>(stream), db, workspace,
                        int(runs), int(n_mels), int(frames), int(n_images), int(image_w), int(image_stride), top_db, int(bpc), out);
     MLA_LAUNCH_OK("melspec_images_kernel");
     return MLA_OK;
+}
+}  // namespace
+
+extern "C" int mla_melspec_images(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
+                                  float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, float* out, mla_stream_t stream) {
+    MLA_REQUIRE(clips >= 0, MLA_E_ARG, "melspec clips %lld < 0", (long long)clips);
+    if (int rc = check_signal(n_samples, hop, n_mels)) return rc;
+    const int64_t frames = 1 + n_samples / hop, runs = runs_of(n_samples, hop);
+    if (int rc = check_images(frames, top_db, n_images, image_w, image_stride)) return rc;
+    if (clips == 0) return MLA_OK;
+    MLA_REQUIRE(db && workspace && out, MLA_E_ARG, "null melspec argument");
+    return launch_images(db, workspace, clips, frames, runs, n_mels, top_db, n_images, image_w, image_stride, out, stream);
+}
+
+// ---- the VGGish branch's librosa path: unpadded frames (center=False), any mel basis of mla_melspec_build_band_tables ----
+
+extern "C" int64_t mla_melspec_band_table_floats(double sr, int64_t n_mels, double fmin, double fmax, int htk) {
+    return melspec::table_floats(MelConfig{sr, n_mels, fmin, fmax, htk != 0});
+}
+
+extern "C" int mla_melspec_build_band_tables(double sr, int64_t n_mels, double fmin, double fmax, int htk, float* host_out) {
+    MLA_REQUIRE(host_out, MLA_E_ARG, "null melspec table buffer");
+    const MelConfig c{sr, n_mels, fmin, fmax, htk != 0};
+    MLA_REQUIRE(melspec::valid_config(c), MLA_E_ARG,
+                "melspec tables need sr > 0, 1 <= n_mels <= %d and 0 <= fmin < fmax <= sr / 2 (got sr %g, n_mels %lld, fmin %g, fmax %g)", kMaxMels,
+                sr, (long long)n_mels, fmin, fmax);
+    return melspec::build_tables(c, host_out) == 0 ? MLA_OK : ::mla::fail(MLA_E_ARG, "melspec tables could not be built");
+}
+
+extern "C" int64_t mla_melspec_nopad_frames(int64_t n_samples, int64_t hop) { return nopad_frames(n_samples, hop); }
+
+namespace {
+int check_nopad_signal(int64_t n_samples, int64_t hop, int64_t n_mels) {
+    MLA_REQUIRE(hop >= 1, MLA_E_ARG, "melspec hop %lld < 1", (long long)hop);
+    MLA_REQUIRE(n_mels >= 1 && n_mels <= kMaxMels, MLA_E_ARG, "melspec n_mels %lld outside [1, %d]", (long long)n_mels, kMaxMels);
+    MLA_REQUIRE(n_samples >= kFft, MLA_E_SHORT, "melspec without padding needs at least %d samples per clip, one whole frame (got %lld)", kFft,
+                (long long)n_samples);
+    MLA_REQUIRE(n_samples <= (1 << 30), MLA_E_SHAPE, "melspec clips longer than 2^30 samples are not supported (got %lld)", (long long)n_samples);
+    return MLA_OK;
+}
+int64_t nopad_runs_of(int64_t n_samples, int64_t hop) {
+    const int64_t frames = nopad_frames(n_samples, hop), per = wave_run_frames(hop);
+    return (frames + per - 1) / per;
+}
+}  // namespace
+
+extern "C" int64_t mla_melspec_nopad_workspace_bytes(int64_t clips, int64_t n_samples, int64_t hop) {
+    if (clips < 0 || n_samples < kFft || hop < 1) return -1;
+    return clips * nopad_runs_of(n_samples, hop) * int64_t(sizeof(float));
+}
+
+extern "C" int mla_melspec_nopad_db(const float* pcm, int64_t clips, int64_t n_samples, int64_t clip_stride, int64_t hop, int64_t n_mels,
+                                    float amin, const float* tables, int64_t table_floats, float* out_db, float* workspace,
+                                    mla_stream_t stream) {
+    MLA_REQUIRE(clips >= 0, MLA_E_ARG, "melspec clips %lld < 0", (long long)clips);
+    if (int rc = check_nopad_signal(n_samples, hop, n_mels)) return rc;
+    MLA_REQUIRE(clip_stride >= n_samples, MLA_E_ARG, "melspec clip stride %lld < n_samples %lld", (long long)clip_stride, (long long)n_samples);
+    MLA_REQUIRE(amin > 0.f, MLA_E_ARG, "melspec amin must be positive (got %g)", double(amin));
+    const int64_t nnz = table_floats - tab_weights(int(n_mels));
+    MLA_REQUIRE(nnz >= 0 && nnz <= kMaxWeights, MLA_E_ARG, "melspec table_floats %lld is not a table of %lld bands (%d + up to %d weights)",
+                (long long)table_floats, (long long)n_mels, tab_weights(int(n_mels)), kMaxWeights);
+    if (clips == 0) return MLA_OK;
+    MLA_REQUIRE(pcm && tables && out_db && workspace, MLA_E_ARG, "null melspec argument");
+    const int64_t frames = nopad_frames(n_samples, hop), per = wave_run_frames(hop), runs = nopad_runs_of(n_samples, hop);
+    MLA_REQUIRE(clips * runs <= 0x7fffffffll, MLA_E_SHAPE, "melspec grid of %lld workgroups is too large", (long long)(clips * runs));
+    const size_t lds = size_t(wave_lds_floats(int(n_mels), int(nnz))) * sizeof(float);
+    MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(melspec_nopad_db_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    hipLaunchKernelGGL(melspec_nopad_db_kernel, dim3(unsigned(clips * runs)), dim3(kThreads), lds, static_cast<hipStream_t>(stream), pcm,
+                       clip_stride, int(hop), int(frames), int(runs), int(per), tables, int(n_mels), int(nnz), amin, out_db, workspace);
+    MLA_LAUNCH_OK("melspec_nopad_db_kernel");
+    return MLA_OK;
+}
+
+extern "C" int mla_melspec_nopad_bags(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
+                                      float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, void* out, int out_dtype,
+                                      mla_stream_t stream) {
+    MLA_REQUIRE(clips >= 0, MLA_E_ARG, "melspec clips %lld < 0", (long long)clips);
+    if (int rc = check_nopad_signal(n_samples, hop, n_mels)) return rc;
+    MLA_REQUIRE(out_dtype == MLA_F32 || out_dtype == MLA_BF16, MLA_E_DTYPE, "out_dtype %d is neither MLA_F32 nor MLA_BF16", out_dtype);
+    if (int rc = check_images(nopad_frames(n_samples, hop), top_db, n_images, image_w, image_stride)) return rc;
+    if (clips == 0) return MLA_OK;
+    MLA_REQUIRE(db && workspace && out, MLA_E_ARG, "null melspec argument");
+    const int64_t frames = nopad_frames(n_samples, hop), runs = nopad_runs_of(n_samples, hop);
+    if (out_dtype == MLA_BF16)
+        return launch_images(db, workspace, clips, frames, runs, n_mels, top_db, n_images, image_w, image_stride, static_cast<__hip_bfloat16*>(out), stream);
+    return launch_images(db, workspace, clips, frames, runs, n_mels, top_db, n_images, image_w, image_stride, static_cast<float*>(out), stream);
 }

@@ -3,8 +3,9 @@ the native spectrogram path of ``create_spec`` (dataset.py:318-324) and ``split`
 ``overlapping_split`` / ``contiguous_split`` (dataset.py:329-363), i.e. the actual caller of
 ``waveform_to_examples`` in the reference's data pipeline. Same names and argument order; tensors
 stay on the GPU. The ResNet variant of the librosa path (dataset.py:308-316: melspectrogram + power_to_db with librosa's
-defaults) runs on the HIP kernels of csrc/melspec.hip; the VGGish variant of the librosa path (HTK, center=False), the
-UrbanSound8K fold logic and the HDF5 writer are outside scope.
+defaults) runs on the HIP kernels of csrc/melspec.hip, and so does the VGGish variant of the librosa path (dataset.py:305-307:
+HTK basis, center=False) through the ``*_librosa`` functions at the end of this file; the UrbanSound8K fold logic and the HDF5
+writer are outside scope.
 
 ``clips_to_frames`` is the batched fast path: PCM of many clips -> (clips, T, 1, 64, 96) in two
 kernels (fused log-mel + the re-framing gather), which is the tensor ``Input`` reshapes at
@@ -36,8 +37,8 @@ def create_spec(audio_array, cnn_type, sr, samples_num, x_size, y_size, use_libr
         hop = resnet_hop_length(samples_num, x_size, overlap)
         return frontend.melspectrogram_db(frontend.as_device_mono(audio_array)[None], sr, y_size, hop)[0]
     if use_librosa or cnn_type != "vggish":
-        raise NotImplementedError("of the librosa paths only cnn_type='resnet' is on the HIP hot path; VGGish runs the native "
-                                  "path (use_librosa=False)")
+        raise NotImplementedError("create_spec builds cnn_type='resnet' (always the librosa path) and the native VGGish path "
+                                  "(use_librosa=False); the VGGish librosa path (HTK mel-dB, center=False) is create_spec_librosa")
     ex = frontend.waveforms_to_examples(frontend.as_device_mono(audio_array)[None])
     if ex.shape[0] > 4:
         raise ValueError("could not broadcast input array from shape (%d,96,64) into shape (4,96,64)" % ex.shape[0])
@@ -356,3 +357,74 @@ def audiofiles_to_frames(paths, overlap=True, out_dtype=torch.float32):
     files = _checked_audiofiles(paths, SR_VGGISH)
     counts = _bag_counts([d[1][3] for d in files], [d[1][2] for d in files])
     return _bags(_pack_audiofiles(files, SR_VGGISH, SAMPLES_NUM_VGGISH), counts, overlap, out_dtype)
+
+
+# ---- the VGGish branch on the librosa path: load_hdf5(cnn_type="vggish", use_librosa=True), dataset.py:232-243, :305-307, :316 -------
+SAMPLES_NUM_VGGISH_LIBROSA = SR_VGGISH * 4       # 64 000: the reference's SAMPLES_NUM_VGGISH (params.py:10), the rows of this path
+LIBROSA_N_MELS, LIBROSA_HOP, LIBROSA_FMIN, LIBROSA_FMAX, LIBROSA_TOP_DB = 64, 160, 125.0, 7500.0, 80.0
+
+
+def create_spec_librosa(audio_array):
+    """create_spec(audio_array, "vggish", 16000, ..., use_librosa=True, ...) of the reference (dataset.py:305-307, :316) for one
+    clip of 16 kHz audio of any length from 2 048 samples on: librosa.feature.melspectrogram(y, sr=16000, n_mels=64,
+    hop_length=160, center=False, htk=True, fmin=125, fmax=7500) + power_to_db -> (64, 1 + (n - 2048) // 160) float32 dB values on
+    the device, clipped at the clip's maximum - 80. Shorter clips raise ValueError (librosa cannot frame them either)."""
+    pcm = frontend.as_device_mono(audio_array)[None]
+    return frontend.melspectrogram_db(pcm, SR_VGGISH, LIBROSA_N_MELS, LIBROSA_HOP, LIBROSA_TOP_DB, center=False, htk=True,
+                                      fmin=LIBROSA_FMIN, fmax=LIBROSA_FMAX)[0]
+
+
+def _librosa_overlap_only(what, overlap):
+    if not overlap:
+        raise ValueError("%s: overlap=False is not defined on the VGGish librosa path: the 388 columns give four whole 96-column "
+                         "frames and a fifth of width 4, which the reference's split refuses (dataset.py:361)" % what)
+
+
+def clips_to_frames_librosa(pcm, out_dtype=torch.float32):
+    """(clips, 64 000) float32 device PCM at 16 kHz -> (clips, T, 1, 64, 96), the tensor load_hdf5(cnn_type="vggish",
+    use_librosa=True) stores (dataset.py:243-254, mnemonic vggish_10_s) and Ensemble consumes, in TWO launches: the HTK mel-dB
+    spectrogram of unpadded frames (388 columns) and the top_db clip + the ten overlapping windows 32 columns apart, written in
+    `out_dtype` (float32 or bfloat16). Bit-identical to create_spec_librosa + split per clip. Rows are exactly 64 000 samples: the
+    caller cuts longer clips and zero-fills shorter ones, as load_hdf5 means to."""
+    assert pcm.dim() == 2
+    if pcm.shape[1] != SAMPLES_NUM_VGGISH_LIBROSA:
+        raise ValueError("clips_to_frames_librosa takes rows of exactly %d samples (%d s at %d Hz), got %d"
+                         % (SAMPLES_NUM_VGGISH_LIBROSA, SAMPLES_NUM_VGGISH_LIBROSA // SR_VGGISH, SR_VGGISH, pcm.shape[1]))
+    assert pcm.is_cuda
+    if pcm.dtype != torch.float32:
+        pcm = pcm.float()
+    x_size = 96
+    width = frontend.melspec_frames_librosa(SAMPLES_NUM_VGGISH_LIBROSA, LIBROSA_HOP)
+    db, ws = frontend.melspec_db_unclipped_librosa(pcm, SR_VGGISH, LIBROSA_N_MELS, LIBROSA_HOP, LIBROSA_FMIN, LIBROSA_FMAX, True)
+    return frontend.melspec_bags(db, ws, SAMPLES_NUM_VGGISH_LIBROSA, LIBROSA_HOP, LIBROSA_TOP_DB, T, x_size, (width - x_size) // (T - 1),
+                                 out_dtype)
+
+
+def recordings_to_frames_librosa(recordings, rates, overlap=True, out_dtype=torch.float32):
+    """Recordings as they are decoded -> the (B, T, 1, 64, 96) bags of the VGGish librosa path in THREE launches whatever B is:
+    recordings_to_clips at 16 kHz into rows of 64 000 samples (channel mean, resampy 'kaiser_best' resampling of the whole
+    recording, cut at 4 s, zero fill), then clips_to_frames_librosa's two. recordings / rates: as recordings_to_clips takes them,
+    with its errors. overlap=False raises ValueError. An empty sequence gives (0, T, 1, 64, 96)."""
+    _librosa_overlap_only("recordings_to_frames_librosa", overlap)
+    return _librosa_bags(recordings_to_clips(recordings, rates, SR_VGGISH, SAMPLES_NUM_VGGISH_LIBROSA), out_dtype)
+
+
+def _librosa_bags(clips, out_dtype):
+    if clips.shape[0] == 0:
+        return torch.empty((0, T, 1, 64, 96), dtype=out_dtype, device=clips.device)
+    return clips_to_frames_librosa(clips, out_dtype)
+
+
+def wavfiles_to_frames_librosa(paths, overlap=True, out_dtype=torch.float32):
+    """16-bit WAV files -> (B, T, 1, 64, 96) bags of the VGGish librosa path: read_wav16 on every path, then
+    recordings_to_frames_librosa."""
+    _librosa_overlap_only("wavfiles_to_frames_librosa", overlap)
+    return recordings_to_frames_librosa(*_read_wav16s(paths), overlap, out_dtype)
+
+
+def audiofiles_to_frames_librosa(paths, overlap=True, out_dtype=torch.float32):
+    """WAV files of any mixture of encodings read_audiofile accepts -> (B, T, 1, 64, 96) bags of the VGGish librosa path, in three
+    launches: audiofiles_to_clips at 16 kHz / 64 000 samples (the files' bytes decoded in the clips launch), then
+    clips_to_frames_librosa's two."""
+    _librosa_overlap_only("audiofiles_to_frames_librosa", overlap)
+    return _librosa_bags(audiofiles_to_clips(paths, SR_VGGISH, SAMPLES_NUM_VGGISH_LIBROSA), out_dtype)

@@ -343,11 +343,88 @@ def melspec_images(db, ws, n_samples, hop_length, top_db, n_images, image_w, ima
     return out
 
 
-def melspectrogram_db(pcm, sr, n_mels, hop_length, top_db=80.0):
+def melspec_band_tables(device, sr, n_mels, fmin, fmax, htk):
+    """melspec_tables for any mel basis librosa.filters.mel(sr, 2048, n_mels, fmin, fmax, htk) builds (norm="slaney")."""
+    key = (str(device), float(sr), int(n_mels), float(fmin), float(fmax), bool(htk))
+    if key not in _melspec_tables:
+        L = _lib.lib()
+        cfg = (float(sr), int(n_mels), float(fmin), float(fmax), int(bool(htk)))
+        n = int(L.mla_melspec_band_table_floats(*cfg))
+        if n < 0:
+            raise ValueError("the mel basis needs sr > 0, 1 <= n_mels <= 1024 and 0 <= fmin < fmax <= sr / 2 (got sr=%r, n_mels=%r, "
+                             "fmin=%r, fmax=%r)" % (sr, n_mels, fmin, fmax))
+        host = np.zeros(n, dtype=np.float32)
+        _lib.check(L.mla_melspec_build_band_tables(*cfg, host.ctypes.data_as(ctypes.c_void_p)))
+        _melspec_tables[key] = torch.from_numpy(host).to(device)
+    return _melspec_tables[key]
+
+
+def melspec_frames_librosa(n_samples, hop_length):
+    """Spectrogram columns without padding (center=False): 1 + (n_samples - 2048) // hop_length; -1 below one whole frame."""
+    return int(_lib.lib().mla_melspec_nopad_frames(int(n_samples), int(hop_length)))
+
+
+def _check_nopad(n, hop_length):
+    if n < 2048:
+        raise ValueError("without padding (center=False) a clip needs at least 2048 samples, one whole frame (got %d)" % n)
+    if int(hop_length) < 1:
+        raise ValueError("hop_length must be a positive integer (got %r)" % (hop_length,))
+
+
+def melspec_db_unclipped_librosa(pcm, sr, n_mels, hop_length, fmin=0.0, fmax=None, htk=False):
+    """melspec_db_unclipped on UNPADDED frames (librosa's center=False) with the mel basis (fmin, fmax, htk): (clips, n) device PCM
+    -> ((clips, n_mels, 1 + (n - 2048) // hop_length) dB values before the top_db clip, the workspace of per-clip partial maxima that
+    melspec_bags reads). Kernel 1 of the VGGish branch's librosa path (csrc/melspec.hip, melspec_nopad_db_kernel)."""
+    assert pcm.dim() == 2 and pcm.is_cuda and pcm.dtype == torch.float32 and (pcm.shape[1] <= 1 or pcm.stride(1) == 1)
+    clips, n = pcm.shape
+    _check_nopad(n, hop_length)
+    L = _lib.lib()
+    tab = melspec_band_tables(pcm.device, sr, n_mels, fmin, float(sr) / 2 if fmax is None else fmax, htk)
+    ws = torch.empty(int(L.mla_melspec_nopad_workspace_bytes(clips, n, int(hop_length))) // 4, dtype=torch.float32, device=pcm.device)
+    db = torch.empty((clips, int(n_mels), melspec_frames_librosa(n, hop_length)), dtype=torch.float32, device=pcm.device)
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_nopad_db", L.mla_melspec_nopad_db, vp(pcm.data_ptr()), clips, n, pcm.stride(0) if clips > 1 else n,
+                          int(hop_length), int(n_mels), MELSPEC_AMIN, vp(tab.data_ptr()), tab.shape[0], vp(db.data_ptr()), vp(ws.data_ptr()),
+                          _lib.stream_ptr()))
+    return db, ws
+
+
+def melspec_bags(db, ws, n_samples, hop_length, top_db, n_images, image_w, image_stride, out_dtype=torch.float32):
+    """melspec_images for the spectrogram and workspace of melspec_db_unclipped_librosa, written in `out_dtype` (float32, or
+    bfloat16 by one rounding to nearest even): (clips, n_mels, frames) -> (clips, n_images, 1, n_mels, image_w). Kernel 2 of the
+    VGGish branch's librosa path: a select and a gather, bit-determined by `db`."""
+    clips, n_mels, _ = db.shape
+    _check_nopad(int(n_samples), hop_length)
+    out_code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}[out_dtype]
+    out = torch.empty((clips, int(n_images), 1, n_mels, int(image_w)), dtype=out_dtype, device=db.device)
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_nopad_bags", _lib.lib().mla_melspec_nopad_bags, vp(db.data_ptr()), vp(ws.data_ptr()), clips,
+                          int(n_samples), int(hop_length), n_mels, float(top_db), int(n_images), int(image_w), int(image_stride),
+                          vp(out.data_ptr()), out_code, _lib.stream_ptr()))
+    return out
+
+
+def melspectrogram_db(pcm, sr, n_mels, hop_length, top_db=80.0, center=True, htk=False, fmin=0.0, fmax=None):
     """librosa.power_to_db(librosa.feature.melspectrogram(y, sr=sr, n_mels=n_mels, hop_length=hop_length), top_db=top_db) with
     librosa's defaults (n_fft 2048, periodic Hann, centre reflect padding, power 2, Slaney mel basis; ref 1.0, amin 1e-10) for
     every row of `pcm`: (clips, n) float32 device PCM -> (clips, n_mels, 1 + n // hop_length) float32. top_db=None skips the clip.
-    Clips shorter than 1025 samples raise ValueError (reflect padding by 1024 needs them)."""
+    Clips shorter than 1025 samples raise ValueError (reflect padding by 1024 needs them).
+
+    center=False is librosa's unpadded framing, (clips, n_mels, 1 + (n - 2048) // hop_length) from 2048 samples on, and takes the
+    mel basis of melspectrogram's htk / fmin / fmax keywords (fmax None: sr / 2) -- the VGGish branch's librosa path is
+    (16000, 64, 160, center=False, htk=True, fmin=125, fmax=7500). With center=True only the default basis is built."""
+    if not center:
+        if top_db is not None and top_db < 0:
+            raise ValueError("top_db must be non-negative")
+        db, ws = melspec_db_unclipped_librosa(pcm, sr, n_mels, hop_length, fmin, fmax, htk)
+        if top_db is None:
+            return db
+        return melspec_bags(db, ws, pcm.shape[1], hop_length, top_db, 1, db.shape[2], 0)[:, 0, 0]
+    if htk or fmin != 0.0 or (fmax is not None and float(fmax) != float(sr) / 2):
+        raise NotImplementedError("the centred spectrogram is built with librosa's default mel basis only (htk=False, fmin=0, fmax=sr/2); "
+                                  "another basis runs with center=False")
     if pcm.shape[1] < 1025:
         raise ValueError("melspectrogram_db needs at least 1025 samples per clip (got %d)" % pcm.shape[1])
     if top_db is not None and top_db < 0:

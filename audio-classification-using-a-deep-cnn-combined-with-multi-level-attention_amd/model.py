@@ -135,7 +135,7 @@ class Ensemble(nn.Module):
         just_bottlenecks act as in forward()."""
         if self.cnn_type != "resnet":
             raise NotImplementedError("forward_clips feeds the ResNet branch's mel-dB images; cnn_type 'vggish' takes 16 kHz PCM "
-                                      "through forward_waveforms()")
+                                      "through forward_waveforms(), or 4 s clips of it through forward_clips_librosa()")
         from . import dataset
         return self.forward(dataset.clips_to_images(pcm, overlap))
 
@@ -143,7 +143,8 @@ class Ensemble(nn.Module):
         if self.cnn_type != "resnet":
             raise NotImplementedError("%s cuts and zero-fills 4 s clips for the ResNet branch; cnn_type 'vggish' does not zero-fill "
                                       "the waveform (its native path pads missing 0.96 s slots of the spectrogram with 0.0): use "
-                                      "%s_native(), or forward_waveforms() for 16 kHz PCM" % (what, what))
+                                      "%s_native(), or forward_waveforms() for 16 kHz PCM; the librosa dataset path, which does "
+                                      "zero-fill, is %s_librosa()" % (what, what, what))
 
     def forward_recordings(self, recordings, rates, overlap=True):
         """The ResNet branch from recordings as they are decoded: a sequence of host arrays, (n,) or (n, channels), int16 or
@@ -197,6 +198,42 @@ class Ensemble(nn.Module):
         """forward_recordings_native for WAV files of any PCM width or IEEE float (dataset.audiofiles_to_frames)."""
         from . import dataset
         return self._native_bags("forward_audiofiles_native", dataset.audiofiles_to_frames, (paths,), overlap)
+
+    def _librosa_bags(self, what, frames_fn, source, overlap):
+        """The VGGish branch on the reference's librosa dataset path (load_hdf5(cnn_type="vggish", use_librosa=True), mnemonic
+        vggish_10_s): HTK mel-dB bags written in the CNN's compute dtype, then the CNN and the head as _native_bags runs them."""
+        if self.cnn_type != "vggish":
+            raise NotImplementedError("%s builds the VGGish branch's HTK mel-dB bags (64 bands, unpadded frames); cnn_type 'resnet' "
+                                      "takes librosa's default spectrogram: use %s()" % (what, what[:-len("_librosa")]))
+        if not overlap:
+            raise ValueError("%s: overlap=False is not defined on the VGGish librosa path (388 columns do not split into whole "
+                             "96-column frames; the reference's split refuses it)" % what)
+        dtype = torch.bfloat16 if self.cnn.precision == "bf16" else torch.float32
+        frames = frames_fn(*source, out_dtype=dtype)
+        features = self.cnn(frames.view(frames.shape[0] * T, S_VGGISH_SHAPE[0], S_VGGISH_SHAPE[1]))        # Input's reshape (model.py:98-99), not a transpose
+        return self.mla(features.reshape(-1, T, self.emb_input_size))
+
+    def forward_clips_librosa(self, pcm, overlap=True):
+        """The VGGish branch's wave -> scores entry on the librosa path: (B, 64 000) float32 PCM at 16 kHz on the device ->
+        dataset.clips_to_frames_librosa (two HIP kernels) -> (B, K) scores."""
+        from . import dataset
+        return self._librosa_bags("forward_clips_librosa", dataset.clips_to_frames_librosa, (pcm,), overlap)
+
+    def forward_recordings_librosa(self, recordings, rates, overlap=True):
+        """forward_clips_librosa from recordings as they are decoded (host arrays, (n,) or (n, channels), int16 or floating, any
+        rates and lengths): dataset.recordings_to_frames_librosa cuts at 4 s and zero-fills."""
+        from . import dataset
+        return self._librosa_bags("forward_recordings_librosa", dataset.recordings_to_frames_librosa, (recordings, rates), overlap)
+
+    def forward_wavfiles_librosa(self, paths, overlap=True):
+        """forward_recordings_librosa for 16-bit WAV files (dataset.wavfiles_to_frames_librosa)."""
+        from . import dataset
+        return self._librosa_bags("forward_wavfiles_librosa", dataset.wavfiles_to_frames_librosa, (paths,), overlap)
+
+    def forward_audiofiles_librosa(self, paths, overlap=True):
+        """forward_recordings_librosa for WAV files of any PCM width or IEEE float (dataset.audiofiles_to_frames_librosa)."""
+        from . import dataset
+        return self._librosa_bags("forward_audiofiles_librosa", dataset.audiofiles_to_frames_librosa, (paths,), overlap)
 
     def stream_waveforms(self, host_batches):
         """Host-resident PCM: iterate over (B, n_samples) float32 / int16 tensors in PINNED host memory and yield the

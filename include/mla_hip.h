@@ -157,6 +157,36 @@ int mla_melspec_db(const float* pcm, int64_t clips, int64_t n_samples, int64_t c
 int mla_melspec_images(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
                        float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, float* out, mla_stream_t stream);
 
+/* ---- VGGish branch, librosa path: dataset.create_spec(cnn_type="vggish", use_librosa=True) + split (dataset.py:305-307, :316,
+ * :329-363): librosa.feature.melspectrogram(y, sr, n_mels=64, hop_length=160, center=False, htk=True, fmin=125, fmax=7500)
+ * followed by librosa.power_to_db, for a batch of clips. center=False: no padding, frame f is y[f * hop .. f * hop + 2047],
+ * frames = 1 + (n_samples - 2048) / hop; clips shorter than one frame (2048 samples) return MLA_E_SHORT. */
+
+/* The tables of mla_melspec_build_tables for any mel basis librosa.filters.mel(sr, 2048, n_mels, fmin, fmax, htk, norm="slaney")
+ * builds: htk != 0 is the HTK scale mel = 2595 log10(1 + hz / 700), htk == 0 the Slaney scale; 0 <= fmin < fmax <= sr / 2.
+ * (sr, n_mels, 0, sr / 2, 0) gives mla_melspec_build_tables' tables bit for bit. Same layout, same sparse form (a band without a
+ * bin centre inside it has a count of 0); -1 / MLA_E_ARG for an invalid configuration. */
+int64_t mla_melspec_band_table_floats(double sr, int64_t n_mels, double fmin, double fmax, int htk);
+int     mla_melspec_build_band_tables(double sr, int64_t n_mels, double fmin, double fmax, int htk, float* host_out);
+/* Spectrogram columns of a clip without padding: 1 + (n_samples - 2048) / hop (host; -1 for n_samples < 2048 or hop < 1). */
+int64_t mla_melspec_nopad_frames(int64_t n_samples, int64_t hop);
+/* Bytes of the per-clip partial maxima mla_melspec_nopad_db writes and mla_melspec_nopad_bags reads (-1 for bad arguments). */
+int64_t mla_melspec_nopad_workspace_bytes(int64_t clips, int64_t n_samples, int64_t hop);
+/* pcm[clips][clip_stride] f32 (the first n_samples of each row are used; nothing else is read) ->
+ * out_db[clips][n_mels][frames], 10 log10(max(amin, S)) WITHOUT the top_db clip, frames = mla_melspec_nopad_frames(n_samples, hop),
+ * and the workspace of partial maxima. `tables` is the device copy of either builder's tables for n_mels bands and
+ * `table_floats` their size (the packed weights are staged in LDS, at most 2050 of them). A clip's values depend on its own
+ * samples only: the same bits alone, in any batch and at any position. */
+int mla_melspec_nopad_db(const float* pcm, int64_t clips, int64_t n_samples, int64_t clip_stride, int64_t hop, int64_t n_mels,
+                         float amin, const float* tables, int64_t table_floats, float* out_db, float* workspace, mla_stream_t stream);
+/* mla_melspec_images for the spectrogram and workspace of mla_melspec_nopad_db, written as MLA_F32 or MLA_BF16 (one rounding to
+ * nearest even of the float32 value): out[clips][n_images][1][n_mels][image_w],
+ * out[c][t][0][b][x] = max(db[c][b][t * image_stride + x], max(db[c]) - top_db). With (10, 96, 32) on 388 columns of 64 bands
+ * this is the bag tensor the reference stores (dataset.py:252-255). Errors as mla_melspec_images; another dtype code is MLA_E_DTYPE. */
+int mla_melspec_nopad_bags(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
+                           float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, void* out, int out_dtype,
+                           mla_stream_t stream);
+
 /* vggish.Postprocessor.postprocess (vggish.py:62-102): PCA, clamp to [-2, 2], 8-bit quantisation
  * (as float). embeddings (rows, 128), pca_eigen_vectors (128, 128), pca_means (128). */
 int mla_postprocess(const float* embeddings, const float* pca_eigen_vectors, const float* pca_means, int64_t rows,
