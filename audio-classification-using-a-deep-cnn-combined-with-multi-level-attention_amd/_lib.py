@@ -101,6 +101,9 @@ def lib():
         L.mla_bn_bwd_sums.argtypes = [vp, i64, vp, i64, vp, i64, ci, cf, i64, i64, ci, ci, vp, vp, cf, vp, vp, vp]
         L.mla_bn_bwd_apply.argtypes = [vp, i64, vp, i64, vp, i64, ci, cf, i64, i64, ci, ci, vp, vp, vp, cf, vp, vp, cd,
                                        vp, i64, ci, vp, vp, vp]
+        L.mla_bn_bwd_sums_wide.argtypes = [vp, i64, vp, i64, vp, i64, ci, cf, i64, i64, vp, vp, cf, vp, vp, vp]
+        L.mla_bn_bwd_apply_wide.argtypes = [vp, i64, vp, i64, vp, i64, ci, cf, i64, i64, vp, vp, vp, cf, vp, vp, cd,
+                                            vp, i64, ci, vp, vp, vp]
         L.mla_attention_pool_bwd.argtypes = [vp, i64, vp, vp, i64, ci, ci, vp, vp, vp]
         L.mla_linear_small_bwd.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp]
         L.mla_transpose_f32.argtypes = [vp, i64, vp, i64, i64, i64, vp]

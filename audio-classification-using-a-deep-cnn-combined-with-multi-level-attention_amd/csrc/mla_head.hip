@@ -13,7 +13,8 @@
 //                         data-parallel ranks can all-reduce the sums in between (SyncBN).
 //   attention_pool(_bwd)  model.py:237-240: att = softmax_K(BNv(z)), cla = sigmoid(BNf(z)) on the
 //                         SAME z = fcv(h) (the reference never uses fcf), att normalised over T,
-//                         y = sum_T cla * att. 16 lanes per bag, shuffle reductions.
+//                         y = sum_T cla * att. 16 lanes per bag, shuffle reductions (T, K <= 16); wider
+//                         bags (T <= 64, K <= 1024) take one workgroup each, see attention_pool_wide_kernel.
 //   linear_small(_bwd)    model.py:255/:268 fc (L*K -> K): too small / unaligned for the MFMA GEMM.
 //
 // Reductions are deterministic: per-block double-precision partials in a caller-provided
@@ -23,7 +24,11 @@
 namespace {
 
 constexpr int kStatBlocks = 512;        // upper bound on partial-producing blocks
-constexpr int kMaxChannels = 64;
+constexpr int kMaxChannels = 64;         // row mode (period), and the column mode of sums_cols_kernel
+constexpr int kMaxWideChannels = 1024;  // column mode beyond that: sums_cols_wide_kernel
+constexpr int kWideRowBlocks = 32;      // its row blocks: 32 x 1024 channels of partials fill what 512 x 64 did
+constexpr int kMaxSlots = 64;           // wide attention pooling: T
+constexpr int kMaxClasses = 1024;       //                          K
 
 __device__ __forceinline__ double wave_sum(double v) {
     _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -152,6 +157,37 @@ __global__ __launch_bounds__(256) void sums_cols_kernel(Op op, int64_t rows, int
     }
 }
 
+// mode 1 with 64 < cols <= 1024: block (x, y) takes columns 64 x .. 64 x + 63 of row block y; wave g of its four walks rows
+// g, g + 4, ... (a wave-instruction reads 256 contiguous bytes of one row), then the four waves' sums are added in wave order.
+// Partials are laid out [row block][cols][2] as in sums_cols_kernel, so the same partial_reduce_kernel combines them.
+template <typename Op>
+__global__ __launch_bounds__(256) void sums_cols_wide_kernel(Op op, int64_t rows, int cols, double* __restrict__ partial) {
+    __shared__ double part[4][64][2];
+    const int g = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int c = int(blockIdx.x) * 64 + lane;
+    double s = 0.0, ss = 0.0;
+    if (c < cols) {
+        const int64_t per_block = (rows + gridDim.y - 1) / gridDim.y;
+        const int64_t r0 = int64_t(blockIdx.y) * per_block;
+        const int64_t r1 = r0 + per_block < rows ? r0 + per_block : rows;
+        for (int64_t r = r0 + g; r < r1; r += 4) {
+            double a, b;
+            op(r, c, c, a, b);
+            s += a;
+            ss += b;
+        }
+    }
+    part[g][lane][0] = s;
+    part[g][lane][1] = ss;
+    __syncthreads();
+    if (g == 0 && c < cols) {
+        double a = 0.0, b = 0.0;
+        for (int gg = 0; gg < 4; ++gg) { a += part[gg][lane][0]; b += part[gg][lane][1]; }
+        partial[(int64_t(blockIdx.y) * cols + c) * 2] = a;
+        partial[(int64_t(blockIdx.y) * cols + c) * 2 + 1] = b;
+    }
+}
+
 // fixed-order combination of the per-block partials -> sums[channel][2]: one wave per channel, lane l
 // adds blocks l, l + 64, ... then a shuffle tree (a single thread walking 512 strided partials per
 // channel took 110 us per call and 16 % of the training step)
@@ -205,9 +241,12 @@ int channel_sums(Op op, int64_t rows, int64_t cols, int mode, int period, void* 
         const int64_t groups = rows / period;
         blocks = int(groups < kStatBlocks ? groups : kStatBlocks);
         hipLaunchKernelGGL(sums_rows_kernel<Op>, dim3(blocks), dim3(256), 0, s, op, rows, int(cols), period, partial);
-    } else {
+    } else if (cols <= kMaxChannels) {
         blocks = int((rows + 63) / 64 < kStatBlocks ? (rows + 63) / 64 : kStatBlocks);
         hipLaunchKernelGGL(sums_cols_kernel<Op>, dim3(blocks), dim3(256), 0, s, op, rows, int(cols), partial);
+    } else {
+        blocks = int((rows + 63) / 64 < kWideRowBlocks ? (rows + 63) / 64 : kWideRowBlocks);
+        hipLaunchKernelGGL(sums_cols_wide_kernel<Op>, dim3(unsigned((cols + 63) / 64), blocks), dim3(256), 0, s, op, rows, int(cols), partial);
     }
     MLA_LAUNCH_OK("channel sums");
     if (finish && channels <= 16) {
@@ -223,7 +262,7 @@ int channel_sums(Op op, int64_t rows, int64_t cols, int mode, int period, void* 
 __global__ void stats_finish_kernel(const double* __restrict__ sums, int channels, double count, float* __restrict__ mean,
                                     float* __restrict__ var, float* __restrict__ run_mean, float* __restrict__ run_var,
                                     float momentum, int64_t* __restrict__ num_batches_tracked) {
-    const int c = threadIdx.x;
+    const int c = threadIdx.x;                                         // one block: 64 threads, 1024 for more than 64 channels
     if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;      // nn.BatchNorm1d's counter, advanced by the same launch
     if (c >= channels) return;
     const double m = sums[2 * c] / count;
@@ -269,9 +308,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BwdOp op, const float
                                                            float* __restrict__ dx, int64_t ld_dx, int accumulate,
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta) {
     const int channels = MODE == 0 ? period : cols;
-    if (blockIdx.x == 0 && threadIdx.x < channels && dgamma) {
-        dbeta[threadIdx.x] = float(sums_local[2 * threadIdx.x]);
-        dgamma[threadIdx.x] = float(sums_local[2 * threadIdx.x + 1]);
+    if (blockIdx.x == 0 && dgamma) {
+        for (int ch = threadIdx.x; ch < channels; ch += 256) {
+            dbeta[ch] = float(sums_local[2 * ch]);
+            dgamma[ch] = float(sums_local[2 * ch + 1]);
+        }
     }
     if (!dx) return;
     const int64_t total = rows * cols;
@@ -374,6 +415,106 @@ __global__ __launch_bounds__(256) void attention_pool_bwd_kernel(const float* __
     if (live) {
         _Pragma("unroll") for (int k = 0; k < KMAX; ++k)
             if (k < K) du_v[(bag * T + t) * K + k] = att[k] * (datt[k] - dot);
+    }
+}
+
+// ---- bags wider than the register kernels take (T <= 64, K <= 1024): ONE WORKGROUP PER BAG, the T x K tile re-read from L1 / L2
+// (21 KB at 10 x 527) instead of held in registers or LDS (256 KB at 64 x 1024). Softmax runs over k within a row, the pooling
+// sums over t within a column, so the two phases want the tile by rows and by columns:
+//   phase 1  wave w takes rows w, w + 4, ...; lanes stride k (coalesced). Row maximum and softmax denominator: per-lane in k
+//            order, then an xor butterfly over the 64 lanes (every lane ends with the same bits) -> 2 T floats in LDS.
+//   phase 2  thread i takes columns i, i + 256, ...; t ascending: att = exp(u - max_t) / den_t and cla rebuilt from z (same
+//            expressions as phase 1, so the same bits), written out when asked for; S_k = sum_t att, y_k = (sum_t cla att) / S_k.
+// Every sum has a fixed order that depends on (T, K) only: a bag's bits do not depend on its batch or on att_out / cla_out.
+// Dead rows / columns are never touched: all loops are bounded by T and K.
+struct SlotCoef { float mean_v, scale_v, gamma_v, beta_v, mean_f, scale_f, gamma_f, beta_f; };
+
+__device__ __forceinline__ float wave_max_f(float v) {
+    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_sum_f(float v) {
+    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void attention_pool_wide_kernel(const float* __restrict__ z, int T, int K, BnParams nv, BnParams nf,
+                                                                  float eps, float* __restrict__ y, int64_t ldy,
+                                                                  float* __restrict__ att_out, float* __restrict__ cla_out) {
+    __shared__ SlotCoef coef[kMaxSlots];
+    __shared__ float row_max[kMaxSlots], row_inv[kMaxSlots];
+    const int64_t bag = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float* tile = z + bag * T * K;
+    if (threadIdx.x < T) {
+        const int t = threadIdx.x;
+        coef[t] = SlotCoef{nv.mean[t], 1.0f / sqrtf(nv.var[t] + eps), nv.gamma[t], nv.beta[t],
+                           nf.mean[t], 1.0f / sqrtf(nf.var[t] + eps), nf.gamma[t], nf.beta[t]};
+    }
+    __syncthreads();
+    for (int t = wave; t < T; t += 4) {                       // wave-uniform: the butterflies stay convergent
+        const SlotCoef c = coef[t];
+        const float* row = tile + int64_t(t) * K;
+        float mx = -3.0e38f;
+        for (int k = lane; k < K; k += 64) mx = fmaxf(mx, (row[k] - c.mean_v) * c.scale_v * c.gamma_v + c.beta_v);
+        mx = wave_max_f(mx);
+        float den = 0.f;
+        for (int k = lane; k < K; k += 64) den += __expf(((row[k] - c.mean_v) * c.scale_v * c.gamma_v + c.beta_v) - mx);
+        den = wave_sum_f(den);
+        if (lane == 0) { row_max[t] = mx; row_inv[t] = 1.0f / den; }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += 256) {
+        float S = 0.f, num = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const SlotCoef c = coef[t];
+            const float v = tile[int64_t(t) * K + k];
+            const float att = __expf(((v - c.mean_v) * c.scale_v * c.gamma_v + c.beta_v) - row_max[t]) * row_inv[t];
+            const float cla = sigmoidf((v - c.mean_f) * c.scale_f * c.gamma_f + c.beta_f);
+            if (att_out) att_out[(bag * T + t) * K + k] = att;
+            if (cla_out) cla_out[(bag * T + t) * K + k] = cla;
+            S += att;
+            num = fmaf(cla, att, num);
+        }
+        y[bag * ldy + k] = num / S;                            // model.py:239-240: sum_t cla * (att / sum_t att)
+    }
+}
+
+// The backward, same structure (formulas above attention_pool_bwd_kernel):
+//   phase 1  thread per column, t ascending: S_k and y_k exactly as the forward formed them -> 2 K floats in LDS (8 KB at 1024)
+//   phase 2  wave per row, lanes stride k: d cla and du_f; d att, the row's dot = sum_k d att * att (per-lane in k order, then
+//            the butterfly); then the same wave runs over its row again for du_v = att * (d att - dot). No block-wide step.
+__global__ __launch_bounds__(256) void attention_pool_bwd_wide_kernel(const float* __restrict__ dy, int64_t ld_dy,
+                                                                      const float* __restrict__ att_in, const float* __restrict__ cla_in,
+                                                                      int T, int K, float* __restrict__ du_v, float* __restrict__ du_f) {
+    __shared__ float col_inv[kMaxClasses], col_y[kMaxClasses];
+    const int64_t bag = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t base = bag * T * K;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        float S = 0.f, num = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const float a = att_in[base + int64_t(t) * K + k];
+            S += a;
+            num = fmaf(cla_in[base + int64_t(t) * K + k], a, num);
+        }
+        col_inv[k] = 1.0f / S;
+        col_y[k] = num / S;
+    }
+    __syncthreads();
+    for (int t = wave; t < T; t += 4) {
+        const int64_t row = base + int64_t(t) * K;
+        float dot = 0.f;
+        for (int k = lane; k < K; k += 64) {
+            const float g = dy[bag * ld_dy + k], a = att_in[row + k], c = cla_in[row + k];
+            du_f[row + k] = g * (a * col_inv[k]) * c * (1.f - c);
+            dot = fmaf(g * (c - col_y[k]) * col_inv[k], a, dot);
+        }
+        dot = wave_sum_f(dot);
+        for (int k = lane; k < K; k += 64) {
+            const float g = dy[bag * ld_dy + k], a = att_in[row + k], c = cla_in[row + k];
+            du_v[row + k] = a * (g * (c - col_y[k]) * col_inv[k] - dot);
+        }
     }
 }
 
@@ -505,14 +646,21 @@ __global__ __launch_bounds__(256) void linear_small_bwd_kernel(const float* __re
 
 }  // namespace
 
-extern "C" int64_t mla_bn_stats_workspace_bytes(void) { return (int64_t(kStatBlocks) + 1) * kMaxChannels * 2 * sizeof(double); }
+// partials ([blocks][channels][2] doubles: 512 x 64 or 32 x 1024, the same area), then the tail mla_bn_stats keeps its sums in
+static_assert(kWideRowBlocks * kMaxWideChannels <= kStatBlocks * kMaxChannels, "the wide column partials must fit the partial area");
+extern "C" int64_t mla_bn_stats_workspace_bytes(void) {
+    return (int64_t(kStatBlocks) * kMaxChannels + kMaxWideChannels) * 2 * sizeof(double);
+}
+
+// channels a layout may have: the period in row mode, the columns in column mode
+static inline int max_channels(int mode) { return mode == 0 ? kMaxChannels : kMaxWideChannels; }
 
 extern "C" int mla_bn_stats_sums(const float* x, int64_t rows, int64_t cols, int64_t ldx, int mode, int period, void* workspace,
                                  double* sums, mla_stream_t stream) {
     MLA_REQUIRE(x && workspace && sums && rows > 0 && cols > 0 && ldx >= cols, MLA_E_ARG, "bad bn_stats arguments");
     MLA_REQUIRE(mode == 0 || mode == 1, MLA_E_ARG, "bn_stats mode %d", mode);
     const int channels = mode == 0 ? period : int(cols);
-    MLA_REQUIRE(channels >= 1 && channels <= kMaxChannels, MLA_E_SHAPE, "bn_stats supports 1..%d channels (got %d)", kMaxChannels, channels);
+    MLA_REQUIRE(channels >= 1 && channels <= max_channels(mode), MLA_E_SHAPE, "bn_stats supports 1..%d channels (got %d)", max_channels(mode), channels);
     MLA_REQUIRE(mode == 1 || rows % period == 0, MLA_E_SHAPE, "rows %lld not a multiple of period %d", (long long)rows, period);
     return channel_sums(StatsOp{x, ldx}, rows, cols, mode, period, workspace, sums, static_cast<hipStream_t>(stream));
 }
@@ -520,8 +668,8 @@ extern "C" int mla_bn_stats_sums(const float* x, int64_t rows, int64_t cols, int
 extern "C" int mla_bn_stats_finish(const double* sums, int channels, double count, float* mean, float* var_biased,
                                    float* running_mean, float* running_var, float momentum, int64_t* num_batches_tracked,
                                    mla_stream_t stream) {
-    MLA_REQUIRE(sums && mean && var_biased && channels >= 1 && channels <= kMaxChannels && count > 0, MLA_E_ARG, "bad bn_stats_finish arguments");
-    hipLaunchKernelGGL(stats_finish_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), sums, channels, count, mean,
+    MLA_REQUIRE(sums && mean && var_biased && channels >= 1 && channels <= kMaxWideChannels && count > 0, MLA_E_ARG, "bad bn_stats_finish arguments");
+    hipLaunchKernelGGL(stats_finish_kernel, dim3(1), dim3(channels <= 64 ? 64 : kMaxWideChannels), 0, static_cast<hipStream_t>(stream), sums, channels, count, mean,
                        var_biased, running_mean, running_var, momentum, num_batches_tracked);
     MLA_LAUNCH_OK("bn stats finish");
     return MLA_OK;
@@ -548,7 +696,7 @@ extern "C" int mla_bn_stats_fused(const float* x, int64_t rows, int64_t cols, in
     MLA_REQUIRE(x && workspace && sums_out && mean && var_biased && rows > 0 && cols > 0 && ldx >= cols, MLA_E_ARG, "bad bn_stats arguments");
     MLA_REQUIRE(mode == 0 || mode == 1, MLA_E_ARG, "bn_stats mode %d", mode);
     const int channels = mode == 0 ? period : int(cols);
-    MLA_REQUIRE(channels >= 1 && channels <= kMaxChannels, MLA_E_SHAPE, "bn_stats supports 1..%d channels (got %d)", kMaxChannels, channels);
+    MLA_REQUIRE(channels >= 1 && channels <= max_channels(mode), MLA_E_SHAPE, "bn_stats supports 1..%d channels (got %d)", max_channels(mode), channels);
     MLA_REQUIRE(mode == 1 || rows % period == 0, MLA_E_SHAPE, "rows %lld not a multiple of period %d", (long long)rows, period);
     const double count = mode == 0 ? double(rows / period) * double(cols) : double(rows);
     const FinishArgs f{count, mean, var_biased, running_mean, running_var, momentum, num_batches_tracked};
@@ -578,28 +726,29 @@ extern "C" int mla_bn_apply(const float* x, int64_t ldx, float* y, int64_t ldy, 
     return MLA_OK;
 }
 
-extern "C" int mla_bn_bwd_sums(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
-                               int act, float drop_scale, int64_t rows, int64_t cols, int mode, int period, const float* mean,
-                               const float* var, float eps, void* workspace, double* sums, mla_stream_t stream) {
+// The two stages of the backward; max_cols: the column-mode limit of the calling entry point (64, or 1024 for the _wide pair)
+static int bn_bwd_sums(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                       int act, float drop_scale, int64_t rows, int64_t cols, int mode, int period, const float* mean,
+                       const float* var, float eps, void* workspace, double* sums, mla_stream_t stream, int max_cols) {
     MLA_REQUIRE(x && dy && mean && var && workspace && sums && rows > 0 && cols > 0, MLA_E_ARG, "bad bn_bwd_sums arguments");
     MLA_REQUIRE(act == 0 || yout, MLA_E_ARG, "bn_bwd needs the forward output for act %d", act);
-    MLA_REQUIRE((mode == 0 && period >= 1 && period <= kMaxChannels && rows % period == 0) || (mode == 1 && cols <= kMaxChannels),
+    MLA_REQUIRE((mode == 0 && period >= 1 && period <= kMaxChannels && rows % period == 0) || (mode == 1 && cols <= max_cols),
                 MLA_E_SHAPE, "bn_bwd channel layout");
     BwdOp op{x, dy, yout, mean, var, ldx, ld_dy, ld_y, act, drop_scale, eps};
     return channel_sums(op, rows, cols, mode, period, workspace, sums, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int mla_bn_bwd_apply(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
-                                int act, float drop_scale, int64_t rows, int64_t cols, int mode, int period, const float* mean,
-                                const float* var, const float* gamma, float eps, const double* sums_global,
-                                const double* sums_local, double count, float* dx, int64_t ld_dx, int accumulate,
-                                float* dgamma, float* dbeta, mla_stream_t stream) {
+static int bn_bwd_apply(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                        int act, float drop_scale, int64_t rows, int64_t cols, int mode, int period, const float* mean,
+                        const float* var, const float* gamma, float eps, const double* sums_global,
+                        const double* sums_local, double count, float* dx, int64_t ld_dx, int accumulate,
+                        float* dgamma, float* dbeta, mla_stream_t stream, int max_cols) {
     MLA_REQUIRE(x && dy && mean && var && gamma && sums_global && sums_local && count > 0 && rows > 0 && cols > 0, MLA_E_ARG,
                 "bad bn_bwd_apply arguments");
     MLA_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), MLA_E_ARG, "dgamma and dbeta go together");
     MLA_REQUIRE(act == 0 || yout, MLA_E_ARG, "bn_bwd needs the forward output for act %d", act);
     // the same channel layout mla_bn_bwd_sums accepts (period 0 in mode 0 would reach r % period on the device)
-    MLA_REQUIRE((mode == 0 && period >= 1 && period <= kMaxChannels && rows % period == 0) || (mode == 1 && cols <= kMaxChannels),
+    MLA_REQUIRE((mode == 0 && period >= 1 && period <= kMaxChannels && rows % period == 0) || (mode == 1 && cols <= max_cols),
                 MLA_E_SHAPE, "bn_bwd channel layout");
     BwdOp op{x, dy, yout, mean, var, ldx, ld_dy, ld_y, act, drop_scale, eps};
     const int64_t total = rows * cols;
@@ -615,14 +764,57 @@ extern "C" int mla_bn_bwd_apply(const float* x, int64_t ldx, const float* dy, in
     return MLA_OK;
 }
 
+extern "C" int mla_bn_bwd_sums(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                               int act, float drop_scale, int64_t rows, int64_t cols, int mode, int period, const float* mean,
+                               const float* var, float eps, void* workspace, double* sums, mla_stream_t stream) {
+    return bn_bwd_sums(x, ldx, dy, ld_dy, yout, ld_y, act, drop_scale, rows, cols, mode, period, mean, var, eps, workspace, sums, stream,
+                       kMaxChannels);
+}
+
+extern "C" int mla_bn_bwd_apply(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                                int act, float drop_scale, int64_t rows, int64_t cols, int mode, int period, const float* mean,
+                                const float* var, const float* gamma, float eps, const double* sums_global,
+                                const double* sums_local, double count, float* dx, int64_t ld_dx, int accumulate,
+                                float* dgamma, float* dbeta, mla_stream_t stream) {
+    return bn_bwd_apply(x, ldx, dy, ld_dy, yout, ld_y, act, drop_scale, rows, cols, mode, period, mean, var, gamma, eps, sums_global,
+                        sums_local, count, dx, ld_dx, accumulate, dgamma, dbeta, stream, kMaxChannels);
+}
+
+// Column mode (channel = column) for 1..1024 columns: BatchNorm1d(K) of a head with more than 64 classes. The two entry points above
+// keep refusing more than 64 columns, which is the contract their callers were written against; up to 64 columns the pairs are the
+// same launches and the same bits.
+extern "C" int mla_bn_bwd_sums_wide(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                                    int act, float drop_scale, int64_t rows, int64_t cols, const float* mean, const float* var,
+                                    float eps, void* workspace, double* sums, mla_stream_t stream) {
+    return bn_bwd_sums(x, ldx, dy, ld_dy, yout, ld_y, act, drop_scale, rows, cols, 1, 0, mean, var, eps, workspace, sums, stream,
+                       kMaxWideChannels);
+}
+
+extern "C" int mla_bn_bwd_apply_wide(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                                     int act, float drop_scale, int64_t rows, int64_t cols, const float* mean, const float* var,
+                                     const float* gamma, float eps, const double* sums_global, const double* sums_local,
+                                     double count, float* dx, int64_t ld_dx, int accumulate, float* dgamma, float* dbeta,
+                                     mla_stream_t stream) {
+    return bn_bwd_apply(x, ldx, dy, ld_dy, yout, ld_y, act, drop_scale, rows, cols, 1, 0, mean, var, gamma, eps, sums_global,
+                        sums_local, count, dx, ld_dx, accumulate, dgamma, dbeta, stream, kMaxWideChannels);
+}
+
 extern "C" int mla_attention_pool(const float* z, int64_t bags, int T, int K, const float* v_mean, const float* v_var,
                                   const float* v_gamma, const float* v_beta, const float* f_mean, const float* f_var,
                                   const float* f_gamma, const float* f_beta, float eps, float* y, int64_t ldy,
                                   float* att_out, float* cla_out, mla_stream_t stream) {
     MLA_REQUIRE(z && y && v_mean && v_var && v_gamma && v_beta && f_mean && f_var && f_gamma && f_beta, MLA_E_ARG, "null attention_pool argument");
-    MLA_REQUIRE(T >= 1 && T <= 16 && K >= 1 && K <= 16 && ldy >= K, MLA_E_SHAPE, "attention_pool supports T, K <= 16 (got %d, %d)", T, K);
+    MLA_REQUIRE(T >= 1 && T <= kMaxSlots && K >= 1 && K <= kMaxClasses && ldy >= K, MLA_E_SHAPE,
+                "attention_pool supports T <= %d, K <= %d (got %d, %d)", kMaxSlots, kMaxClasses, T, K);
+    MLA_REQUIRE(bags >= 0 && bags <= 0x7fffffff, MLA_E_ARG, "attention_pool: %lld bags", (long long)bags);
     if (bags == 0) return MLA_OK;
     BnParams nv{v_mean, v_var, v_gamma, v_beta}, nf{f_mean, f_var, f_gamma, f_beta};
+    if (T > 16 || K > 16) {
+        hipLaunchKernelGGL(attention_pool_wide_kernel, dim3(unsigned(bags)), dim3(256), 0, static_cast<hipStream_t>(stream), z, T, K, nv,
+                           nf, eps, y, ldy, att_out, cla_out);
+        MLA_LAUNCH_OK("attention_pool (wide)");
+        return MLA_OK;
+    }
     hipLaunchKernelGGL(attention_pool_kernel<16>, dim3(unsigned((bags + 15) / 16)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), z, bags, T, K, nv, nf, eps, y, ldy, att_out, cla_out);
     MLA_LAUNCH_OK("attention_pool");
@@ -632,8 +824,16 @@ extern "C" int mla_attention_pool(const float* z, int64_t bags, int T, int K, co
 extern "C" int mla_attention_pool_bwd(const float* dy, int64_t ld_dy, const float* att, const float* cla, int64_t bags, int T,
                                       int K, float* du_v, float* du_f, mla_stream_t stream) {
     MLA_REQUIRE(dy && att && cla && du_v && du_f && ld_dy >= K, MLA_E_ARG, "bad attention_pool_bwd arguments");
-    MLA_REQUIRE(T >= 1 && T <= 16 && K >= 1 && K <= 16, MLA_E_SHAPE, "attention_pool_bwd supports T, K <= 16 (got %d, %d)", T, K);
+    MLA_REQUIRE(T >= 1 && T <= kMaxSlots && K >= 1 && K <= kMaxClasses, MLA_E_SHAPE,
+                "attention_pool_bwd supports T <= %d, K <= %d (got %d, %d)", kMaxSlots, kMaxClasses, T, K);
+    MLA_REQUIRE(bags >= 0 && bags <= 0x7fffffff, MLA_E_ARG, "attention_pool_bwd: %lld bags", (long long)bags);
     if (bags == 0) return MLA_OK;
+    if (T > 16 || K > 16) {
+        hipLaunchKernelGGL(attention_pool_bwd_wide_kernel, dim3(unsigned(bags)), dim3(256), 0, static_cast<hipStream_t>(stream), dy, ld_dy,
+                           att, cla, T, K, du_v, du_f);
+        MLA_LAUNCH_OK("attention_pool_bwd (wide)");
+        return MLA_OK;
+    }
     hipLaunchKernelGGL(attention_pool_bwd_kernel<16>, dim3(unsigned((bags + 15) / 16)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), dy, ld_dy, att, cla, bags, T, K, du_v, du_f);
     MLA_LAUNCH_OK("attention_pool_bwd");

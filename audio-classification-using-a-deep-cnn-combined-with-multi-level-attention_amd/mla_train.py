@@ -5,7 +5,7 @@ only) and by the fused training step of ``train.py`` (forward with a tape, then 
 import torch
 
 from . import ops
-from .params import DR, H, K, T
+from .params import DR
 
 
 class Ctx:
@@ -31,7 +31,7 @@ def _bn_stats(bn, z, mode, period, train, ctx):
 def embedded_mapping_forward(em, x, ctx=None):
     """model.py:217-222 on x (B, T, F) float32 -> (B, T, H)."""
     ctx = ctx or Ctx()
-    B = x.shape[0]
+    B, T, H = x.shape[0], em.slots, em.hidden
     rows = x.detach().reshape(B * T, -1).float().contiguous()
     train = em.training
     mean, var = _bn_stats(em.norm0, rows, 0, T, train, ctx)
@@ -60,7 +60,7 @@ def embedded_mapping_forward(em, x, ctx=None):
 def attention_forward(am, h, y, ctx=None, level=0):
     """model.py:236-242 on h (B, T, H): writes y (B, K) (a column block of the concatenation)."""
     ctx = ctx or Ctx()
-    B = h.shape[0]
+    B, T, H, K = h.shape[0], am.slots, am.hidden, am.classes
     rows = h.reshape(B * T, H)
     z = ops.linear(rows, am.fcv.weight.detach(), am.fcv.bias.detach())
     if am.training:
@@ -82,7 +82,7 @@ def mla_forward(mla, x, ctx=None):
     """model.py:258-269: x (B, T, M) -> (B, K) sigmoid scores."""
     ctx = ctx or Ctx()
     ctx.train = mla.training                 # batch statistics + dropout (train) or running statistics (eval): the backward must match
-    B = x.shape[0]
+    B, K = x.shape[0], mla.classes
     L = len(mla.model)
     conc = torch.empty((B, L * K), dtype=torch.float32, device=x.device)
     cur = x
@@ -129,6 +129,7 @@ def mla_backward(mla, ctx, dout, grads, need_input_grad=False):
     relative to `mla` (e.g. 'embedded_mappings.0.fc.1.weight') to preallocated gradient tensors,
     all of which are overwritten. Returns d(loss)/dx (B*T, M) if need_input_grad."""
     tape, dist = ctx.tape, ctx.dist
+    T, K = mla.slots, mla.classes
     bs = ctx.train                           # eval-mode forward: fixed (running) statistics, no dropout scale
     drop = 1.0 / (1.0 - DR) if bs else 1.0
     kind, _, conc, z, mean, var, out = tape[-1]

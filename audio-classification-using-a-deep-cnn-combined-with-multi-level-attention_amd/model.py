@@ -70,10 +70,27 @@ class Dropout(nn.Module):
         raise RuntimeError("Dropout is fused into the HIP BatchNorm/ReLU kernel of its parent module")
 
 
+def check_head_shape(classes, slots, hidden):
+    """The head's accepted range, checked by every constructor before anything is allocated: the wide pooling and column-mode
+    BatchNorm kernels take up to 1024 classes, the row-mode BatchNorm up to 64 time slots (its period limit), the GEMM wants
+    16-byte rows (hidden a multiple of 4)."""
+    for name, v in (("classes", classes), ("slots", slots), ("hidden", hidden)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError("%s must be an int, got %r" % (name, v))
+    if not 1 <= classes <= 1024:
+        raise ValueError("classes must be in 1..1024, got %d" % classes)
+    if not 1 <= slots <= 64:
+        raise ValueError("slots must be in 1..64, got %d" % slots)
+    if hidden < 4 or hidden % 4:
+        raise ValueError("hidden must be a multiple of 4 and at least 4, got %d" % hidden)
+
+
 class Ensemble(nn.Module):
     def __init__(self, input_conf: str, cnn_conf: Dict[str, Union[str, int]], model_conf: List[int], device,
-                 precision: str = "f32", trunk_backward: bool = False):
+                 precision: str = "f32", trunk_backward: bool = False, classes: int = K, slots: int = T, hidden: int = H):
+        check_head_shape(classes, slots, hidden)
         super().__init__()
+        self.classes, self.slots, self.hidden = classes, slots, hidden
         self.cnn_type = cnn_conf["cnn_type"]
         self.just_bottlenecks = cnn_conf["just_bottlenecks"]
         self.num_classes = cnn_conf["num_classes"]
@@ -88,7 +105,7 @@ class Ensemble(nn.Module):
         else:
             raise Exception("CNN type is not valid.")
         self.input = Input(input_conf=input_conf, cnn_type=self.cnn_type, device=device)
-        self.mla = MultiLevelAttention(model_conf, self.emb_input_size)
+        self.mla = MultiLevelAttention(model_conf, self.emb_input_size, classes=classes, slots=slots, hidden=hidden)
         self.cnn = CNN(**cnn_conf, precision=precision, trunk_backward=trunk_backward)
 
     def set_precision(self, precision):
@@ -102,8 +119,13 @@ class Ensemble(nn.Module):
     def forward(self, x):
         x_proc = self.input(x)
         features = self.cnn(x_proc)
-        out = self.mla(features.reshape(-1, T, self.emb_input_size))
+        out = self.mla(features.reshape(-1, self.slots, self.emb_input_size))
         return out
+
+    def _ten_window_bags(self, what):
+        if self.slots != T:
+            raise ValueError("%s builds the dataset's bags of %d windows, the model takes slots = %d; feed (B, slots, ...) inputs "
+                             "through forward()" % (what, T, self.slots))
 
     def _waveforms_only_vggish(self):
         if self.cnn_type != "vggish":
@@ -121,13 +143,13 @@ class Ensemble(nn.Module):
         feats = self.cnn.cnn_model[0] if self.just_bottlenecks else self.cnn.cnn_model.features
         if ops.FUSED_FRONT and dtype == torch.bfloat16 and not differentiable.wants_grad(feats):
             # bf16 inference: front-end + conv1 in one kernel, the examples tensor is never written
-            assert pcm.dim() == 2 and frontend.counts(pcm.shape[1])[1] == T, "each waveform must yield exactly T examples"
+            assert pcm.dim() == 2 and frontend.counts(pcm.shape[1])[1] == self.slots, "each waveform must yield exactly T examples"
             features = self.cnn(PcmInput(pcm))
-            return self.mla(features.reshape(-1, T, self.emb_input_size))
+            return self.mla(features.reshape(-1, self.slots, self.emb_input_size))
         ex = frontend.waveforms_to_examples(pcm, out_dtype=dtype)
-        assert ex.shape[0] == pcm.shape[0] * T, "each waveform must yield exactly T examples"
+        assert ex.shape[0] == pcm.shape[0] * self.slots, "each waveform must yield exactly T examples"
         features = self.cnn(ex)
-        return self.mla(features.reshape(-1, T, self.emb_input_size))
+        return self.mla(features.reshape(-1, self.slots, self.emb_input_size))
 
     def forward_clips(self, pcm, overlap=True):
         """The ResNet branch's wave -> scores entry: (B, SAMPLES_NUM_RESNET) float32 PCM at 22 050 Hz on the device -> the
@@ -136,6 +158,7 @@ class Ensemble(nn.Module):
         if self.cnn_type != "resnet":
             raise NotImplementedError("forward_clips feeds the ResNet branch's mel-dB images; cnn_type 'vggish' takes 16 kHz PCM "
                                       "through forward_waveforms(), or 4 s clips of it through forward_clips_librosa()")
+        self._ten_window_bags("forward_clips")
         from . import dataset
         return self.forward(dataset.clips_to_images(pcm, overlap))
 
@@ -151,12 +174,14 @@ class Ensemble(nn.Module):
         floating, of any rates and lengths -> dataset.recordings_to_clips (one HIP launch: channel mean, resampling to 22 050 Hz,
         cut at 4 s, zero fill) -> forward_clips() -> (B, K) scores."""
         self._recordings_only_resnet("forward_recordings")
+        self._ten_window_bags("forward_recordings")
         from . import dataset
         return self.forward_clips(dataset.recordings_to_clips(recordings, rates), overlap)
 
     def forward_wavfiles(self, paths, overlap=True):
         """forward_recordings for 16-bit WAV files (dataset.wavfiles_to_clips)."""
         self._recordings_only_resnet("forward_wavfiles")
+        self._ten_window_bags("forward_wavfiles")
         from . import dataset
         return self.forward_clips(dataset.wavfiles_to_clips(paths), overlap)
 
@@ -164,6 +189,7 @@ class Ensemble(nn.Module):
         """forward_recordings for WAV files of any PCM width or IEEE float, mixed in one batch: dataset.audiofiles_to_clips uploads
         the files' bytes and decodes them in the clips launch."""
         self._recordings_only_resnet("forward_audiofiles")
+        self._ten_window_bags("forward_audiofiles")
         from . import dataset
         return self.forward_clips(dataset.audiofiles_to_clips(paths), overlap)
 
@@ -175,6 +201,7 @@ class Ensemble(nn.Module):
             raise NotImplementedError("%s builds the VGGish branch's log-mel bags (the reference's native dataset path); cnn_type "
                                       "'resnet' always takes the librosa path (dataset.py:176-178): use %s()"
                                       % (what, what[:-len("_native")]))
+        self._ten_window_bags(what)
         if not overlap:
             raise ValueError("%s: overlap=False gives 4 frames per bag, the model takes T = %d; the dataset functions "
                              "(dataset.recordings_to_frames, ...) support it" % (what, T))
@@ -205,6 +232,7 @@ class Ensemble(nn.Module):
         if self.cnn_type != "vggish":
             raise NotImplementedError("%s builds the VGGish branch's HTK mel-dB bags (64 bands, unpadded frames); cnn_type 'resnet' "
                                       "takes librosa's default spectrogram: use %s()" % (what, what[:-len("_librosa")]))
+        self._ten_window_bags(what)
         if not overlap:
             raise ValueError("%s: overlap=False is not defined on the VGGish librosa path (388 columns do not split into whole "
                              "96-column frames; the reference's split refuses it)" % what)
@@ -415,45 +443,51 @@ class CnnFlatten(nn.Module):
 
 
 class EmbeddedMapping(nn.Module):
-    def __init__(self, n_fc, is_first, emb_input_size):
+    def __init__(self, n_fc, is_first, emb_input_size, *, slots=T, hidden=H):
+        check_head_shape(1, slots, hidden)
         super().__init__()
-        self.n_fc = n_fc
-        self.norm0 = BatchNorm1d(T)
+        self.n_fc, self.slots, self.hidden = n_fc, slots, hidden
+        self.norm0 = BatchNorm1d(slots)
         if is_first:
-            self.fc = nn.ModuleList([Linear(emb_input_size, H)] + [Linear(H, H) for _ in range(n_fc - 1)])
+            self.fc = nn.ModuleList([Linear(emb_input_size, hidden)] + [Linear(hidden, hidden) for _ in range(n_fc - 1)])
         else:
-            self.fc = nn.ModuleList([Linear(H, H) for _ in range(n_fc)])
+            self.fc = nn.ModuleList([Linear(hidden, hidden) for _ in range(n_fc)])
         self.dropouts = nn.ModuleList([Dropout(p=DR) for _ in range(n_fc)])
-        self.norms = nn.ModuleList([BatchNorm1d(T) for _ in range(n_fc)])
+        self.norms = nn.ModuleList([BatchNorm1d(slots) for _ in range(n_fc)])
 
     def forward(self, x):
         return mla_train.embedded_mapping_forward(self, x, None)
 
 
 class AttentionModule(nn.Module):
-    def __init__(self):
+    def __init__(self, *, classes=K, slots=T, hidden=H):
+        check_head_shape(classes, slots, hidden)
         super().__init__()
-        self.fcv = Linear(H, K)
-        self.fcf = Linear(H, K)          # never used by forward (model.py:237-238); kept for the state_dict
-        self.normv = BatchNorm1d(T)
-        self.normf = BatchNorm1d(T)
+        self.classes, self.slots, self.hidden = classes, slots, hidden
+        self.fcv = Linear(hidden, classes)
+        self.fcf = Linear(hidden, classes)          # never used by forward (model.py:237-238); kept for the state_dict
+        self.normv = BatchNorm1d(slots)
+        self.normf = BatchNorm1d(slots)
 
     def forward(self, h):
-        y = torch.empty((h.shape[0], K), dtype=torch.float32, device=h.device)
+        y = torch.empty((h.shape[0], self.classes), dtype=torch.float32, device=h.device)
         mla_train.attention_forward(self, h, y, None)
         return y
 
 
 class MultiLevelAttention(nn.Module):
-    def __init__(self, model_conf, emb_input_size):
+    def __init__(self, model_conf, emb_input_size, *, classes=K, slots=T, hidden=H):
+        check_head_shape(classes, slots, hidden)
         super().__init__()
         self.model = model_conf
+        self.classes, self.slots, self.hidden = classes, slots, hidden
+        shape = dict(slots=slots, hidden=hidden)
         self.embedded_mappings = nn.ModuleList(
-            [EmbeddedMapping(model_conf[0], is_first=True, emb_input_size=emb_input_size)] +
-            [EmbeddedMapping(n_layers, is_first=False, emb_input_size=emb_input_size) for n_layers in model_conf[1:]])
-        self.attention_modules = nn.ModuleList([AttentionModule() for _ in model_conf])
-        self.fc = Linear(len(model_conf) * K, K)
-        self.norm = BatchNorm1d(K)
+            [EmbeddedMapping(model_conf[0], is_first=True, emb_input_size=emb_input_size, **shape)] +
+            [EmbeddedMapping(n_layers, is_first=False, emb_input_size=emb_input_size, **shape) for n_layers in model_conf[1:]])
+        self.attention_modules = nn.ModuleList([AttentionModule(classes=classes, **shape) for _ in model_conf])
+        self.fc = Linear(len(model_conf) * classes, classes)
+        self.norm = BatchNorm1d(classes)
 
     def forward(self, x):
         if differentiable.wants_grad(self, x):

@@ -494,8 +494,13 @@ def bn_backward(x, dy, yout, act, drop_scale, mode, period, mean, var, gamma, di
     L = _lib.lib()
     local = torch.empty(2 * ch, dtype=torch.float64, device=x.device)
     ld_y = yout.stride(0) if yout is not None else 0
-    _lib.check(L.mla_bn_bwd_sums(_p(x), x.stride(0), _p(dy), dy.stride(0), _p(yout), ld_y, act, float(drop_scale), rows, cols, mode,
-                                 period, _p(mean), _p(var), BN_EPS, _p(_workspace(x.device)), _p(local), _lib.stream_ptr()))
+    wide = mode == 1 and cols > 64                  # a head with more than 64 classes: the column-mode pair without the 64-column limit
+    if wide:
+        _lib.check(L.mla_bn_bwd_sums_wide(_p(x), x.stride(0), _p(dy), dy.stride(0), _p(yout), ld_y, act, float(drop_scale), rows, cols,
+                                          _p(mean), _p(var), BN_EPS, _p(_workspace(x.device)), _p(local), _lib.stream_ptr()))
+    else:
+        _lib.check(L.mla_bn_bwd_sums(_p(x), x.stride(0), _p(dy), dy.stride(0), _p(yout), ld_y, act, float(drop_scale), rows, cols, mode,
+                                     period, _p(mean), _p(var), BN_EPS, _p(_workspace(x.device)), _p(local), _lib.stream_ptr()))
     glob = local
     if not batch_stats:
         glob = torch.zeros_like(local)
@@ -505,10 +510,10 @@ def bn_backward(x, dy, yout, act, drop_scale, mode, period, mean, var, gamma, di
         count = (rows // period * cols if mode == 0 else rows) * dist.bn_world
     if want_dx and dx is None:
         dx = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
-    _lib.check(L.mla_bn_bwd_apply(_p(x), x.stride(0), _p(dy), dy.stride(0), _p(yout), ld_y, act, float(drop_scale), rows, cols, mode,
-                                  period, _p(mean), _p(var), _p(gamma), BN_EPS, _p(glob), _p(local), float(count),
-                                  _p(dx) if want_dx else None, dx.stride(0) if want_dx else 0, int(accumulate), _p(dgamma),
-                                  _p(dbeta), _lib.stream_ptr()))
+    tail = (_p(mean), _p(var), _p(gamma), BN_EPS, _p(glob), _p(local), float(count), _p(dx) if want_dx else None,
+            dx.stride(0) if want_dx else 0, int(accumulate), _p(dgamma), _p(dbeta), _lib.stream_ptr())
+    head = (_p(x), x.stride(0), _p(dy), dy.stride(0), _p(yout), ld_y, act, float(drop_scale), rows, cols)
+    _lib.check(L.mla_bn_bwd_apply_wide(*head, *tail) if wide else L.mla_bn_bwd_apply(*head, mode, period, *tail))
     return dx
 
 

@@ -208,7 +208,7 @@ class TrainStep:
                 raise RuntimeError("parameter %s no longer lives in the flat buffer of this TrainStep (the model was moved or "
                                    "cast after the step was built): build a new TrainStep" % n)
         clf.train()
-        ops.check_labels(labels, clf.num_classes)
+        ops.check_labels(labels, clf.mla.classes)
         if self._graph_usable(inputs):
             return self._graphed(inputs, labels)
         with torch.no_grad():
@@ -292,7 +292,7 @@ class TrainStep:
         else:
             feats = clf.cnn(x)
         ctx = mla_train.Ctx(tape=True, dist=self.dist, counter=self.step_dev if captured else None, bases=bases)
-        out = mla_train.mla_forward(clf.mla, feats.reshape(-1, T, clf.emb_input_size), ctx)
+        out = mla_train.mla_forward(clf.mla, feats.reshape(-1, clf.mla.slots, clf.emb_input_size), ctx)
         loss, dout, hits = ops.cross_entropy(out, labels, 1.0 / B_global)
         d_feats = mla_train.mla_backward(clf.mla, ctx, dout, self.mla_grads,
                                          need_input_grad=self.finetune or self.rn_fc or bool(self.rn_trunk))
@@ -396,9 +396,15 @@ def classification_summary(y_true, y_pred, target_names=TARGET_NAMES):
     return res, cm_pct
 
 
-def test_model(model, dataloader, criterion=None, optimizer=None):
+def default_target_names(classes):
+    """Row names of the test report: the dataset's own for its 10 classes, else class_0, class_1, ..."""
+    return list(TARGET_NAMES) if classes == len(TARGET_NAMES) else ["class_%d" % i for i in range(classes)]
+
+
+def test_model(model, dataloader, criterion=None, optimizer=None, target_names=None):
     """train.py:182-247: final test pass -> (test accuracy, classification summary dict). The confusion-matrix
-    plot of the reference is not reproduced; the matrix itself is returned under ``results["confusion_matrix_pct"]``."""
+    plot of the reference is not reproduced; the matrix itself is returned under ``results["confusion_matrix_pct"]``.
+    target_names: one name per class of the head; None = TARGET_NAMES for a 10-class head, else class_0, class_1, ..."""
     if dataloader is None:
         return None
     device = next(model.parameters()).device
@@ -407,7 +413,10 @@ def test_model(model, dataloader, criterion=None, optimizer=None):
     loss, acc, preds, trues = _evaluate(model, dataloader, device, collect=True)
     print("{} Loss: {:.4f}, Acc: {:.4f}".format("test", loss, acc))
     print("Testing complete in {:.0f}s".format(time.time() - since))
-    results, cm = classification_summary(trues.numpy(), preds.numpy())
+    if target_names is None:
+        mla = getattr(model, "mla", model)
+        target_names = default_target_names(getattr(mla, "classes", len(TARGET_NAMES)))
+    results, cm = classification_summary(trues.numpy(), preds.numpy(), target_names)
     results["confusion_matrix_pct"] = cm
     return acc, results
 

@@ -280,6 +280,10 @@ int mla_linear_small(const float* a, int64_t lda, const float* w, int64_t ldw, c
  *   mode 1: channel = column        -- BatchNorm1d(K) on (B, K) (model.py:256).
  * Writes mean and BIASED variance (what normalisation uses); if running_mean/var are non-NULL
  * and momentum >= 0 they are updated in place with the UNBIASED variance, as torch does.
+ * Limits: mode 0 period 1..64 (rows a multiple of it); mode 1 cols 1..1024 (above 64 columns a kernel of its own; up to 64
+ * the launches and bits are what they were). Anything else: MLA_E_SHAPE. The same limits hold for the two-stage and fused
+ * forms below. The backward pair mla_bn_bwd_sums / mla_bn_bwd_apply keeps 64 columns as its mode-1 limit; wider layers go
+ * through mla_bn_bwd_sums_wide / mla_bn_bwd_apply_wide.
  * workspace: mla_bn_stats_workspace_bytes() bytes of device memory. Deterministic. */
 int64_t mla_bn_stats_workspace_bytes(void);
 int mla_bn_stats(const float* x, int64_t rows, int64_t cols, int64_t ldx, int mode, int period,
@@ -297,7 +301,10 @@ int mla_bn_apply(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t row
 /* model.AttentionModule.forward (model.py:236-242) after the fcv Linear: z (bags*T, K) ->
  * y (bags, K) written with leading dimension ldy (so levels concatenate in place,
  * model.py:267). BatchNorm parameters of normv (v_*) and normf (f_*) per time slot (T values).
- * att_out / cla_out (bags*T*K each) receive softmax / sigmoid for the backward pass, or NULL. */
+ * att_out / cla_out (bags*T*K each) receive softmax / sigmoid for the backward pass, or NULL.
+ * Limits: 1 <= T <= 64, 1 <= K <= 1024, else MLA_E_SHAPE. T, K <= 16: 16 lanes per bag, the classes in registers; wider bags
+ * take one workgroup each. Either way a bag's result does not depend on the batch it sits in or on att_out / cla_out, and
+ * mla_attention_pool_bwd has the same limits and dispatch. */
 int mla_attention_pool(const float* z, int64_t bags, int T, int K, const float* v_mean, const float* v_var,
                        const float* v_gamma, const float* v_beta, const float* f_mean, const float* f_var,
                        const float* f_gamma, const float* f_beta, float eps, float* y, int64_t ldy,
@@ -336,6 +343,15 @@ int mla_bn_bwd_apply(const float* x, int64_t ldx, const float* dy, int64_t ld_dy
                      const float* var, const float* gamma, float eps, const double* sums_global,
                      const double* sums_local, double count, float* dx, int64_t ld_dx, int accumulate,
                      float* dgamma, float* dbeta, mla_stream_t stream);
+/* The same two stages in column mode (channel = column; BatchNorm1d(K), model.py:256) for 1 <= cols <= 1024, without the
+ * mode / period arguments. Up to 64 columns: the launches and bits of the pair above. workspace as mla_bn_stats. */
+int mla_bn_bwd_sums_wide(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                         int act, float drop_scale, int64_t rows, int64_t cols, const float* mean, const float* var,
+                         float eps, void* workspace, double* sums, mla_stream_t stream);
+int mla_bn_bwd_apply_wide(const float* x, int64_t ldx, const float* dy, int64_t ld_dy, const float* yout, int64_t ld_y,
+                          int act, float drop_scale, int64_t rows, int64_t cols, const float* mean, const float* var,
+                          const float* gamma, float eps, const double* sums_global, const double* sums_local, double count,
+                          float* dx, int64_t ld_dx, int accumulate, float* dgamma, float* dbeta, mla_stream_t stream);
 
 /* Backward of mla_attention_pool: dy (bags, K; leading dim ld_dy) and the saved att / cla ->
  * gradients w.r.t. the normv output (du_v) and the normf output (du_f), (bags*T, K) each. */
