@@ -52,6 +52,9 @@ def lib():
         L.mla_logmel_examples.argtypes = [vp, ci, i64, i64, i64, vp, vp, ci, vp]
         L.mla_logmel_conv1.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, vp]
         L.mla_logmel_bags.argtypes = [vp, ci, i64, i64, i64, vp, vp, ci, ci, vp, vp, ci, vp]
+        L.mla_timeline_counts.argtypes = [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+        L.mla_logmel_timeline.argtypes = [vp, ci, i64, i64, i64, vp, vp, i64, vp, vp, ci, vp]
+        L.mla_gather_bags.argtypes = [vp, i64, i64, vp, vp, i64, ci, i64, vp, vp]
         cf = ctypes.c_float
         L.mla_stft_magnitude.argtypes = [vp, i64, vp, vp, i64, i64, i64, vp, vp]
         L.mla_mel_log.argtypes = [vp, vp, i64, i64, i64, cf, vp, vp]

@@ -37,6 +37,7 @@
 #include "logmel_bags_core.h"
 #include "logmel_core.h"
 #include "logmel_tables.h"
+#include "logmel_timeline_core.h"
 
 namespace {
 
@@ -524,6 +525,114 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_bags_kernel(const InT* 
     }
 }
 
+// Timeline (logmel_timeline_core.h): ragged rows of 16 kHz PCM -> the DISTINCT slots of every recording's windows at a hop of 32 q
+// columns, out[slot][band][x]. The bags kernel's schedule and store over the items of the whole batch; what is new is the map from
+// an item to its recording, which is ragged here. It is the descriptors' first_item prefix, built on the host: a wave finds the
+// recording of its first item by a binary search and from then on walks forward (a workgroup's share is contiguous and its waves
+// pull increasing items, so the walk is usually zero or one step of scalar loads). The alternative, a range of workgroups per
+// recording, would leave a batch of one long and many short recordings to the few workgroups of the long one. Everything about an
+// item is wave-uniform; an item of columns without a spectrum (a short recording's missing examples) only stores zeros.
+struct TimelineCursor {
+    int rec, end_item;                       // the recording of the item and the first item past it
+    int first_item, cols, spec_cols, q;
+    int64_t first_slot;
+    int col;                                 // first column of the item
+};
+
+template <typename InT, typename OutT, bool VEC>
+__global__ __launch_bounds__(kThreadsDyn, 1) void logmel_timeline_kernel(const InT* __restrict__ pcm, int64_t row_stride,
+                                                                         const logmel_timeline::Rec* __restrict__ recs, int n_rec,
+                                                                         int n_items, const float* __restrict__ tab, OutT* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* s_xch = smem;
+    float* s_mel = s_xch + (kThreadsDyn / 16) * kPair * kXchFloats;
+    float* s_pw = s_mel + 16 * kMelRow;
+    float* s_win = s_pw + 16 * kPwPitch;
+    int* s_next = reinterpret_cast<int*>(s_win + kWinFloats);
+
+    const int t = threadIdx.x, g = t >> 4, gl = g & 3, j = t & 15, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    float* xa = s_xch + (kPair * g) * kXchFloats;
+    float* xb = xa + kXchFloats;
+    float* stage = s_xch + (kItemFrames * wv) * kXchFloats;      // the wave's first exchange buffer: 8 columns x 64 bands
+
+    LaneConsts c;
+    load_consts(c, tab, j);
+    for (int i = t; i < 16 * kMelRow; i += kThreadsDyn) s_mel[i] = tab[kTabMelW + i];
+    for (int i = t; i < 16 * kPwRow; i += kThreadsDyn) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
+    for (int i = t; i < kWinFloats; i += kThreadsDyn) s_win[i] = tab[kTabWindow + i];
+    // this workgroup's contiguous share of the items
+    const int lo = int(int64_t(n_items) * int64_t(blockIdx.x) / int64_t(gridDim.x)), hi = int(int64_t(n_items) * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
+    if (t == 0) *s_next = lo;
+    const float* melw = s_mel + kMelRow * j;
+    const float* pw = s_pw + kPwPitch * j;
+    __syncthreads();                        // the only workgroup barrier: tables and the counter visible
+
+    auto pull = [&]() {                      // wave-uniform: one lane takes the next item of the workgroup's share
+        int v = 0;
+        if (lane == 0) v = atomicAdd(s_next, 1);
+        return __builtin_amdgcn_readfirstlane(v);
+    };
+    const int lane_frame = kPair * gl;                        // this group's frame pair inside the item
+    auto uni = [](int64_t v) { return __builtin_amdgcn_readfirstlane(int(v)); };
+    auto enter = [&](TimelineCursor& k, int rec) {            // wave-uniform: the descriptor of `rec` into the cursor
+        const logmel_timeline::Rec& r = recs[rec];
+        k.rec = rec;
+        k.first_item = uni(r.first_item);
+        k.cols = uni(r.cols);
+        k.spec_cols = uni(r.spec_cols);
+        k.q = uni(r.q);
+        k.first_slot = (int64_t(uni(r.first_slot >> 32)) << 32) | uint32_t(uni(r.first_slot));
+        k.end_item = rec + 1 < n_rec ? uni(recs[rec + 1].first_item) : n_items;
+    };
+    // wave-uniform: moves the cursor (which stands at or before `item`) to `item` and returns the first sample of this group's
+    // pair, or null where the item's columns have no spectrum (or the item is past the share)
+    auto item_frame = [&](int item, TimelineCursor& k) -> const InT* {
+        if (item >= hi) return nullptr;
+        while (item >= k.end_item) enter(k, k.rec + 1);
+        k.col = logmel_timeline::item_column(item - k.first_item, k.cols, k.q);
+        if (k.col >= k.spec_cols) return nullptr;
+        return pcm + int64_t(k.rec) * row_stride + logmel_timeline::column_sample(k.col + lane_frame);
+    };
+    auto wave_fence = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    Samples<InT> smp;
+    int cur = pull();
+    if (cur >= hi) return;
+    TimelineCursor k;
+    enter(k, logmel_timeline::find_rec(recs, n_rec, cur));
+    const InT* frame = item_frame(cur, k);
+    bool fetched = false;                                      // smp holds `frame`'s samples (prefetched by the item before)
+    while (cur < hi) {
+        const int nxt = pull();
+        TimelineCursor kn = k;
+        const InT* next_frame = item_frame(nxt, kn);
+        f32x4 v_lo = {0.f, 0.f, 0.f, 0.f}, v_hi = {0.f, 0.f, 0.f, 0.f};
+        if (frame) {
+            // after a zero item, or at the start, nothing has been prefetched for this one
+            if (!fetched) smp.template fetch<VEC>(frame, j);
+            pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, ColsToStage{stage + lane_frame * kBands});
+            _Pragma("unroll") for (int x = 0; x < 4; ++x) {
+                v_lo[x] = stage[x * kBands + lane];
+                v_hi[x] = stage[(4 + x) * kBands + lane];
+            }
+            wave_fence();                   // the stage is rewritten by the next FFT
+        }
+        fetched = frame && next_frame;
+        _Pragma("unroll") for (int s = 0; s < logmel_timeline::kColumnSlots; ++s) {
+            int row, x;
+            if (logmel_timeline::column_slot(k.col, k.cols, k.q, s, &row, &x)) {
+                store_cols<OutT>(out + logmel_timeline::out_offset(k.first_slot, row, lane, x), v_lo, v_hi);
+            }
+        }
+        cur = nxt;
+        frame = next_frame;
+        k = kn;
+    }
+}
+
 // Fused front (bf16 inference): PCM -> conv1's pooled NHWC output in one kernel; the bf16 examples never exist in memory. The
 // stand-alone pair is bound by different things -- logmel_dyn_kernel by vector issue and LDS, conv1_patch_kernel by the store
 // path -- so here conv1's non-temporal stores drain while other waves run FFTs.
@@ -693,6 +802,23 @@ int launch_bags(const void* pcm, int64_t clips, int64_t row_stride, const int32_
 }
 
 template <typename InT, typename OutT>
+int launch_timeline(const void* pcm, int64_t row_stride, const int64_t* desc, int n_rec, int64_t n_items, const float* tables, void* out,
+                    hipStream_t stream) {
+    const bool vec = mla::aligned(pcm, 2 * sizeof(InT)) && (row_stride % 2 == 0);
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t wgs = (n_items + 7) / 8 < cus ? (n_items + 7) / 8 : cus;
+    auto go = [&](auto kern) -> int {
+        MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesDyn));
+        hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(kThreadsDyn), kLdsBytesDyn, stream, static_cast<const InT*>(pcm), row_stride,
+                           reinterpret_cast<const logmel_timeline::Rec*>(desc), n_rec, int(n_items), tables, static_cast<OutT*>(out));
+        MLA_LAUNCH_OK("logmel_timeline_kernel");
+        return MLA_OK;
+    };
+    return vec ? go(logmel_timeline_kernel<InT, OutT, true>) : go(logmel_timeline_kernel<InT, OutT, false>);
+}
+
+template <typename InT, typename OutT>
 int launch(const void* pcm, int64_t n_wave, int64_t wave_stride, int64_t examples, const float* tables,
            void* out, bool wave_sync, bool static_wave, hipStream_t stream) {
     const int64_t n_chunks = n_wave * examples * (kExFrames / kChunk);
@@ -823,6 +949,70 @@ extern "C" int mla_logmel_bags(const void* pcm, int pcm_dtype, int64_t clips, in
     }
     return out_dtype == MLA_F32 ? launch_bags<int16_t, float>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s)
                                 : launch_bags<int16_t, __hip_bfloat16>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s);
+}
+
+extern "C" int mla_timeline_counts(int64_t n_samples, int64_t hop_slots, int64_t* windows, int64_t* slots, int64_t* samples_read) {
+    MLA_REQUIRE(n_samples >= 0, MLA_E_ARG, "n_samples %lld < 0", (long long)n_samples);
+    MLA_REQUIRE(hop_slots >= 1 && hop_slots <= logmel_timeline::kMaxCols, MLA_E_ARG, "hop_slots %lld is not in 1 .. %lld", (long long)hop_slots,
+                (long long)logmel_timeline::kMaxCols);
+    int64_t W = 0, S = 0, cols = 0, spec = 0;
+    MLA_REQUIRE(logmel_timeline::counts(n_samples, hop_slots, &W, &S, &cols, &spec), MLA_E_SHORT,
+                "waveform of %lld samples gives a negative frame count (reference raises ValueError)", (long long)n_samples);
+    MLA_REQUIRE(cols <= logmel_timeline::kMaxCols, MLA_E_SHAPE, "%lld columns are more than one recording may have (%lld)", (long long)cols,
+                (long long)logmel_timeline::kMaxCols);
+    if (windows) *windows = W;
+    if (slots) *slots = S;
+    if (samples_read) *samples_read = logmel_timeline::samples_read(spec);
+    return MLA_OK;
+}
+
+extern "C" int mla_logmel_timeline(const void* pcm, int pcm_dtype, int64_t recordings, int64_t n_samples, int64_t row_stride,
+                                   const int64_t* desc, const int64_t* host_desc, int64_t total_slots, const float* tables, void* out,
+                                   int out_dtype, mla_stream_t stream) {
+    static_assert(sizeof(logmel_timeline::Rec) == logmel_timeline::kRecFields * sizeof(int64_t), "a descriptor is five int64");
+    MLA_REQUIRE(recordings >= 0 && n_samples >= 0 && row_stride >= n_samples && total_slots >= 0, MLA_E_ARG,
+                "bad recordings %lld / stride %lld < n_samples %lld / total_slots %lld", (long long)recordings, (long long)row_stride,
+                (long long)n_samples, (long long)total_slots);
+    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d is neither MLA_F32 nor MLA_I16", pcm_dtype);
+    MLA_REQUIRE(out_dtype == MLA_F32 || out_dtype == MLA_BF16, MLA_E_DTYPE, "out_dtype %d is neither MLA_F32 nor MLA_BF16", out_dtype);
+    if (recordings == 0) {
+        MLA_REQUIRE(total_slots == 0, MLA_E_ARG, "no recordings but %lld slots", (long long)total_slots);
+        return MLA_OK;
+    }
+    MLA_REQUIRE(pcm && desc && host_desc && tables && out, MLA_E_ARG, "null pcm/desc/host_desc/tables/out");
+    MLA_REQUIRE(mla::aligned(out, 16), MLA_E_ARG, "out must be 16-byte aligned");
+    MLA_REQUIRE(mla::aligned(tables, 4) && mla::aligned(desc, 8), MLA_E_ARG, "tables must be 4-byte and desc 8-byte aligned");
+    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
+    MLA_REQUIRE(recordings <= 0x7fffffff / logmel_timeline::kWindowItems, MLA_E_SHAPE, "too many recordings for one launch (%lld)",
+                (long long)recordings);
+    const logmel_timeline::Rec* recs = reinterpret_cast<const logmel_timeline::Rec*>(host_desc);
+    int64_t slot_prefix = 0, item_prefix = 0;
+    for (int64_t i = 0; i < recordings; ++i) {
+        const logmel_timeline::Rec& r = recs[i];
+        const int bad = logmel_timeline::check_rec(r, n_samples, slot_prefix, item_prefix);
+        MLA_REQUIRE(bad != 1, MLA_E_ARG, "recording %lld: hop_slots %lld is not in 1 .. %lld", (long long)i, (long long)r.q,
+                    (long long)logmel_timeline::kMaxCols);
+        MLA_REQUIRE(bad != 2 && bad != 3, MLA_E_ARG, "recording %lld: %lld columns (%lld with a spectrum) at hop_slots %lld are no track",
+                    (long long)i, (long long)r.cols, (long long)r.spec_cols, (long long)r.q);
+        MLA_REQUIRE(bad != 4, MLA_E_SHAPE, "recording %lld: %lld columns read %lld samples, the rows hold %lld", (long long)i,
+                    (long long)r.spec_cols, (long long)logmel_timeline::samples_read(r.spec_cols), (long long)n_samples);
+        MLA_REQUIRE(bad == 0, MLA_E_ARG, "recording %lld: first_slot %lld / first_item %lld are not the sums before it (%lld / %lld)",
+                    (long long)i, (long long)r.first_slot, (long long)r.first_item, (long long)slot_prefix, (long long)item_prefix);
+        slot_prefix += logmel_timeline::slots_of(r.cols, r.q);
+        item_prefix += logmel_timeline::items_of(r.cols, r.q);
+        MLA_REQUIRE(item_prefix <= 0x7fffffff, MLA_E_SHAPE, "too many columns for one launch (%lld items at recording %lld)",
+                    (long long)item_prefix, (long long)i);
+    }
+    MLA_REQUIRE(slot_prefix == total_slots, MLA_E_ARG, "the descriptors fill %lld slots, out has %lld", (long long)slot_prefix,
+                (long long)total_slots);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int n_rec = int(recordings);
+    if (pcm_dtype == MLA_F32) {
+        return out_dtype == MLA_F32 ? launch_timeline<float, float>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s)
+                                    : launch_timeline<float, __hip_bfloat16>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s);
+    }
+    return out_dtype == MLA_F32 ? launch_timeline<int16_t, float>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s)
+                                : launch_timeline<int16_t, __hip_bfloat16>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s);
 }
 
 extern "C" int mla_logmel_conv1(const void* pcm, int pcm_dtype, int64_t n_wave, int64_t n_samples, int64_t wave_stride,

@@ -644,6 +644,20 @@ __global__ __launch_bounds__(256) void linear_small_bwd_kernel(const float* __re
     }
 }
 
+// Bags from shared rows: out[(w T + t)][:] = emb[first_row[w] + t][:]. Windows of one recording overlap in their slots, so the CNN
+// runs once per distinct slot and the head's (bags, T, M) input is gathered here. V = floats per access: 4 (16 bytes) or 1.
+template <int V>
+__global__ __launch_bounds__(256) void gather_bags_kernel(const float* __restrict__ emb, int64_t ld, const int64_t* __restrict__ first_row,
+                                                          int64_t windows, int T, int64_t M, float* __restrict__ out) {
+    typedef float vec_t __attribute__((ext_vector_type(V)));
+    const int64_t per_row = M / V, total = windows * T * per_row;
+    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += int64_t(gridDim.x) * 256) {
+        const int64_t r = i / per_row, p = i - r * per_row, w = r / T;
+        const int t = int(r - w * T);
+        *reinterpret_cast<vec_t*>(out + r * M + p * V) = *reinterpret_cast<const vec_t*>(emb + (first_row[w] + t) * ld + p * V);
+    }
+}
+
 }  // namespace
 
 // partials ([blocks][channels][2] doubles: 512 x 64 or 32 x 1024, the same area), then the tail mla_bn_stats keeps its sums in
@@ -875,6 +889,27 @@ extern "C" int mla_linear_narrow(const float* a, int64_t lda, const float* w, in
     MLA_NARROW_CASE(16)
 #undef MLA_NARROW_CASE
     MLA_LAUNCH_OK("linear_narrow");
+    return MLA_OK;
+}
+
+extern "C" int mla_gather_bags(const float* emb, int64_t rows, int64_t ld, const int64_t* first_row, const int64_t* host_first_row,
+                               int64_t windows, int T, int64_t M, float* out, mla_stream_t stream) {
+    MLA_REQUIRE(rows >= 0 && windows >= 0 && T >= 1 && M >= 1 && ld >= M, MLA_E_ARG, "bad gather_bags sizes (rows %lld, windows %lld, T %d, M %lld, ld %lld)",
+                (long long)rows, (long long)windows, T, (long long)M, (long long)ld);
+    if (windows == 0) return MLA_OK;
+    MLA_REQUIRE(emb && first_row && host_first_row && out, MLA_E_ARG, "null emb/first_row/host_first_row/out");
+    MLA_REQUIRE(mla::aligned(emb, 4) && mla::aligned(out, 4) && mla::aligned(first_row, 8), MLA_E_ARG, "gather_bags operands are misaligned");
+    for (int64_t w = 0; w < windows; ++w) {
+        MLA_REQUIRE(host_first_row[w] >= 0 && host_first_row[w] <= rows - T, MLA_E_ARG, "window %lld: rows %lld .. %lld leave emb (%lld rows)",
+                    (long long)w, (long long)host_first_row[w], (long long)host_first_row[w] + T - 1, (long long)rows);
+    }
+    const bool vec = M % 4 == 0 && ld % 4 == 0 && mla::aligned(emb, 16) && mla::aligned(out, 16);
+    const int64_t blocks = (windows * T * (vec ? M / 4 : M) + 255) / 256;
+    const dim3 grid(unsigned(blocks < 4096 ? blocks : 4096));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(gather_bags_kernel<4>, grid, dim3(256), 0, s, emb, ld, first_row, windows, T, M, out);
+    else hipLaunchKernelGGL(gather_bags_kernel<1>, grid, dim3(256), 0, s, emb, ld, first_row, windows, T, M, out);
+    MLA_LAUNCH_OK("gather_bags");
     return MLA_OK;
 }
 

@@ -359,6 +359,85 @@ def audiofiles_to_frames(paths, overlap=True, out_dtype=torch.float32):
     return _bags(_pack_audiofiles(files, SR_VGGISH, SAMPLES_NUM_VGGISH), counts, overlap, out_dtype)
 
 
+# ---- timelines: recordings of any length in windows of four examples (no counterpart in the reference, whose loader stops at 4 s) ----
+HOP_SECONDS = 0.32                                # one slot of hop: 32 log-mel columns
+_CLIPS_MAX_SAMPLES = 0x7fffffff - 256             # mla_clips_prepare: samples_num, and rows * ceil(samples_num / 256) workgroups
+
+
+def timeline_counts(n, hop_slots=3):
+    """(windows, kept slots, samples read) of a recording of n samples at 16 kHz scored at a hop of hop_slots * 0.32 s:
+    frontend.timeline_counts. n >= 61 680: windows = 1 + (n - 61 680) // (5 120 * hop_slots), window j the native bag of
+    wave[5 120 * hop_slots * j :][: 61 680]; 240 <= n < 61 680: one window, the bag recordings_to_frames gives; n < 240: ValueError."""
+    return frontend.timeline_counts(n, hop_slots)
+
+
+def _timeline_lengths(frames, rates, hop_slots):
+    """Samples of every recording once it is at 16 kHz (the library's resampled length), checked: ValueError, naming the recording,
+    for fewer than 240 of them; and for a batch whose rows the clips launch cannot tile. -> (lengths, samples per row)."""
+    if int(hop_slots) != hop_slots or hop_slots < 1:
+        raise ValueError("hop_slots must be an integer >= 1 (the hop is hop_slots * 0.32 s), got %r" % (hop_slots,))
+    L = _lib.lib()
+    n16, most = np.zeros(len(frames), dtype=np.int64), 1
+    for i, (n, r) in enumerate(zip(frames, rates)):
+        n16[i] = int(n) if float(r) == float(SR_VGGISH) else int(L.mla_resample_length(int(n), float(r), float(SR_VGGISH)))
+        try:
+            most = max(most, frontend.timeline_counts(n16[i], hop_slots)[2])
+        except ValueError as e:
+            raise ValueError("recording %d: %s (%d samples at 16 kHz)" % (i, e, n16[i])) from None
+    if most > _CLIPS_MAX_SAMPLES or len(frames) * ((most + 255) // 256) > 0x7fffffff:
+        raise ValueError("%d recordings of up to %d samples at 16 kHz are more than one clips launch tiles (rows of at most %d "
+                         "samples, at most 2**31 - 1 tiles of 256 samples in the batch): split the batch" % (len(frames), most, _CLIPS_MAX_SAMPLES))
+    return n16, most
+
+
+def _slots(clips, n16, hop_slots, out_dtype):
+    if clips.shape[0] == 0:
+        none = np.zeros(0, dtype=np.int64)
+        return torch.empty((0, 64, 96), dtype=out_dtype, device=clips.device), none, none, np.zeros(0, dtype=np.float64)
+    slots, first_rows, index = frontend.logmel_timeline(clips, n16, hop_slots, out_dtype)
+    step = min(int(hop_slots), T)
+    starts = np.zeros(first_rows.shape[0], dtype=np.float64)
+    if first_rows.shape[0]:
+        first = first_rows[np.searchsorted(index, index)]          # the first window's row of each window's recording
+        starts = HOP_SECONDS * hop_slots * ((first_rows - first) // step)
+    return slots, first_rows, index, starts
+
+
+def recordings_to_slots(recordings, rates, hop_slots=3, out_dtype=torch.float32):
+    """Recordings of ANY length as they are decoded -> (slots, first_rows, recording_index, start_seconds) in TWO launches
+    whatever the batch is: recordings_to_clips at 16 kHz (channel mean, resampy 'kaiser_best' over the whole recording) into rows
+    as long as the longest recording needs, then frontend.logmel_timeline.
+
+    A recording of n samples at 16 kHz is scored in windows of four 0.96 s examples (61 680 samples, the bag of
+    recordings_to_frames) that start hop_slots * 0.32 s apart: timeline_counts(n, hop_slots). A trailing stretch that fills no
+    window is dropped, as the reference drops a trailing partial example; a recording shorter than one window gives the one bag
+    recordings_to_frames gives. slots: (S, 64, 96) device tensor in out_dtype (float32, or bfloat16 with one rounding), the
+    distinct 96-column slots of all windows, each computed once; first_rows / recording_index (host int64) and start_seconds (host
+    float64) have one entry per window: slots[first_rows[w] : first_rows[w] + 10] is the (10, 64, 96) bag of the window that starts
+    start_seconds[w] into recordings[recording_index[w]], bit for bit the bag recordings_to_frames gives for that crop of the
+    resampled recording. recordings / rates: as recordings_to_clips takes them, with its errors; ValueError, naming the recording,
+    for fewer than 240 samples at 16 kHz. Limit (the clips launch tiles a row in 256-sample workgroups): rows of at most
+    2**31 - 257 samples, about 37 hours, and at most 2**31 - 1 tiles in the batch; more raises ValueError. All errors come before
+    anything is copied or launched."""
+    recs, rates = _checked_recordings(recordings, rates, SR_VGGISH)
+    n16, most = _timeline_lengths([x.shape[0] for x in recs], rates, hop_slots)
+    return _slots(_pack_recordings(recs, rates, SR_VGGISH, most), n16, hop_slots, out_dtype)
+
+
+def wavfiles_to_slots(paths, hop_slots=3, out_dtype=torch.float32):
+    """16-bit WAV files -> recordings_to_slots: read_wav16 on every path (other widths are refused)."""
+    return recordings_to_slots(*_read_wav16s(paths), hop_slots, out_dtype)
+
+
+def audiofiles_to_slots(paths, hop_slots=3, out_dtype=torch.float32):
+    """WAV files of any mixture of encodings read_audiofile accepts -> what recordings_to_slots returns, in two launches: the
+    files' bytes are decoded, mixed and resampled to 16 kHz by frontend.prepare_clips_raw, then frontend.logmel_timeline.
+    Bit-identical to wavfiles_to_slots for 16-bit files."""
+    files = _checked_audiofiles(paths, SR_VGGISH)
+    n16, most = _timeline_lengths([d[1][3] for d in files], [d[1][2] for d in files], hop_slots)
+    return _slots(_pack_audiofiles(files, SR_VGGISH, most), n16, hop_slots, out_dtype)
+
+
 # ---- the VGGish branch on the librosa path: load_hdf5(cnn_type="vggish", use_librosa=True), dataset.py:232-243, :305-307, :316 -------
 SAMPLES_NUM_VGGISH_LIBROSA = SR_VGGISH * 4       # 64 000: the reference's SAMPLES_NUM_VGGISH (params.py:10), the rows of this path
 LIBROSA_N_MELS, LIBROSA_HOP, LIBROSA_FMIN, LIBROSA_FMAX, LIBROSA_TOP_DB = 64, 160, 125.0, 7500.0, 80.0

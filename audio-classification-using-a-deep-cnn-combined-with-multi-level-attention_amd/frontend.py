@@ -288,8 +288,78 @@ def logmel_bags(pcm, counts, n_frames=10, stride=32, out_dtype=torch.float32, ou
     return out
 
 
+def timeline_counts(n_samples, hop_slots):
+    """(windows, kept slots, samples read) of a 16 kHz recording of n_samples scored at a hop of hop_slots * 0.32 s
+    (mla_timeline_counts, the single source of the arithmetic; include/mla_hip.h states it). ValueError for fewer than 240
+    samples, where the reference raises, and for hop_slots < 1."""
+    if int(hop_slots) != hop_slots or hop_slots < 1:
+        raise ValueError("hop_slots must be an integer >= 1 (the hop is hop_slots * 0.32 s), got %r" % (hop_slots,))
+    w, s, r = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    rc = _lib.lib().mla_timeline_counts(int(n_samples), int(hop_slots), ctypes.byref(w), ctypes.byref(s), ctypes.byref(r))
+    if rc == _lib.E_SHORT:
+        raise ValueError("negative dimensions are not allowed")
+    _lib.check(rc)
+    return w.value, s.value, r.value
+
+
+def timeline_descriptors(n_valid, hop_slots):
+    """The (R, 5) int64 descriptors mla_logmel_timeline takes for recordings of n_valid[i] samples at 16 kHz -- first_slot, cols,
+    spec_cols, first_item, q per recording -- with (the windows of each, all kept slots, the most samples a row must hold)."""
+    q = int(hop_slots)
+    desc = np.zeros((len(n_valid), 5), dtype=np.int64)
+    windows = np.zeros(len(n_valid), dtype=np.int64)
+    slot, item, most = 0, 0, 0
+    for i, n in enumerate(n_valid):
+        w, s, read = timeline_counts(int(n), q)
+        cols = 32 * q * (w - 1) + 384
+        desc[i] = (slot, cols, max(read - 240, 0) // 160, item, q)      # `read` samples = 160 spec_cols + 240, or none
+        windows[i] = w
+        slot += s
+        item += 48 + min(4 * q, 48) * (w - 1)
+        most = max(most, read)
+    return desc, windows, slot, most
+
+
+def logmel_timeline(pcm, n_valid, hop_slots=3, out_dtype=torch.float32, out=None):
+    """(R, n) device rows of 16 kHz mono PCM (float32 or int16), row i a recording of n_valid[i] samples of which the row holds at
+    least timeline_counts(n_valid[i], hop_slots)[2] -> (slots, first_rows, recording_index) in ONE launch of csrc/logmel.hip
+    (logmel_timeline_kernel). slots: (S, 64, 96) in `out_dtype` (float32 or bfloat16), the DISTINCT 96-column slots of every
+    recording's windows at a hop of hop_slots * 0.32 s, each log-mel column computed once. first_rows / recording_index: host
+    int64 arrays with one entry per window, recordings in order and windows in order of time: slots[first_rows[w] : first_rows[w]
+    + 10] is window w's bag, bit for bit what logmel_bags gives for the crop pcm[i, 5120 * hop_slots * j :][: 61680] (a recording
+    of fewer than 61 680 samples has one window, its logmel_bags bag). n_valid: host integers (a device tensor is read back
+    first); the descriptors travel in one pinned buffer and one copy. Nothing beyond the samples counted is read. `out`, when
+    given, is overwritten completely."""
+    assert pcm.dim() == 2 and pcm.is_cuda and (pcm.shape[1] <= 1 or pcm.stride(1) == 1) and pcm.dtype in (torch.float32, torch.int16)
+    R, n = pcm.shape
+    nv = _host_array(n_valid, np.int64)
+    assert nv.shape[0] == R, "one length per row"
+    desc, windows, total, _ = timeline_descriptors(nv, hop_slots)
+    if out is None:
+        out = torch.empty((total, 64, 96), dtype=out_dtype, device=pcm.device)
+    else:
+        assert out.is_cuda and out.is_contiguous() and out.dtype == out_dtype and tuple(out.shape) == (total, 64, 96)
+    recording_index = np.repeat(np.arange(R, dtype=np.int64), windows)
+    step = min(int(hop_slots), 10)
+    first_rows = np.concatenate([desc[i, 0] + step * np.arange(windows[i], dtype=np.int64) for i in range(R)]) if R else np.zeros(0, np.int64)
+    if R == 0:
+        return out, first_rows, recording_index
+    pcm_code = {torch.float32: _lib.F32, torch.int16: _lib.I16}[pcm.dtype]
+    out_code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}[out_dtype]
+    tab = device_tables(pcm.device)
+    host = torch.empty(desc.size, dtype=torch.int64, pin_memory=True)
+    host.numpy()[:] = desc.reshape(-1)
+    d = host.to(pcm.device, non_blocking=True)
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("logmel_timeline", _lib.lib().mla_logmel_timeline, vp(pcm.data_ptr()), pcm_code, R, n, pcm.stride(0) if R > 1 else n,
+                          vp(d.data_ptr()), desc.ctypes.data_as(vp), total, vp(tab.data_ptr()), vp(out.data_ptr()), out_code,
+                          _lib.stream_ptr()))
+    return out, first_rows, recording_index
+
+
 _melspec_tables = {}
-MELSPEC_AMIN = 1e-10      # librosa.power_to_db's default amin (ref = 1.0)
+MELSPEC_AMIN = 1e-10     # librosa.power_to_db's default amin (ref = 1.0)
 
 
 def melspec_tables(device, sr, n_mels):

@@ -226,6 +226,48 @@ class Ensemble(nn.Module):
         from . import dataset
         return self._native_bags("forward_audiofiles_native", dataset.audiofiles_to_frames, (paths,), overlap)
 
+    def _timeline(self, what, slots_fn, source, hop_slots, max_slots):
+        """Recordings of any length scored over time: the distinct slots of all windows in two launches (dataset.recordings_to_slots),
+        the CNN once per distinct slot in chunks of at most max_slots, the windows' bags gathered from the embeddings
+        (ops.gather_bags), then the head. BatchNorm1d(T) of the head is per slot position, so only the CNN is shared."""
+        if self.cnn_type != "vggish":
+            raise NotImplementedError("%s scores the VGGish branch's log-mel bags over time; cnn_type 'resnet' has no timeline path: "
+                                      "crop 4 s pieces on the host and use forward_recordings()" % what)
+        self._ten_window_bags(what)
+        if self.training:
+            raise RuntimeError("%s runs in eval mode only: batch statistics over the windows of one recording are no defined training "
+                               "step, and the chunks of max_slots would change them; call eval() first" % what)
+        if int(max_slots) < 1:
+            raise ValueError("%s: max_slots must be >= 1, got %r" % (what, max_slots))
+        dtype = torch.bfloat16 if self.cnn.precision == "bf16" else torch.float32
+        slots, first_rows, index, starts = slots_fn(*source, hop_slots=hop_slots, out_dtype=dtype)
+        if first_rows.shape[0] == 0:
+            return torch.empty((0, self.classes), dtype=torch.float32, device=slots.device), index, starts
+        ex = slots.view(slots.shape[0], S_VGGISH_SHAPE[0], S_VGGISH_SHAPE[1])        # Input's reshape (model.py:98-99), not a transpose
+        parts = [self.cnn(ex[at:at + int(max_slots)]) for at in range(0, ex.shape[0], int(max_slots))]
+        emb = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return self.mla(ops.gather_bags(emb, first_rows, T).view(-1, T, self.emb_input_size)), index, starts
+
+    def score_timeline(self, recordings, rates, hop_slots=3, max_slots=8192):
+        """The VGGish branch over recordings of ANY length (host arrays, (n,) or (n, channels), int16 or floating, any rates): one
+        score vector per window of four 0.96 s examples, the windows hop_slots * 0.32 s apart (dataset.recordings_to_slots states
+        which). -> (scores (windows of all recordings, K) on the device, recording_index (int64, host), start_seconds (float64,
+        host)), recordings in order and windows in order of time. A recording shorter than one window gives the one row
+        forward_recordings_native gives. The CNN runs once per distinct 0.96 s slot, max_slots of them at a time (which bounds its
+        activations); eval mode only."""
+        from . import dataset
+        return self._timeline("score_timeline", dataset.recordings_to_slots, (recordings, rates), hop_slots, max_slots)
+
+    def score_timeline_wavfiles(self, paths, hop_slots=3, max_slots=8192):
+        """score_timeline for 16-bit WAV files (dataset.wavfiles_to_slots)."""
+        from . import dataset
+        return self._timeline("score_timeline_wavfiles", dataset.wavfiles_to_slots, (paths,), hop_slots, max_slots)
+
+    def score_timeline_audiofiles(self, paths, hop_slots=3, max_slots=8192):
+        """score_timeline for WAV files of any PCM width or IEEE float (dataset.audiofiles_to_slots)."""
+        from . import dataset
+        return self._timeline("score_timeline_audiofiles", dataset.audiofiles_to_slots, (paths,), hop_slots, max_slots)
+
     def _librosa_bags(self, what, frames_fn, source, overlap):
         """The VGGish branch on the reference's librosa dataset path (load_hdf5(cnn_type="vggish", use_librosa=True), mnemonic
         vggish_10_s): HTK mel-dB bags written in the CNN's compute dtype, then the CNN and the head as _native_bags runs them."""

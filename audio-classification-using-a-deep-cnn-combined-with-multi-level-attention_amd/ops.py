@@ -290,6 +290,28 @@ def attention_pool(z, bags, T, K, nv, nf, y, save=False):
 
 # ----------------------------------------------------------------- training-step kernels ----
 
+def gather_bags(emb, first_rows, T):
+    """(N, M) float32 embeddings (rows may be strided) and the first row of each of W windows -> the (W * T, M) head input
+    out[w * T + t] = emb[first_rows[w] + t] in one launch (mla_gather_bags). Windows may overlap: a timeline's CNN runs once per
+    distinct slot and its bags are gathered here. first_rows: host integers (a device tensor is read back first); they travel in
+    one pinned buffer and one copy. A window that leaves emb raises before anything is launched."""
+    import numpy as np
+    _chk_rows(emb, torch.float32)
+    if isinstance(first_rows, torch.Tensor):
+        first_rows = first_rows.detach().cpu().numpy()
+    fr = np.ascontiguousarray(np.asarray(first_rows), dtype=np.int64).reshape(-1)
+    W, (N, M) = fr.shape[0], emb.shape
+    out = torch.empty((W * int(T), M), dtype=torch.float32, device=emb.device)
+    if W == 0:
+        return out
+    host = torch.empty(W, dtype=torch.int64, pin_memory=True)
+    host.numpy()[:] = fr
+    d = host.to(emb.device, non_blocking=True)
+    _lib.check(_timed("gather_bags", _lib.lib().mla_gather_bags, _p(emb), N, emb.stride(0) if N > 1 else M, _p(d),
+                      fr.ctypes.data_as(ctypes.c_void_p), W, int(T), M, _p(out), _lib.stream_ptr()))
+    return out
+
+
 class Dist:
     """Data-parallel context of the training step: SyncBN statistics, gradient buffer, loss and hit count are summed over
     the ranks of a ``torch.distributed`` process group.

@@ -127,6 +127,35 @@ int mla_dataset_frames(const float* examples, int64_t clips, int ex_per_clip, in
 int mla_logmel_bags(const void* pcm, int pcm_dtype, int64_t clips, int64_t n_samples, int64_t row_stride, const int32_t* counts,
                     const int32_t* host_counts, int n_frames, int stride, const float* tables, void* out, int out_dtype,
                     mla_stream_t stream);
+/* ---- Timelines: a recording of any length scored in windows of four examples at a hop of hop_slots * 0.32 s ----
+ * Host only, the single source of the arithmetic. A 16 kHz recording of n_samples has log-mel columns 0 .. (n - 400) / 160; slot u
+ * is columns [32 u, 32 u + 96). With q = hop_slots >= 1:
+ *   n >= 61 680: windows = 1 + (n - 61 680) / (5 120 q); window j is the bag mla_logmel_bags gives for the crop
+ *     [5 120 q j, 5 120 q j + 61 680), i.e. slots q j .. q j + 9; a trailing stretch that fills no window is dropped;
+ *   240 <= n < 61 680: one window, the bag mla_logmel_bags gives (examples the recording lacks are 0.0).
+ * A slot is kept iff u mod q < 10 (and u <= q (windows - 1) + 9); *slots is their number: q (windows - 1) + 10 for q <= 10, where
+ * window j is rows q j .. q j + 9 of the recording's kept slots, and 10 * windows for q > 10, window j = rows 10 j .. 10 j + 9.
+ * *samples_read = all a row must hold: 61 680 + 5 120 q (windows - 1), or 15 600 + 15 360 (examples - 1) (0 without an example).
+ * Any output pointer may be NULL. n_samples < 240 -> MLA_E_SHORT (the reference raises); n_samples < 0 or hop_slots < 1 -> MLA_E_ARG. */
+int mla_timeline_counts(int64_t n_samples, int64_t hop_slots, int64_t* windows, int64_t* slots, int64_t* samples_read);
+/* The kept slots of a RAGGED batch of recordings in one launch, each column's spectrum computed once however many windows share it.
+ * pcm[recordings][row_stride] as in mla_logmel_bags (the first n_samples of a row are valid input). desc[recordings][5] (DEVICE,
+ * int64) and host_desc, the same array on the HOST, read for validation before anything is launched. Per recording:
+ *   [0] first_slot  first row of out it writes: the kept slots of the recordings before it
+ *   [1] cols        columns in its track: 32 q (windows - 1) + 384
+ *   [2] spec_cols   columns that have a spectrum: cols, or for a one-window track 96 * examples (0, 96, 192 or 288)
+ *   [3] first_item  work items (8 columns) before it: per recording 48 + min(4 q, 48) (windows - 1)
+ *   [4] q           hop_slots of this recording
+ * out[total_slots][64][96], MLA_F32 or MLA_BF16 (one rounding of the f32 value), 16-byte aligned: out[first_slot + r][b][x] =
+ * log-mel of band b, column 32 u + x, for the recording's r-th kept slot u; exactly 0.0 for columns >= spec_cols. The layout of
+ * mla_logmel_bags' windows: ten consecutive rows from a window's first row ARE its bag, bit for bit. Every element of out is
+ * written exactly once; columns in no kept slot (q > 11) get no spectrum; no sample beyond 160 spec_cols + 240 of a row is read.
+ * Errors, all before any launch: null pointer, misaligned out, q < 1, (cols, spec_cols) that are no track, first_slot /
+ * first_item that are not the sums before them, total_slots that is not the sum -> MLA_E_ARG; a descriptor that reads past
+ * n_samples, more than 2^31 - 1 items -> MLA_E_SHAPE; dtype codes -> MLA_E_DTYPE. recordings == 0 returns MLA_OK. */
+int mla_logmel_timeline(const void* pcm, int pcm_dtype, int64_t recordings, int64_t n_samples, int64_t row_stride, const int64_t* desc,
+                        const int64_t* host_desc, int64_t total_slots, const float* tables, void* out, int out_dtype,
+                        mla_stream_t stream);
 /* ---- ResNet branch front-end: dataset.create_spec(cnn_type="resnet") + split (dataset.py:309-316, :329-363) ----
  * librosa.feature.melspectrogram(y, sr, n_mels=n_mels, hop_length=hop) with its defaults (n_fft = win_length = 2048,
  * periodic Hann, center=True, pad_mode="reflect", power 2, Slaney mel basis over 0..sr/2, norm="slaney") followed by
@@ -309,6 +338,14 @@ int mla_attention_pool(const float* z, int64_t bags, int T, int K, const float* 
                        const float* v_gamma, const float* v_beta, const float* f_mean, const float* f_var,
                        const float* f_gamma, const float* f_beta, float eps, float* y, int64_t ldy,
                        float* att_out, float* cla_out, mla_stream_t stream);
+
+/* Bags of T consecutive rows out of shared embeddings: out[(w T + t)][m] = emb[first_row[w] + t][m], m < M. emb (rows, M; leading
+ * dimension ld), out (windows * T, M) contiguous, both f32; first_row[windows] (DEVICE, int64) and host_first_row, the same on the
+ * HOST for validation. Windows may overlap (a timeline's do). BatchNorm1d(T) of the head is per slot position, so only the CNN is
+ * shared between windows, not the head. 16-byte accesses where M, ld and both pointers allow, scalar ones otherwise.
+ * Errors: negative sizes, T < 1, M < 1, ld < M, null pointers, a window that leaves emb -> MLA_E_ARG. windows == 0 returns MLA_OK. */
+int mla_gather_bags(const float* emb, int64_t rows, int64_t ld, const int64_t* first_row, const int64_t* host_first_row,
+                    int64_t windows, int T, int64_t M, float* out, mla_stream_t stream);
 
 /* Two-stage form of mla_bn_stats for data-parallel training: stage 1 writes the LOCAL
  * per-channel (sum x, sum x^2) as 2*channels doubles; the host side may all-reduce them over
