@@ -17,7 +17,7 @@ from torch import nn
 
 from . import differentiable, mla_train, ops, resnet
 from .params import *  # noqa: F401,F403  (T, H, K, DR, M_VGGISH, M_VGGISH_JB, S_VGGISH_SHAPE: model.py:9)
-from .torchvggish.vggish import Linear, PcmInput, VGGish
+from .torchvggish.vggish import Linear, PcmInput, VGGish, cache_stamp, weight_caches
 
 
 class BatchNorm1d(nn.Module):
@@ -346,11 +346,19 @@ class Ensemble(nn.Module):
 class GraphedWaveforms:
     """forward_waveforms of an eval-mode Ensemble captured once into a HIP graph. The C-ABI kernels are plain
     launches on torch's current stream, so torch's capture records them; scratch tensors allocated while
-    capturing live in the graph's private pool. Call with a tensor of the captured shape/dtype."""
+    capturing live in the graph's private pool. Call with a tensor of the captured shape/dtype.
+
+    The recorded kernels also address memory the capture did not allocate: the cached weight copies (repacked / bf16) and the
+    library's scratch buffers. Those tensors are kept in ``held`` for as long as this object lives, so their addresses stay the
+    graph's even after the cache or ``ops`` has moved on to newer ones; a grown scratch buffer therefore changes nothing. What
+    would make a replay compute something else than ``forward_waveforms`` does now -- weights changed in place or re-seated
+    (load_state_dict), set_precision, a train() switch -- is compared on the host before every replay and raises RuntimeError:
+    the output buffer is static, so the caller has to capture again. ``captures`` counts the graphs recorded (always 1)."""
 
     def __init__(self, model, pcm):
         assert not model.training, "graph capture covers the eval-mode forward (train-mode statistics sync with the host)"
         self.model = model
+        self.captures = 0
         self.static_in = pcm.clone()
         side = torch.cuda.Stream(device=pcm.device)
         side.wait_stream(torch.cuda.current_stream(pcm.device))
@@ -361,8 +369,20 @@ class GraphedWaveforms:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="relaxed"), torch.no_grad():
             self.static_out = model.forward_waveforms(self.static_in)
+        self.captures += 1
+        self.stamp = self._stamp()
+        self.held = [t for c in weight_caches(model.cnn) for t in c.tensors()] + list(ops.scratch(pcm.device).values())
+
+    def _stamp(self):
+        m = self.model
+        return {"train / eval mode": m.training, "precision": m.cnn.precision,
+                "CNN weights (written in place or re-seated, e.g. by load_state_dict)": cache_stamp(weight_caches(m.cnn))}
 
     def __call__(self, pcm):
+        now = self._stamp()
+        if now != self.stamp:
+            raise RuntimeError("the captured forward_waveforms graph no longer matches the model: %s changed since the capture; "
+                               "call capture_waveforms() again" % ", ".join(k for k in now if now[k] != self.stamp[k]))
         if pcm.data_ptr() != self.static_in.data_ptr():
             assert pcm.shape == self.static_in.shape and pcm.dtype == self.static_in.dtype
             self.static_in.copy_(pcm, non_blocking=True)

@@ -753,6 +753,13 @@ def relu_pool_bwd(a, d_out, pool, db=None, bf16=False):
 _wg_ws = {}
 
 
+def scratch(device):
+    """The live scratch entries of `device`, {key: tensor}. An entry is REPLACED when a call needs more room than it has, and
+    the old tensor goes back to torch's allocator unless somebody else holds it: whoever records an entry's address in a HIP
+    graph keeps the tensor from this dict (so the address stays the graph's) and compares data_ptr() before a replay."""
+    return {(i, k): t for i, d in enumerate((_ws, _wg_ws)) for k, t in d.items() if t.device == device}
+
+
 def conv_wgrad(dz, a_in, dw):
     _chk(dz); _chk(a_in, dz.dtype)
     n, H, W_, cout = dz.shape

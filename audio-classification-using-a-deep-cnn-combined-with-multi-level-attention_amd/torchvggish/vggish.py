@@ -56,13 +56,36 @@ class _Cache:
     """Derived (repacked / bf16) weight copies, refreshed when a parameter changes in place."""
 
     def __init__(self):
-        self.key, self.val = None, None
+        self.key, self.val, self.params = None, None, ()
 
     def get(self, params, dtype, make):
         key = (dtype,) + tuple((p.data_ptr(), p._version) for p in params)
+        self.params = tuple(params)
         if key != self.key:
             self.key, self.val = key, make()
         return self.val
+
+    def tensors(self):
+        """The copies handed out last (a list, or a dict per layer)."""
+        val = self.val if self.val is not None else ()
+        return list(val.values()) if isinstance(val, dict) else list(val)
+
+
+def cache_stamp(caches, skip=lambda p: False):
+    """What a HIP graph that recorded the addresses of the copies in `caches` compares before each replay: the (data_ptr, _version)
+    of every tensor the copies derive from (host reads only, no device sync). An in-place change of such a tensor (load_state_dict,
+    copy_) or a re-seated one makes the next eager call derive fresh copies; a graph keeps reading the ones it recorded. skip(p):
+    tensors the graph's holder accounts for itself (TrainStep: the views of its flat buffer, which Adam writes behind the counters)."""
+    return tuple((p.data_ptr(), p._version) for c in caches for p in c.params if not skip(p))
+
+
+def weight_caches(cnn):
+    """Every cache of derived weight copies below a ``model.CNN`` that a captured forward reads: the VGGish containers' and the
+    ResNet trunk's repacks (its eval-mode BatchNorm coefficients are not read by any graph: the training step runs the trunk in train
+    mode, and the waveform graph is VGGish only)."""
+    caches = [m._cache for m in cnn.modules() if isinstance(getattr(m, "_cache", None), _Cache)]
+    rn = getattr(cnn, "_rn_cache", None)
+    return caches + ([rn["w"]] if rn is not None else [])
 
 
 class PcmInput:

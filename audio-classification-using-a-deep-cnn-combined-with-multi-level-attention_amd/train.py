@@ -21,6 +21,7 @@ from torch.utils.data import Dataset
 
 from . import cnn_train, mla_train, ops
 from .params import *  # noqa: F401,F403
+from .torchvggish.vggish import cache_stamp, weight_caches
 
 
 class H5Loader(Dataset):
@@ -84,6 +85,7 @@ class TrainStep:
         # MLA_TRAIN_GRAPH=0 or graph=False keeps every step eager)
         self.use_graph = (os.environ.get("MLA_TRAIN_GRAPH", "1") == "1") if graph is None else bool(graph)
         self._graph, self._eager_shape, self._dev_t = None, None, -1
+        self.captures = 0                                   # graphs recorded so far (a re-capture after a disturbance counts)
         held = None if params is None else {id(p) for p in params}
         named = [(n, p) for n, p in clf.named_parameters()
                  if p.requires_grad and ".fcf." not in n and (held is None or id(p) in held)]
@@ -201,7 +203,8 @@ class TrainStep:
         """inputs (B, T, 1, 96, 64) (or whatever ``clf.input`` reshapes), labels (B,) int64.
         Returns (loss, hits) as device tensors (no host sync; train.py:141-142 syncs via .item()): hits = int32
         [n_correct, n_labels_out_of_range] over the global batch (``ops.raise_on_bad_labels(hits)`` -> n_correct or IndexError).
-        With the HIP graph in use the two tensors (and ``last_out``) are the graph's own buffers: valid until the next step."""
+        With the HIP graph in use the two tensors (and ``last_out``) are the graph's own buffers: valid until the next step.
+        ``inputs`` and ``labels`` are only read, and not kept: the graph works on private copies (one device copy per step)."""
         clf = self.clf
         for n, p, ptr in self._seated:
             if p.data_ptr() != ptr:
@@ -209,7 +212,7 @@ class TrainStep:
                                    "cast after the step was built): build a new TrainStep" % n)
         clf.train()
         ops.check_labels(labels, clf.mla.classes)
-        if self._graph_usable(inputs):
+        if self._graph_usable(inputs) and not self._graph_disturbed():
             return self._graphed(inputs, labels)
         with torch.no_grad():
             loss, hits, out = self._body(inputs, labels.to(inputs.device).long().contiguous(), captured=False)
@@ -232,6 +235,30 @@ class TrainStep:
         # first step of a shape runs eagerly: it sizes the library's workspaces and warms the weight caches outside any capture
         return self._eager_shape == tuple(inputs.shape)
 
+    def _stamp(self):
+        """What the recorded kernels read by address without the graph or this step owning it, as host values (no device sync):
+        the model precision and the (data_ptr, _version) of every tensor outside the flat buffer that a cached weight copy derives
+        from (the frozen VGGish's repacked / bf16 weights, the frozen ResNet trunk's repacks)."""
+        lo = self.flat_p.data_ptr()
+        hi = lo + 4 * self.flat_p.numel()
+        cnn = self.clf.cnn
+        return cnn.precision, cache_stamp(weight_caches(cnn), lambda p: lo <= p.data_ptr() < hi)
+
+    def _graph_disturbed(self):
+        """True (and the graph is dropped) when something the graph addresses was changed or replaced since the capture: frozen
+        weights written in place (load_state_dict) or re-seated, set_precision, a library scratch buffer that grew. The step then
+        runs eagerly, which derives fresh copies and sizes the scratch, and the next one is captured again -- the path a change
+        of batch shape takes. Until it is dropped the graph holds the tensors it addresses (g["held"]), so none of them has gone
+        back to the allocator by then."""
+        g = self._graph
+        if g is None:
+            return False
+        live = ops.scratch(self.flat_p.device)
+        if self._stamp() == g["stamp"] and all(k in live and live[k].data_ptr() == ptr for k, ptr in g["scratch"].items()):
+            return False
+        self._graph = None
+        return True
+
     def _graphed(self, inputs, labels):
         dev = inputs.device
         drops = self._dropouts()
@@ -242,16 +269,22 @@ class TrainStep:
             self.step_dev.fill_(self.t)
             self._dev_t = self.t
         if g is None:
-            g = {"shape": tuple(inputs.shape), "x": inputs, "y": labels.to(dev).long().contiguous().clone(),
+            # the static input and labels are the graph's own: the caller's tensors are never written and never kept
+            g = {"shape": tuple(inputs.shape), "x": inputs.clone(), "y": labels.to(dev).long().contiguous().clone(),
                  "bases": {id(d): d.calls - self.t for d in drops}}
             torch.cuda.synchronize()
             g["graph"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g["graph"], capture_error_mode="relaxed"), torch.no_grad():
                 g["loss"], g["hits"], g["out"] = self._body(g["x"], g["y"], captured=True, bases=g["bases"])
+            # what the recorded kernels address without having allocated it during the capture: compared before every replay
+            # (_graph_disturbed) and kept alive for as long as this graph is
+            scratch = ops.scratch(dev)
+            g["stamp"], g["scratch"] = self._stamp(), {k: t.data_ptr() for k, t in scratch.items()}
+            g["held"] = [t for c in weight_caches(self.clf.cnn) for t in c.tensors()] + list(scratch.values())
             self._graph = g
+            self.captures += 1
         else:
-            if inputs.data_ptr() != g["x"].data_ptr():
-                g["x"].copy_(inputs, non_blocking=True)
+            g["x"].copy_(inputs, non_blocking=True)
             g["y"].copy_(labels.to(dev, non_blocking=True).long(), non_blocking=True)
         ops.adam_prepare(self.adam_scal, self.lr, self.betas[0], self.betas[1], self.t + 1)
         g["graph"].replay()

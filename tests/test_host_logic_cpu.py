@@ -91,3 +91,39 @@ def test_every_abi_entry_point_cites_what_it_replaces():
         return any("_".join(parts[:k]) in integ for k in range(len(parts), 1, -1) if k > 2 or k == len(parts))
     missing = [s for s in syms if not listed(s) and not s.startswith(("mla_abi", "mla_last", "mla_logmel_table", "mla_logmel_reference"))]
     assert not missing, missing
+
+
+def test_graph_stamp_sees_in_place_writes_reseating_and_replaced_scratch():
+    """What a HIP graph holder compares before a replay (no device needed): the stamp of a weight cache moves when a tensor its
+    copies derive from is written in place or re-seated, not otherwise; tensors the holder accounts for itself can be left out;
+    ops.scratch lists one device's live entries and shows a replaced one under its old key."""
+    V = importlib.import_module(PKG + ".torchvggish.vggish")
+    ops = importlib.import_module(PKG + ".ops")
+    a, b = torch.nn.Parameter(torch.zeros(4)), torch.nn.Parameter(torch.ones(3))
+    made = []
+    cache = V._Cache()
+    assert V.cache_stamp([cache]) == () and cache.tensors() == []
+    make = lambda: made.append(1) or [a.detach().clone(), b.detach().clone()]          # noqa: E731
+    first = cache.get([a, b], "bf16", make)
+    assert cache.get([a, b], "bf16", make) is first and len(made) == 1
+    s0 = V.cache_stamp([cache])
+    assert len(s0) == 2 and V.cache_stamp([cache]) == s0 and [t.data_ptr() for t in cache.tensors()] == [t.data_ptr() for t in first]
+    with torch.no_grad():
+        b.copy_(torch.full((3,), 2.0))                              # load_state_dict writes like this
+    s1 = V.cache_stamp([cache])
+    assert s1 != s0 and s1[0] == s0[0]
+    assert V.cache_stamp([cache], skip=lambda p: p is b) == s0[:1]
+    assert cache.get([a, b], "bf16", make) is not first and len(made) == 2 and V.cache_stamp([cache]) == s1
+    a.data = torch.zeros(4)                                         # re-seated: same version, another address
+    assert V.cache_stamp([cache])[0] != s1[0]
+    cache.val = {1: first[0], 2: first[1]}                          # the ResNet trunk keeps a dict per conv
+    assert [t.data_ptr() for t in cache.tensors()] == [t.data_ptr() for t in first]
+    cpu = torch.device("cpu")
+    keep = dict(ops._ws)
+    try:
+        ops._ws["ksplit/cpu"] = old = torch.empty(8)
+        assert ops.scratch(cpu)[(0, "ksplit/cpu")] is old and ops.scratch(torch.device("meta")) == {}
+        ops._ws["ksplit/cpu"] = torch.empty(16)
+        assert ops.scratch(cpu)[(0, "ksplit/cpu")].data_ptr() != old.data_ptr()
+    finally:
+        ops._ws.clear(); ops._ws.update(keep)
