@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ a, T
         const Window win = window_of<V>(i, H, W, C);
         float v[4][V], m[V];
         _Pragma("unroll") for (int k = 0; k < 4; ++k) load_chunk(a + win.base + win.off[k], v[k]);
-        _Pragma("unroll") for (int e = 0; e < V; ++e) m[e] = fmaxf(fmaxf(v[0][e], v[1][e]), fmaxf(v[2][e], v[3][e]));
+        _Pragma("unroll") for (int e = 0; e < V; ++e) m[e] = mla::nan_max(mla::nan_max(mla::nan_max(v[0][e], v[1][e]), v[2][e]), v[3][e]);   // keeps NaN, as nn.MaxPool2d
         store_chunk(out + i * V, m);                             // bf16: the max of bf16 values is a bf16 value, the repack is exact
     }
 }

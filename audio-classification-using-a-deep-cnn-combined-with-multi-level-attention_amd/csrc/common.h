@@ -9,6 +9,7 @@
 #include <cstdio>
 
 #include "../../include/mla_hip.h"
+#include "nanprop.h"
 
 namespace mla {
 

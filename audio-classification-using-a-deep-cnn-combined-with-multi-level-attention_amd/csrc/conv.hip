@@ -518,7 +518,7 @@ __global__ __launch_bounds__(kThreads, C::MIN_WAVES) void conv3x3_kernel(const t
         MLA_STAMP2(1);
 #endif
         // epilogue: ReLU (+ lane-local 2x2 max-pool; max commutes with the monotone ReLU; the bias is already in the
-        // accumulators); one vector store per pixel.
+        // accumulators); one vector store per pixel. Max and ReLU keep NaN (nanprop.h), as nn.MaxPool2d and nn.ReLU do.
         {
             if (C::POOL) {
                 // training forward (mla_conv3x3_train): the pre-pool post-ReLU activation is kept as well -- the pool / ReLU backward
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(kThreads, C::MIN_WAVES) void conv3x3_kernel(const t
                         const int y = y_tile + l_y0 + i;
                         _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                             float v[C::NS];
-                            _Pragma("unroll") for (int j = 0; j < C::NS; ++j) v[j] = fmaxf(acc[i][j][e], 0.f);
+                            _Pragma("unroll") for (int j = 0; j < C::NS; ++j) v[j] = mla::nan_relu(acc[i][j][e]);
                             const int rr = 4 * q + e;
                             const int img = img0 + (C::SEGW == 8 ? wimg + (rr >> 3) : 0);
                             const int x = C::SEGW == 8 ? (rr & 7) : ((wxh * 16) + rr);
@@ -540,8 +540,8 @@ __global__ __launch_bounds__(kThreads, C::MIN_WAVES) void conv3x3_kernel(const t
                     float p0[C::NS], p1[C::NS];
                     _Pragma("unroll") for (int j = 0; j < C::NS; ++j) {
                         const f32x4 u = acc[2 * ip][j], d = acc[2 * ip + 1][j];
-                        p0[j] = fmaxf(fmaxf(fmaxf(u.x, u.y), fmaxf(d.x, d.y)), 0.f);
-                        p1[j] = fmaxf(fmaxf(fmaxf(u.z, u.w), fmaxf(d.z, d.w)), 0.f);
+                        p0[j] = mla::nan_pool_relu(u.x, u.y, d.x, d.y);
+                        p1[j] = mla::nan_pool_relu(u.z, u.w, d.z, d.w);
                     }
                     const int yo = (y_tile + l_y0 + 2 * ip) >> 1;
                     const int img = img0 + (C::SEGW == 8 ? wimg + (q >> 1) : 0);
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(kThreads, C::MIN_WAVES) void conv3x3_kernel(const t
                     const int y = y_tile + l_y0 + i;
                     _Pragma("unroll") for (int e = 0; e < 4; ++e) {
                         float v[C::NS];
-                        _Pragma("unroll") for (int j = 0; j < C::NS; ++j) v[j] = C::ACT ? fmaxf(acc[i][j][e], 0.f) : acc[i][j][e];
+                        _Pragma("unroll") for (int j = 0; j < C::NS; ++j) v[j] = C::ACT ? mla::nan_relu(acc[i][j][e]) : acc[i][j][e];
                         const int rr = 4 * q + e;
                         const int img = img0 + (C::SEGW == 8 ? wimg + (rr >> 3) : 0);
                         const int x = C::SEGW == 8 ? (rr & 7) : ((wxh * 16) + rr);
@@ -727,8 +727,8 @@ __global__ __launch_bounds__(256, 4) void conv1_kernel(const TIN* __restrict__ x
             float p0[4], p1[4];
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {
                 const f32x4 u = acc[0][j], d = acc[1][j];
-                p0[j] = fmaxf(fmaxf(fmaxf(u.x, u.y), fmaxf(d.x, d.y)) + bj[j], 0.f);
-                p1[j] = fmaxf(fmaxf(fmaxf(u.z, u.w), fmaxf(d.z, d.w)) + bj[j], 0.f);
+                p0[j] = mla::nan_relu(mla::nan_max(mla::nan_max(mla::nan_max(u.x, u.y), d.x), d.y) + bj[j]);
+                p1[j] = mla::nan_relu(mla::nan_max(mla::nan_max(mla::nan_max(u.z, u.w), d.z), d.w) + bj[j]);
             }
             const int xo = 8 * seg + 2 * q;
             if constexpr (SPLIT) {        // f32 arithmetic, [hi(64) | lo(64)] bf16 per pooled pixel = the f32 row's 256 bytes

@@ -8,9 +8,14 @@
 #define MLA_CONV1_CORE_H
 
 #include "mma_core.h"
+#include "nanprop.h"
 
 #ifndef MLA_CONV_NT_STORE
 #define MLA_CONV_NT_STORE 1              // streaming outputs (conv epilogues, conv1) as non-temporal stores: conv1 0.43 -> 0.38 ms, conv3 -4 % in the pipeline
+#endif
+
+#ifndef MLA_CONV1_MASK_INF
+#define MLA_CONV1_MASK_INF 1             // 0: without the masked form for patches that hold an Inf or NaN (A/B: what the check costs)
 #endif
 
 namespace conv1 {
@@ -61,15 +66,36 @@ __device__ __forceinline__ void pooled_row(const uint16_t* rows, const bf16x8 (&
     const int px = lane & 31, h = lane >> 5;
     const uint32_t* r0 = reinterpret_cast<const uint32_t*>(rows + (2 * h) * kPitch) + px;       // 2 px bf16 = px dwords
     const uint32_t* r1 = reinterpret_cast<const uint32_t*>(rows + (2 * h + 1) * kPitch) + px;
-    const bf16x8 bfrag = __builtin_bit_cast(bf16x8, u32x4{r0[0], r0[1], r1[0], r1[1]});
+    const u32x4 braw = u32x4{r0[0], r0[1], r1[0], r1[1]};
+    const bf16x8 bfrag = __builtin_bit_cast(bf16x8, braw);
+    // The four positions share ONE patch operand, and each position's filter copy is zero where it does not use a patch element:
+    // 0 * inf (or 0 * NaN) = NaN would reach a position that never reads that element. A wave whose patches hold an Inf or NaN
+    // (exponent all ones: the add carries into the half's bit 15) takes the masked form below -- one operand per position with the
+    // unused elements zeroed, so that inf * w, relu and the pool see what nn.Conv2d's would. Wave-uniform; finite data never enters.
+    const uint32_t carry = (((braw.x & 0x7fff7fffu) + 0x00800080u) | ((braw.y & 0x7fff7fffu) + 0x00800080u) |
+                            ((braw.z & 0x7fff7fffu) + 0x00800080u) | ((braw.w & 0x7fff7fffu) + 0x00800080u)) & 0x80008000u;
+    const bool special = MLA_CONV1_MASK_INF && __builtin_amdgcn_ballot_w64(carry != 0u) != 0ull;
     _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) {
-        f32x16 m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][mt], bfrag, binit[mt], 0, 0, 0);
-        _Pragma("unroll") for (int pos = 1; pos < 4; ++pos) {
-            const f32x16 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[pos][mt], bfrag, binit[mt], 0, 0, 0);
-            _Pragma("unroll") for (int reg = 0; reg < 16; ++reg) m[reg] = fmaxf(m[reg], a[reg]);
+        f32x16 m;
+        if (__builtin_expect(special, 0)) {
+            _Pragma("unroll") for (int pos = 0; pos < 4; ++pos) {
+                const int dy = pos >> 1, dx = pos & 1;                          // the position reads patch rows dy .. dy + 2, columns dx .. dx + 2
+                const uint32_t c01 = dx ? 0xffff0000u : 0xffffffffu, c23 = dx ? 0xffffffffu : 0x0000ffffu;      // (col 0 | col 1 << 16), (col 2 | col 3 << 16)
+                const uint32_t k0 = (2 * h >= dy && 2 * h <= dy + 2) ? 0xffffffffu : 0u, k1 = (2 * h + 1 >= dy && 2 * h + 1 <= dy + 2) ? 0xffffffffu : 0u;
+                const bf16x8 bm = __builtin_bit_cast(bf16x8, u32x4{braw.x & c01 & k0, braw.y & c23 & k0, braw.z & c01 & k1, braw.w & c23 & k1});
+                const f32x16 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[pos][mt], bm, binit[mt], 0, 0, 0);
+                if (pos == 0) m = a;
+                else _Pragma("unroll") for (int reg = 0; reg < 16; ++reg) m[reg] = mla::nan_max(m[reg], a[reg]);
+            }
+        } else {
+            m = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][mt], bfrag, binit[mt], 0, 0, 0);
+            _Pragma("unroll") for (int pos = 1; pos < 4; ++pos) {
+                const f32x16 a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[pos][mt], bfrag, binit[mt], 0, 0, 0);
+                _Pragma("unroll") for (int reg = 0; reg < 16; ++reg) m[reg] = mla::nan_max(m[reg], a[reg]);
+            }
         }
         uint32_t pk[8];
-        _Pragma("unroll") for (int e = 0; e < 8; ++e) pk[e] = pack_bf16x2(fmaxf(m[2 * e], 0.f), fmaxf(m[2 * e + 1], 0.f));
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) pk[e] = pack_bf16x2(mla::nan_relu(m[2 * e]), mla::nan_relu(m[2 * e + 1]));
         char* dst = stage + px * kStageRow + (mt * 32 + 16 * h) * 2;              // 16 consecutive channels of pixel px
         *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0], pk[1], pk[2], pk[3]};
         *reinterpret_cast<u32x4*>(dst + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};

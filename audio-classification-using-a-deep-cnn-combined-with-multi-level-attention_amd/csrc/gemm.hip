@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const T* __restrict__
                 const int m = m0 + (wm * kMS + i) * 16 + 4 * q + e;
                 if (m < M) {
                     float y = v[e] + b;
-                    if (RELU) y = fmaxf(y, 0.f);
+                    if (RELU) y = mla::nan_relu(y);
                     if (sizeof(TO) == 2 && osplit) {              // [hi(N) | lo(N)] row of 2 N bf16
                         const float hi = bf2f(f2bf(y));
                         store_elem<TO>(out + size_t(m) * ldo + n, hi);
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_ring_kernel(const T* __restr
                 const int m = m0 + (wm * kMS + i) * 16 + 4 * q + e;
                 if (m < M) {
                     float y = v[e] + b;
-                    if (RELU) y = fmaxf(y, 0.f);
+                    if (RELU) y = mla::nan_relu(y);
                     if (sizeof(TO) == 2 && osplit) {              // [hi(N) | lo(N)] row of 2 N bf16
                         const float hi = bf2f(f2bf(y));
                         store_elem<TO>(out + size_t(m) * ldo + n, hi);
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         const int n = int(i - m * N);
         float v = bias ? bias[n] : 0.f;
         for (int k = 0; k < splits; ++k) v += partial[size_t(k) * total + i];
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = mla::nan_relu(v);
         store_elem<TO>(out + m * ldo + n, v);
     }
 }

@@ -10,7 +10,7 @@
 // consecutive in D, so every band's store is one 64-byte run. The run's maximum goes to the clip's workspace slot.
 // A clip's result depends on nothing but its own samples: runs are cut per clip, never across the batch.
 //
-// melspec_images_kernel: reduces the clip's partial maxima (max is exact in any order), then a pure select + gather:
+// melspec_images_kernel: reduces the clip's partial maxima (max is exact in any order and keeps NaN: a NaN sample makes its whole clip NaN, as np.maximum and .max() do), then a pure select + gather:
 // out[c][t][0][band][x] = max(D[c][band][t * stride + x], Dmax_c - top_db), written as float32 or as bfloat16 (one rounding).
 //
 // melspec_nopad_db_kernel: the same spectrogram of UNPADDED frames (center=False; the VGGish branch's librosa path,
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kThreads) void melspec_db_kernel(const float* __res
         }
         power(t, tw, zr, zi, pw);
         __syncthreads();                                                   // zr / zi are free again after this barrier
-        best = fmaxf(best, mel_db(t, pw, meta, weights, n_mels, amin, f, tile));
+        best = mla::nan_max(best, mel_db(t, pw, meta, weights, n_mels, amin, f, tile));
         // pw is next written after the following frame's five FFT barriers
     }
     __syncthreads();
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void melspec_db_kernel(const float* __res
     zr[t] = best;                                                          // block maximum: zr is dead here
     __syncthreads();
     for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) zr[t] = fmaxf(zr[t], zr[t + s]);
+        if (t < s) zr[t] = mla::nan_max(zr[t], zr[t + s]);
         __syncthreads();
     }
     if (t == 0) partial[blockIdx.x] = zr[0];
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void melspec_nopad_db_kernel(const float*
             }
             power_in_place(lane, tw, z);
             wave_sync();
-            best = fmaxf(best, wave_mel_db(lane, z, meta, wts, n_mels, amin, f, tile));
+            best = mla::nan_max(best, wave_mel_db(lane, z, meta, wts, n_mels, amin, f, tile));
             wave_sync();                                     // the next frame's first stage overwrites the powers
         }
     }
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void melspec_nopad_db_kernel(const float*
     red[t] = best;
     __syncthreads();
     for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = fmaxf(red[t], red[t + s]);
+        if (t < s) red[t] = mla::nan_max(red[t], red[t + s]);
         __syncthreads();
     }
     if (t == 0) partial[blockIdx.x] = red[0];
@@ -157,11 +157,11 @@ __global__ __launch_bounds__(256) void melspec_images_kernel(const float* __rest
     const int64_t clip = blockIdx.x / blocks_per_clip;
     const int part = int(blockIdx.x - clip * blocks_per_clip);
     float m = -INFINITY;
-    for (int i = t; i < runs; i += 256) m = fmaxf(m, partial[clip * runs + i]);
+    for (int i = t; i < runs; i += 256) m = mla::nan_max(m, partial[clip * runs + i]);
     red[t] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] = fmaxf(red[t], red[t + s]);
+        if (t < s) red[t] = mla::nan_max(red[t], red[t + s]);
         __syncthreads();
     }
     const float lo = red[0] - top_db;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void melspec_images_kernel(const float* __rest
         const int x = int(i % image_w);
         const int64_t r = i / image_w;
         const int b = int(r % n_mels), img = int(r / n_mels);
-        store_db(dst + i, fmaxf(src[int64_t(b) * frames + int64_t(img) * stride + x], lo));
+        store_db(dst + i, mla::nan_max(src[int64_t(b) * frames + int64_t(img) * stride + x], lo));
     }
 }
 

@@ -15,13 +15,15 @@
 //   X[k] = (Z[k] + conj Z[1024-k]) / 2 - i W_2048^k (Z[k] - conj Z[1024-k]) / 2,  k <= 1024;  P[k] = |X[k]|^2
 //     power       thread t: k = t, t + 256, ... (thread 0 also k = 1024)
 //   S[b] = sum_k M[b][k] P[k] over the band's non-zero bins only, in ascending k, one fmaf chain per band
-//   D[b] = 10 log10(max(amin, S[b]))
+//   D[b] = 10 log10(max(amin, S[b]))        (max keeps NaN, as np.maximum does: nanprop.h)
 //     mel_db      thread t: bands t, t + 256, ...; writes tile[b][frame in run], returns its maximum
 #ifndef MLA_MELSPEC_CORE_H
 #define MLA_MELSPEC_CORE_H
 
 #include <cmath>
 #include <cstdint>
+
+#include "nanprop.h"
 
 #if defined(__HIPCC__)
 #define MLA_MS_HD __host__ __device__ __forceinline__
@@ -126,9 +128,9 @@ MLA_MS_HD float mel_db(int t, const float* pw, const int* meta, const float* wei
         const float* w = weights + meta[3 * b + 2];
         float acc = 0.f;
         for (int i = 0; i < bins; ++i) acc = fmaf(w[i], pw[first + i], acc);
-        const float d = 10.0f * log10f(fmaxf(amin, acc));
+        const float d = 10.0f * log10f(mla::nan_max(amin, acc));
         tile[b * kRunFrames + f] = d;
-        best = fmaxf(best, d);
+        best = mla::nan_max(best, d);
     }
     return best;
 }

@@ -100,9 +100,9 @@ MLA_MS_HD float wave_mel_db(int lane, const float* pw, const int* meta, const fl
             acc = fmaf(w0, p0, acc); acc = fmaf(w1, p1, acc); acc = fmaf(w2, p2, acc); acc = fmaf(w3, p3, acc);
         }
         for (; i < bins; ++i) acc = fmaf(w[i], p[i], acc);
-        const float d = 10.0f * log10f(fmaxf(amin, acc));
+        const float d = 10.0f * log10f(mla::nan_max(amin, acc));
         tile[b * kRunFrames + f] = d;
-        best = fmaxf(best, d);
+        best = mla::nan_max(best, d);
     }
     return best;
 }

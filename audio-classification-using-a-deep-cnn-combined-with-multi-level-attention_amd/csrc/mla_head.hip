@@ -292,9 +292,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
         const int ch = MODE == 0 ? int(r % period) : c;
         const float inv = 1.0f / sqrtf(var[ch] + eps);
         float v = (x[r * ldx + c] - mean[ch]) * inv * gamma[ch] + beta[ch];
-        if (act == 1) v = fmaxf(v, 0.f);
+        if (act == 1) v = mla::nan_relu(v);
         else if (act == 2) v = sigmoidf(v);
-        if (keep) v = keep[i] ? v * drop_scale : 0.f;
+        if (keep) v *= keep[i] ? drop_scale : 0.f;                    // a product, as F.dropout: NaN * 0 = NaN
         y[r * ldy + c] = v;
     }
 }

@@ -43,9 +43,15 @@ __global__ __launch_bounds__(256) void rn_stem_kernel(const float* __restrict__ 
         b[k] = -(w0 * kNormMean[0] * kNormInv[0] + w1 * kNormMean[1] * kNormInv[1] + w2 * kNormMean[2] * kNormInv[2]);
     }
     __syncthreads();
+    // Taps outside the image are skipped, where nn.Conv2d multiplies its zero padding by the weight: a NaN or Inf weight makes the
+    // whole channel NaN there. poison = +0 for finite weights, NaN otherwise, and starts every sum.
+    float wsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 49; ++k) wsum += a[k] + b[k];
+    const float poison = wsum - wsum;
     const float sc = scale ? scale[o] : 1.f, sh = scale ? shift[o] : 0.f;
     for (int ox = pg; ox < kStemOut; ox += 4) {
-        float acc = 0.f;
+        float acc = poison;
 #pragma unroll
         for (int ky = 0; ky < 7; ++ky) {
             const int iy = 2 * oy - 3 + ky;
@@ -57,7 +63,7 @@ __global__ __launch_bounds__(256) void rn_stem_kernel(const float* __restrict__ 
             }
         }
         float v = scale ? acc * sc + sh : acc;
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = mla::nan_relu(v);
         mma::store_elem<T>(out + ((n * kStemOut + oy) * kStemOut + ox) * kStemC + o, v);
     }
 }
@@ -100,7 +106,7 @@ __global__ __launch_bounds__(256) void rn_conv_kernel(const T* __restrict__ in, 
                 const int64_t off = m * Cout + co;
                 if (scale) v = v * sc + sh;
                 if (res) v += mma::load_elem<T>(res + off);
-                if (relu) v = fmaxf(v, 0.f);
+                if (relu) v = mla::nan_relu(v);
                 mma::store_elem<T>(out + off, v);
             };
         });
@@ -209,7 +215,7 @@ __global__ __launch_bounds__(256) void rn_bn_apply_kernel(const T* x, int64_t n8
         for (int k = 0; k < 8; ++k) {
             v[k] = v[k] * scale[c + k] + shift[c + k];
             if (res) v[k] += r[k];
-            if (relu) v[k] = fmaxf(v[k], 0.f);
+            if (relu) v[k] = mla::nan_relu(v[k]);
         }
         store8<T>(out + off, v);
     }
@@ -240,7 +246,7 @@ __global__ __launch_bounds__(256) void rn_maxpool_kernel(const T* __restrict__ i
                 float v[8];
                 load8<T>(in + ((img * H + iy) * W + ix) * C + c, v);
 #pragma unroll
-                for (int k = 0; k < 8; ++k) m[k] = fmaxf(m[k], v[k]);
+                for (int k = 0; k < 8; ++k) m[k] = mla::nan_max(m[k], v[k]);
             }
         }
         store8<T>(out + pix * C + c, m);

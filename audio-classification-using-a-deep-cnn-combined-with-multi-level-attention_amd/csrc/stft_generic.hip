@@ -135,7 +135,7 @@ __global__ __launch_bounds__(128) void postprocess_kernel(const float* __restric
     __syncthreads();
     float acc = 0.f;
     for (int k = 0; k < 128; ++k) acc = fmaf(ev[j * 128 + k], xc[k], acc);
-    acc = fminf(fmaxf(acc, -2.0f), 2.0f);
+    acc = mla::nan_min(mla::nan_max(acc, -2.0f), 2.0f);        // torch.clamp keeps NaN
     out[n * 128 + j] = rintf((acc + 2.0f) * (255.0f / 4.0f));
     (void)rows;
 }
