@@ -32,6 +32,8 @@
 // hipcc pays ~100 v_mov shuffles per frame to form the register pairs.
 #include <hip/hip_bf16.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "conv1_core.h"
 #include "logmel_bags_core.h"
@@ -251,7 +253,7 @@ struct ColsToStage {
 };
 
 // One frame pair of a 16-lane group: window (samples already in `smp`), prefetch of the group's next pair, both FFTs, split,
-// mel, log, and the two finished rows to `sink`. Shared by the dynamic (shipped), the static (cross-check) and the fused kernel.
+// mel, log, and the two finished rows to `sink`. Shared by every kernel of this file.
 template <typename InT, bool VEC, bool WAVE, typename Sink>
 __device__ __forceinline__ void pair_step(const LaneConsts& c, int j, Samples<InT>& smp, const InT* next_frame, float* xa, float* xb,
                                           const float* s_win, const float* melw, const float* pw, const Sink& sink) {
@@ -299,29 +301,71 @@ __device__ __forceinline__ void pair_step(const LaneConsts& c, int j, Samples<In
     group_sync<WAVE>();                 // the buffers are rewritten by the next pair
 }
 
-// Static kernel (cross-check build, MLA_LOGMEL_SYNC=block, and the round-1 schedule): 256 threads, two workgroups per CU, chunks of
-// 32 frames dealt grid-stride; WAVE = false keeps a full workgroup barrier at every hand-off.
-template <typename InT, typename OutT, bool VEC, bool WAVE>
+constexpr int kThreadsDyn = 512;                          // the persistent kernels: one workgroup per CU
+constexpr int kItemFrames = 4 * kPair;                     // frames per wave-iteration
+
+// What every kernel of this file starts from: the LDS carve-up (two exchange buffers per 16-lane group, then the tables; the
+// persistent kernels' work counter follows them, and whatever a kernel adds lies behind that), the lane's constants and its table
+// rows. The constructor only stores the tables; share() ends the prologue of a persistent kernel with its one workgroup barrier.
+template <int THREADS>
+struct Front {
+    static constexpr int kFloats = (THREADS / 16) * kPair * kXchFloats + 16 * kMelRow + 16 * kPwPitch + kWinFloats;
+    LaneConsts c;
+    int t, j, gl, lane, wv, lane_frame;      // thread, lane of its 16-lane group, group of its wave, lane and number of its wave
+    float *xa, *xb;                          // the group's exchange buffers
+    float* wave_xch;                         // the wave's first exchange buffer: the 8 of its groups follow one another
+    const float *melw, *pw, *s_win;          // the lane's mel weights and split twiddles; Hann window + zero tail
+    int* s_next;
+    int lo, hi;
+
+    __device__ __forceinline__ Front(float* smem, const float* __restrict__ tab) {
+        float* s_mel = smem + (THREADS / 16) * kPair * kXchFloats;
+        float* s_pw = s_mel + 16 * kMelRow;
+        float* win = s_pw + 16 * kPwPitch;
+        s_win = win;
+        s_next = reinterpret_cast<int*>(win + kWinFloats);
+        t = threadIdx.x; j = t & 15; gl = (t >> 4) & 3; lane = t & 63; wv = __builtin_amdgcn_readfirstlane(t >> 6);
+        lane_frame = kPair * gl;                                   // this group's frame pair inside an 8-frame item
+        xa = smem + (kPair * (t >> 4)) * kXchFloats;
+        xb = xa + kXchFloats;
+        wave_xch = smem + (kItemFrames * wv) * kXchFloats;
+        load_consts(c, tab, j);
+        for (int i = t; i < 16 * kMelRow; i += THREADS) s_mel[i] = tab[kTabMelW + i];
+        for (int i = t; i < 16 * kPwRow; i += THREADS) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
+        for (int i = t; i < kWinFloats; i += THREADS) win[i] = tab[kTabWindow + i];
+        melw = s_mel + kMelRow * j;
+        pw = s_pw + kPwPitch * j;
+    }
+    // this workgroup's contiguous share [lo, hi) of n units (consecutive frames: the 2.5x frame overlap stays in this XCD's L2), the
+    // counter its waves pull them from, and the only workgroup barrier: tables, counter and what the kernel stored before are visible
+    __device__ __forceinline__ void share(int64_t n) {
+        lo = int(n * int64_t(blockIdx.x) / int64_t(gridDim.x));
+        hi = int(n * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
+        if (t == 0) *s_next = lo;
+        __syncthreads();
+    }
+    __device__ __forceinline__ int pull() const {            // wave-uniform: one lane takes the next unit of the workgroup's share
+        int v = 0;
+        if (lane == 0) v = atomicAdd(s_next, 1);
+        return __builtin_amdgcn_readfirstlane(v);
+    }
+    // pair_step of this group, from `smp` to `sink`
+    template <bool VEC, bool WAVE = true, typename InT, typename Sink>
+    __device__ __forceinline__ void pair(Samples<InT>& smp, const InT* next_frame, const Sink& sink) const {
+        pair_step<InT, VEC, WAVE>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, sink);
+    }
+};
+static_assert(Front<kThreads>::kFloats == kLdsFloats, "static kernel: LDS");
+
+// Static kernel (cross-check build, MLA_LOGMEL_SYNC=block): 256 threads, two workgroups per CU, chunks of 32 frames dealt
+// grid-stride, a full workgroup barrier at every hand-off. The reference the wave-level fences of the kernels below are tested against.
+template <typename InT, typename OutT, bool VEC>
 __global__ __launch_bounds__(kThreads, kWgPerCu) void logmel_kernel(const InT* __restrict__ pcm, ChunkMap map,
                                                               int64_t n_chunks, const float* __restrict__ tab,
                                                               OutT* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_xch = smem;
-    float* s_mel = s_xch + kChunk * kXchFloats;   // per-lane mel weights
-    float* s_pw = s_mel + 16 * kMelRow;           // per-lane split twiddles
-    float* s_win = s_pw + 16 * kPwPitch;          // Hann window + zero tail
-
-    const int t = threadIdx.x, g = t >> 4, j = t & 15;
-    float* xa = s_xch + (kPair * g) * kXchFloats;
-    float* xb = xa + kXchFloats;
-
-    LaneConsts c;
-    load_consts(c, tab, j);
-    for (int i = t; i < 16 * kMelRow; i += kThreads) s_mel[i] = tab[kTabMelW + i];
-    for (int i = t; i < 16 * kPwRow; i += kThreads) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
-    for (int i = t; i < kWinFloats; i += kThreads) s_win[i] = tab[kTabWindow + i];
-    const float* melw = s_mel + kMelRow * j;
-    const float* pw = s_pw + kPwPitch * j;
+    const Front<kThreads> f(smem, tab);
+    const int g = f.t >> 4, j = f.j;
     __syncthreads();                        // tables visible
 
     Samples<InT> smp;
@@ -339,7 +383,7 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void logmel_kernel(const InT* _
             map.locate(next, ns, nr);
             next_frame = pcm + ns + (kPair * g) * kHop;
         }
-        pair_step<InT, VEC, WAVE>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, RowsToGlobal<OutT>{out + (row0 + kPair * g) * kBands});
+        f.template pair<VEC, false>(smp, next_frame, RowsToGlobal<OutT>{out + (row0 + kPair * g) * kBands});
     }
 }
 
@@ -349,9 +393,8 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void logmel_kernel(const InT* _
 // early and leaves its partner alone on the SIMD for the last third of the kernel (a single wave issues at half the pair's rate):
 // wall-clock stamps of the static kernel showed the first-dispatched workgroup of every CU done at 225-233 us and the second at
 // 335-355 us of a 358 us launch (profiles/r02_frontend_counters.txt). No workgroup barrier after the table load, no global state.
-constexpr int kThreadsDyn = 512;
-constexpr int kItemFrames = 4 * kPair;                     // frames per wave-iteration
-constexpr int kLdsFloatsDyn = (kThreadsDyn / 16) * kPair * kXchFloats + 16 * kMelRow + 16 * kPwPitch + kWinFloats + 4;
+using FrontDyn = Front<kThreadsDyn>;
+constexpr int kLdsFloatsDyn = FrontDyn::kFloats + 4;       // + the work counter
 constexpr int kLdsBytesDyn = kLdsFloatsDyn * 4;
 static_assert(kLdsBytesDyn <= 160 * 1024 && kChunk % kItemFrames == 0, "dynamic kernel: LDS / item size");
 
@@ -359,71 +402,45 @@ template <typename InT, typename OutT, bool VEC>
 __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_dyn_kernel(const InT* __restrict__ pcm, ChunkMap map, int64_t n_items,
                                                                     const float* __restrict__ tab, OutT* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_xch = smem;
-    float* s_mel = s_xch + (kThreadsDyn / 16) * kPair * kXchFloats;
-    float* s_pw = s_mel + 16 * kMelRow;
-    float* s_win = s_pw + 16 * kPwPitch;
-    int* s_next = reinterpret_cast<int*>(s_win + kWinFloats);
-
-    const int t = threadIdx.x, g = t >> 4, gl = g & 3, j = t & 15, lane = t & 63;
 #if MLA_LOGMEL_STAMPS
     const unsigned long long stamp_entry = __builtin_amdgcn_s_memrealtime();
 #endif
-    float* xa = s_xch + (kPair * g) * kXchFloats;
-    float* xb = xa + kXchFloats;
-
-    LaneConsts c;
-    load_consts(c, tab, j);
-    for (int i = t; i < 16 * kMelRow; i += kThreadsDyn) s_mel[i] = tab[kTabMelW + i];
-    for (int i = t; i < 16 * kPwRow; i += kThreadsDyn) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
-    for (int i = t; i < kWinFloats; i += kThreadsDyn) s_win[i] = tab[kTabWindow + i];
-    // this workgroup's contiguous share of the items (consecutive frames: the 2.5x frame overlap stays in this XCD's L2)
-    const int lo = int(n_items * int64_t(blockIdx.x) / int64_t(gridDim.x)), hi = int(n_items * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
-    if (t == 0) *s_next = lo;
-    const float* melw = s_mel + kMelRow * j;
-    const float* pw = s_pw + kPwPitch * j;
-    __syncthreads();                        // the only workgroup barrier: tables and the counter visible
-
-    auto pull = [&]() {                      // wave-uniform: one lane takes the next item of the workgroup's share
-        int v = 0;
-        if (lane == 0) v = atomicAdd(s_next, 1);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
+    FrontDyn f(smem, tab);
+    f.share(n_items);
     constexpr int kQ = kChunk / kItemFrames;                  // items per 32-frame chunk of the chunk map
     auto locate_item = [&](int item, int64_t& sample, int64_t& row) {     // wave-uniform: first sample / output row of the item
         int64_t sample0, row0;
         map.locate(item / kQ, sample0, row0);
-        const int f = (item % kQ) * kItemFrames;
-        sample = sample0 + int64_t(f) * kHop;
-        row = row0 + f;
+        const int fr = (item % kQ) * kItemFrames;
+        sample = sample0 + int64_t(fr) * kHop;
+        row = row0 + fr;
     };
-    const int lane_frame = kPair * gl;                        // this group's frame pair inside the item
     Samples<InT> smp;
-    int cur = pull();
+    int cur = f.pull();
     int64_t sample = 0, row = 0;
-    if (cur < hi) {
+    if (cur < f.hi) {
         locate_item(cur, sample, row);
-        smp.template fetch<VEC>(pcm + sample + lane_frame * kHop, j);
+        smp.template fetch<VEC>(pcm + sample + f.lane_frame * kHop, f.j);
     }
 #if MLA_LOGMEL_STAMPS
     const unsigned long long stamp0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    while (cur < hi) {
-        const int nxt = pull();
+    while (cur < f.hi) {
+        const int nxt = f.pull();
         int64_t nsample = 0, nrow = 0;
         const InT* next_frame = nullptr;
-        if (nxt < hi) {
+        if (nxt < f.hi) {
             locate_item(nxt, nsample, nrow);
-            next_frame = pcm + nsample + lane_frame * kHop;
+            next_frame = pcm + nsample + f.lane_frame * kHop;
         }
-        pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, RowsToGlobal<OutT>{out + (row + lane_frame) * kBands});
+        f.template pair<VEC>(smp, next_frame, RowsToGlobal<OutT>{out + (row + f.lane_frame) * kBands});
         cur = nxt;
         row = nrow;
     }
 #if MLA_LOGMEL_STAMPS
-    if (lane == 0 && blockIdx.x < 256) {
-        if (t == 0) { g_logmel_stamps[blockIdx.x][0] = stamp_entry; g_logmel_stamps[blockIdx.x][9] = stamp0; }
-        g_logmel_stamps[blockIdx.x][1 + (t >> 6)] = __builtin_amdgcn_s_memrealtime();
+    if (f.lane == 0 && blockIdx.x < 256) {
+        if (f.t == 0) { g_logmel_stamps[blockIdx.x][0] = stamp_entry; g_logmel_stamps[blockIdx.x][9] = stamp0; }
+        g_logmel_stamps[blockIdx.x][1 + (f.t >> 6)] = __builtin_amdgcn_s_memrealtime();
     }
 #endif
 }
@@ -447,82 +464,74 @@ __device__ __forceinline__ void store_cols(OutT* dst, f32x4 lo, f32x4 hi) {
     }
 }
 
+// The loop of the kernels that store columns (bags, timeline): a wave pulls items, runs pair_step on those that have a spectrum,
+// reads the stage back as lane = band, and stores the 8 columns -- zeros for an item without a spectrum -- wherever `map` puts them.
+// A Map has a Cursor (wave-uniform: where an item lies, as far as its stores need it) and
+//   first(item)                          the cursor to begin from, at or before the wave's first item;
+//   frame(pcm, item, lane_frame, k)      moves k forward to `item`; the first sample of this group's pair, or null for no spectrum;
+//   store(out, k, lane, v_lo, v_hi)      the lane's band of the item's 8 columns to every place that holds them.
+template <typename InT, typename OutT, bool VEC, typename Map>
+__device__ __forceinline__ void column_items(const FrontDyn& f, const InT* __restrict__ pcm, const Map map, OutT* __restrict__ out) {
+    float* stage = f.wave_xch;                                 // 8 columns x 64 bands
+    Samples<InT> smp;
+    int cur = f.pull();
+    if (cur >= f.hi) return;
+    typename Map::Cursor k = map.first(cur);
+    const InT* frame = map.frame(pcm, cur, f.lane_frame, k);
+    bool fetched = false;                                      // smp holds `frame`'s samples (prefetched by the item before)
+    while (cur < f.hi) {
+        const int nxt = f.pull();
+        typename Map::Cursor kn = k;
+        const InT* next_frame = nxt < f.hi ? map.frame(pcm, nxt, f.lane_frame, kn) : nullptr;
+        f32x4 v_lo = {0.f, 0.f, 0.f, 0.f}, v_hi = {0.f, 0.f, 0.f, 0.f};
+        if (frame) {
+            // after a zero item, or at the start, nothing has been prefetched for this one
+            if (!fetched) smp.template fetch<VEC>(frame, f.j);
+            f.template pair<VEC>(smp, next_frame, ColsToStage{stage + f.lane_frame * kBands});
+            _Pragma("unroll") for (int x = 0; x < 4; ++x) {
+                v_lo[x] = stage[x * kBands + f.lane];
+                v_hi[x] = stage[(4 + x) * kBands + f.lane];
+            }
+            group_sync<true>();             // the stage is rewritten by the next FFT
+        }
+        fetched = frame && next_frame;
+        map.store(out, k, f.lane, v_lo, v_hi);
+        cur = nxt;
+        frame = next_frame;
+        k = kn;
+    }
+}
+
+struct BagsMap {
+    const int32_t* __restrict__ counts;
+    int n_frames, stride;
+    int64_t row_stride;
+    struct Cursor { int clip, col; };                          // the item's clip and its first column
+    __device__ __forceinline__ Cursor first(int) const { return Cursor{0, 0}; }
+    template <typename InT>
+    __device__ __forceinline__ const InT* frame(const InT* pcm, int item, int lane_frame, Cursor& k) const {
+        int slot, fr;
+        logmel_bags::item_locate(item, &k.clip, &slot, &fr);
+        k.col = logmel_bags::item_column(slot, fr);
+        if (slot >= counts[k.clip]) return nullptr;            // the clip lacks the item's slot
+        return pcm + int64_t(k.clip) * row_stride + logmel_bags::frame_sample(slot, fr + lane_frame);
+    }
+    template <typename OutT>
+    __device__ __forceinline__ void store(OutT* out, const Cursor& k, int lane, f32x4 v_lo, f32x4 v_hi) const {
+        int t_lo, t_hi;
+        logmel_bags::column_windows(k.col, n_frames, stride, &t_lo, &t_hi);
+        for (int w = t_lo; w <= t_hi; ++w) store_cols<OutT>(out + logmel_bags::out_offset(k.clip, n_frames, stride, w, lane, k.col), v_lo, v_hi);
+    }
+};
+
 template <typename InT, typename OutT, bool VEC>
 __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_bags_kernel(const InT* __restrict__ pcm, int64_t row_stride,
                                                                      const int32_t* __restrict__ counts, int n_items, int n_frames,
                                                                      int stride, const float* __restrict__ tab, OutT* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_xch = smem;
-    float* s_mel = s_xch + (kThreadsDyn / 16) * kPair * kXchFloats;
-    float* s_pw = s_mel + 16 * kMelRow;
-    float* s_win = s_pw + 16 * kPwPitch;
-    int* s_next = reinterpret_cast<int*>(s_win + kWinFloats);
-
-    const int t = threadIdx.x, g = t >> 4, gl = g & 3, j = t & 15, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    float* xa = s_xch + (kPair * g) * kXchFloats;
-    float* xb = xa + kXchFloats;
-    float* stage = s_xch + (kItemFrames * wv) * kXchFloats;      // the wave's first exchange buffer: 8 columns x 64 bands
-
-    LaneConsts c;
-    load_consts(c, tab, j);
-    for (int i = t; i < 16 * kMelRow; i += kThreadsDyn) s_mel[i] = tab[kTabMelW + i];
-    for (int i = t; i < 16 * kPwRow; i += kThreadsDyn) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
-    for (int i = t; i < kWinFloats; i += kThreadsDyn) s_win[i] = tab[kTabWindow + i];
-    // this workgroup's contiguous share of the items
-    const int lo = int(int64_t(n_items) * int64_t(blockIdx.x) / int64_t(gridDim.x)), hi = int(int64_t(n_items) * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
-    if (t == 0) *s_next = lo;
-    const float* melw = s_mel + kMelRow * j;
-    const float* pw = s_pw + kPwPitch * j;
-    __syncthreads();                        // the only workgroup barrier: tables and the counter visible
-
-    auto pull = [&]() {                      // wave-uniform: one lane takes the next item of the workgroup's share
-        int v = 0;
-        if (lane == 0) v = atomicAdd(s_next, 1);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    const int lane_frame = kPair * gl;                        // this group's frame pair inside the item
-    // wave-uniform: the first sample of this group's pair in `item`, or null where the clip lacks the item's slot (or past the share)
-    auto item_frame = [&](int item, int& clip, int& col) -> const InT* {
-        if (item >= hi) return nullptr;
-        int slot, frame;
-        logmel_bags::item_locate(item, &clip, &slot, &frame);
-        col = logmel_bags::item_column(slot, frame);
-        if (slot >= counts[clip]) return nullptr;
-        return pcm + int64_t(clip) * row_stride + logmel_bags::frame_sample(slot, frame + lane_frame);
-    };
-    auto wave_fence = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    Samples<InT> smp;
-    int cur = pull(), clip = 0, col = 0;
-    const InT* frame = item_frame(cur, clip, col);
-    bool fetched = false;                                      // smp holds `frame`'s samples (prefetched by the item before)
-    while (cur < hi) {
-        const int nxt = pull();
-        int nclip = 0, ncol = 0;
-        const InT* next_frame = item_frame(nxt, nclip, ncol);
-        f32x4 v_lo = {0.f, 0.f, 0.f, 0.f}, v_hi = {0.f, 0.f, 0.f, 0.f};
-        if (frame) {
-            // after a zero item, or at the start, nothing has been prefetched for this one
-            if (!fetched) smp.template fetch<VEC>(frame, j);
-            pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, ColsToStage{stage + lane_frame * kBands});
-            _Pragma("unroll") for (int x = 0; x < 4; ++x) {
-                v_lo[x] = stage[x * kBands + lane];
-                v_hi[x] = stage[(4 + x) * kBands + lane];
-            }
-            wave_fence();                   // the stage is rewritten by the next FFT
-        }
-        fetched = frame && next_frame;
-        int t_lo, t_hi;
-        logmel_bags::column_windows(col, n_frames, stride, &t_lo, &t_hi);
-        for (int w = t_lo; w <= t_hi; ++w) store_cols<OutT>(out + logmel_bags::out_offset(clip, n_frames, stride, w, lane, col), v_lo, v_hi);
-        cur = nxt;
-        frame = next_frame;
-        clip = nclip;
-        col = ncol;
-    }
+    FrontDyn f(smem, tab);
+    f.share(n_items);
+    column_items<InT, OutT, VEC>(f, pcm, BagsMap{counts, n_frames, stride, row_stride}, out);
 }
 
 // Timeline (logmel_timeline_core.h): ragged rows of 16 kHz PCM -> the DISTINCT slots of every recording's windows at a hop of 32 q
@@ -532,49 +541,18 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_bags_kernel(const InT* 
 // pull increasing items, so the walk is usually zero or one step of scalar loads). The alternative, a range of workgroups per
 // recording, would leave a batch of one long and many short recordings to the few workgroups of the long one. Everything about an
 // item is wave-uniform; an item of columns without a spectrum (a short recording's missing examples) only stores zeros.
-struct TimelineCursor {
-    int rec, end_item;                       // the recording of the item and the first item past it
-    int first_item, cols, spec_cols, q;
-    int64_t first_slot;
-    int col;                                 // first column of the item
-};
-
-template <typename InT, typename OutT, bool VEC>
-__global__ __launch_bounds__(kThreadsDyn, 1) void logmel_timeline_kernel(const InT* __restrict__ pcm, int64_t row_stride,
-                                                                         const logmel_timeline::Rec* __restrict__ recs, int n_rec,
-                                                                         int n_items, const float* __restrict__ tab, OutT* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_xch = smem;
-    float* s_mel = s_xch + (kThreadsDyn / 16) * kPair * kXchFloats;
-    float* s_pw = s_mel + 16 * kMelRow;
-    float* s_win = s_pw + 16 * kPwPitch;
-    int* s_next = reinterpret_cast<int*>(s_win + kWinFloats);
-
-    const int t = threadIdx.x, g = t >> 4, gl = g & 3, j = t & 15, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    float* xa = s_xch + (kPair * g) * kXchFloats;
-    float* xb = xa + kXchFloats;
-    float* stage = s_xch + (kItemFrames * wv) * kXchFloats;      // the wave's first exchange buffer: 8 columns x 64 bands
-
-    LaneConsts c;
-    load_consts(c, tab, j);
-    for (int i = t; i < 16 * kMelRow; i += kThreadsDyn) s_mel[i] = tab[kTabMelW + i];
-    for (int i = t; i < 16 * kPwRow; i += kThreadsDyn) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
-    for (int i = t; i < kWinFloats; i += kThreadsDyn) s_win[i] = tab[kTabWindow + i];
-    // this workgroup's contiguous share of the items
-    const int lo = int(int64_t(n_items) * int64_t(blockIdx.x) / int64_t(gridDim.x)), hi = int(int64_t(n_items) * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
-    if (t == 0) *s_next = lo;
-    const float* melw = s_mel + kMelRow * j;
-    const float* pw = s_pw + kPwPitch * j;
-    __syncthreads();                        // the only workgroup barrier: tables and the counter visible
-
-    auto pull = [&]() {                      // wave-uniform: one lane takes the next item of the workgroup's share
-        int v = 0;
-        if (lane == 0) v = atomicAdd(s_next, 1);
-        return __builtin_amdgcn_readfirstlane(v);
+struct TimelineMap {
+    const logmel_timeline::Rec* __restrict__ recs;
+    int n_rec, n_items;
+    int64_t row_stride;
+    struct Cursor {
+        int rec, end_item;                   // the recording of the item and the first item past it
+        int first_item, cols, spec_cols, q;
+        int64_t first_slot;
+        int col;                             // first column of the item
     };
-    const int lane_frame = kPair * gl;                        // this group's frame pair inside the item
-    auto uni = [](int64_t v) { return __builtin_amdgcn_readfirstlane(int(v)); };
-    auto enter = [&](TimelineCursor& k, int rec) {            // wave-uniform: the descriptor of `rec` into the cursor
+    static __device__ __forceinline__ int uni(int64_t v) { return __builtin_amdgcn_readfirstlane(int(v)); }
+    __device__ __forceinline__ void enter(Cursor& k, int rec) const {      // wave-uniform: the descriptor of `rec` into the cursor
         const logmel_timeline::Rec& r = recs[rec];
         k.rec = rec;
         k.first_item = uni(r.first_item);
@@ -583,54 +561,38 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_timeline_kernel(const I
         k.q = uni(r.q);
         k.first_slot = (int64_t(uni(r.first_slot >> 32)) << 32) | uint32_t(uni(r.first_slot));
         k.end_item = rec + 1 < n_rec ? uni(recs[rec + 1].first_item) : n_items;
-    };
-    // wave-uniform: moves the cursor (which stands at or before `item`) to `item` and returns the first sample of this group's
-    // pair, or null where the item's columns have no spectrum (or the item is past the share)
-    auto item_frame = [&](int item, TimelineCursor& k) -> const InT* {
-        if (item >= hi) return nullptr;
+    }
+    __device__ __forceinline__ Cursor first(int item) const {
+        Cursor k;
+        enter(k, logmel_timeline::find_rec(recs, n_rec, item));
+        return k;
+    }
+    template <typename InT>
+    __device__ __forceinline__ const InT* frame(const InT* pcm, int item, int lane_frame, Cursor& k) const {
         while (item >= k.end_item) enter(k, k.rec + 1);
         k.col = logmel_timeline::item_column(item - k.first_item, k.cols, k.q);
-        if (k.col >= k.spec_cols) return nullptr;
+        if (k.col >= k.spec_cols) return nullptr;              // a short recording's missing examples
         return pcm + int64_t(k.rec) * row_stride + logmel_timeline::column_sample(k.col + lane_frame);
-    };
-    auto wave_fence = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    Samples<InT> smp;
-    int cur = pull();
-    if (cur >= hi) return;
-    TimelineCursor k;
-    enter(k, logmel_timeline::find_rec(recs, n_rec, cur));
-    const InT* frame = item_frame(cur, k);
-    bool fetched = false;                                      // smp holds `frame`'s samples (prefetched by the item before)
-    while (cur < hi) {
-        const int nxt = pull();
-        TimelineCursor kn = k;
-        const InT* next_frame = item_frame(nxt, kn);
-        f32x4 v_lo = {0.f, 0.f, 0.f, 0.f}, v_hi = {0.f, 0.f, 0.f, 0.f};
-        if (frame) {
-            // after a zero item, or at the start, nothing has been prefetched for this one
-            if (!fetched) smp.template fetch<VEC>(frame, j);
-            pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, ColsToStage{stage + lane_frame * kBands});
-            _Pragma("unroll") for (int x = 0; x < 4; ++x) {
-                v_lo[x] = stage[x * kBands + lane];
-                v_hi[x] = stage[(4 + x) * kBands + lane];
-            }
-            wave_fence();                   // the stage is rewritten by the next FFT
-        }
-        fetched = frame && next_frame;
+    }
+    template <typename OutT>
+    __device__ __forceinline__ void store(OutT* out, const Cursor& k, int lane, f32x4 v_lo, f32x4 v_hi) const {
         _Pragma("unroll") for (int s = 0; s < logmel_timeline::kColumnSlots; ++s) {
             int row, x;
             if (logmel_timeline::column_slot(k.col, k.cols, k.q, s, &row, &x)) {
                 store_cols<OutT>(out + logmel_timeline::out_offset(k.first_slot, row, lane, x), v_lo, v_hi);
             }
         }
-        cur = nxt;
-        frame = next_frame;
-        k = kn;
     }
+};
+
+template <typename InT, typename OutT, bool VEC>
+__global__ __launch_bounds__(kThreadsDyn, 1) void logmel_timeline_kernel(const InT* __restrict__ pcm, int64_t row_stride,
+                                                                         const logmel_timeline::Rec* __restrict__ recs, int n_rec,
+                                                                         int n_items, const float* __restrict__ tab, OutT* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    FrontDyn f(smem, tab);
+    f.share(n_items);
+    column_items<InT, OutT, VEC>(f, pcm, TimelineMap{recs, n_rec, n_items, row_stride}, out);
 }
 
 // Fused front (bf16 inference): PCM -> conv1's pooled NHWC output in one kernel; the bf16 examples never exist in memory. The
@@ -660,55 +622,28 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_conv1_kernel(const InT*
                                                                       const float* __restrict__ w, const float* __restrict__ bias,
                                                                       mma::bf16_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_xch = smem;
-    float* s_mel = s_xch + (kThreadsDyn / 16) * kPair * kXchFloats;
-    float* s_pw = s_mel + 16 * kMelRow;
-    float* s_win = s_pw + 16 * kPwPitch;
-    int* s_next = reinterpret_cast<int*>(s_win + kWinFloats);
     mma::u32x4* s_wa = reinterpret_cast<mma::u32x4*>(smem + kLdsFloatsDyn);
     float* s_bias = smem + kLdsFloatsDyn + kFusedWaBytes / 4;
 
-    const int t = threadIdx.x, g = t >> 4, gl = g & 3, j = t & 15, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    float* xa = s_xch + (kPair * g) * kXchFloats;
-    float* xb = xa + kXchFloats;
+    FrontDyn f(smem, tab);
+    const int lane = f.lane;
     // the wave's 8 exchange buffers: between two FFTs, buffer 0 holds the staged input rows and buffers 1-2 the output stage
-    char* wregion = reinterpret_cast<char*>(s_xch + (kItemFrames * wv) * kXchFloats);
+    char* wregion = reinterpret_cast<char*>(f.wave_xch);
     uint16_t* sX = reinterpret_cast<uint16_t*>(wregion);
     uint32_t* sX32 = reinterpret_cast<uint32_t*>(wregion);
     char* stage = wregion + kXchFloats * 4;
 
-    LaneConsts c;
-    load_consts(c, tab, j);
-    for (int i = t; i < 16 * kMelRow; i += kThreadsDyn) s_mel[i] = tab[kTabMelW + i];
-    for (int i = t; i < 16 * kPwRow; i += kThreadsDyn) s_pw[(i >> 4) * kPwPitch + (i & 15)] = tab[kTabPw + i];
-    for (int i = t; i < kWinFloats; i += kThreadsDyn) s_win[i] = tab[kTabWindow + i];
-    s_wa[t] = __builtin_bit_cast(mma::u32x4, conv1::weight_frag(w, wv >> 1, wv & 1, lane));
-    if (t < 64) s_bias[t] = bias[t];
-    // this workgroup's contiguous share of the clips
-    const int lo = int(int64_t(n_clips) * int64_t(blockIdx.x) / int64_t(gridDim.x)), hi = int(int64_t(n_clips) * (int64_t(blockIdx.x) + 1) / int64_t(gridDim.x));
-    if (t == 0) *s_next = lo;
-    const float* melw = s_mel + kMelRow * j;
-    const float* pw = s_pw + kPwPitch * j;
-    __syncthreads();                        // the only workgroup barrier (no store is in flight yet): tables and the counter visible
+    s_wa[f.t] = __builtin_bit_cast(mma::u32x4, conv1::weight_frag(w, f.wv >> 1, f.wv & 1, lane));
+    if (f.t < 64) s_bias[f.t] = bias[f.t];
+    f.share(n_clips);                       // a share of whole clips; no store is in flight yet at its barrier
 
-    auto pull = [&]() {                      // wave-uniform: one lane takes the next clip of the workgroup's share
-        int v = 0;
-        if (lane == 0) v = atomicAdd(s_next, 1);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    const int lane_frame = kPair * gl;                        // this group's frame pair inside the item
     auto item_frame = [&](int clip, int item) {               // first sample of this group's pair in (clip, item)
         const int wf = clip / examples, e = clip - wf * examples;
-        return pcm + int64_t(wf) * wave_stride + (int64_t(e) * kExFrames + item * kItemFrames + lane_frame) * kHop;
-    };
-    auto wave_fence = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        return pcm + int64_t(wf) * wave_stride + (int64_t(e) * kExFrames + item * kItemFrames + f.lane_frame) * kHop;
     };
     Samples<InT> smp;
-    int clip = pull(), item = 0;
-    if (clip < hi) smp.template fetch<VEC>(item_frame(clip, 0), j);
+    int clip = f.pull(), item = 0;
+    if (clip < f.hi) smp.template fetch<VEC>(item_frame(clip, 0), f.j);
     // The 3 staged rows an item hands to the next one must survive the FFTs in between, which rewrite the exchange buffers --
     // except the two pad columns of every exchange row (phase 1 writes 16 of a row's 18 complex). The pads of exchange rows
     // 9 .. 15 also lie beyond the magnitudes and the finished row (floats 0 .. 319), so nothing touches them: 28 dwords per
@@ -724,7 +659,7 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_conv1_kernel(const InT*
             if (lane < 3 * kStagedDwords - 64) sX32[64 + lane] = item == 0 ? 0u : k1;
         }
         if (lane < kStagedDwords) sX32[11 * kStagedDwords + lane] = 0u;         // row 11: the zero row below the clip (read by item 11 only)
-        wave_fence();
+        group_sync<true>();
         {
             mma::bf16x8 wa[4][2];
             conv1::f32x16 binit[2];
@@ -749,108 +684,63 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_conv1_kernel(const InT*
             parked[park_slot(lane)] = k0;
             parked[park_slot(second)] = k1;         // lanes past the end rewrite the last dword with its own value
         }
-        wave_fence();                       // the staged rows and the stage are rewritten by the next FFT
+        group_sync<true>();                 // the staged rows and the stage are rewritten by the next FFT
     };
-    while (clip < hi) {
+    while (clip < f.hi) {
         int nclip = clip, nitem = item + 1;
-        if (nitem == kClipItems) { nclip = pull(); nitem = 0; }
-        const InT* next_frame = nclip < hi ? item_frame(nclip, nitem) : nullptr;
+        if (nitem == kClipItems) { nclip = f.pull(); nitem = 0; }
+        const InT* next_frame = nclip < f.hi ? item_frame(nclip, nitem) : nullptr;
         // staged row r <-> input row 8 item - 3 + r: this item's rows are r = 3 .. 10
-        pair_step<InT, VEC, true>(c, j, smp, next_frame, xa, xb, s_win, melw, pw, RowsToStaged{sX + (3 + lane_frame) * conv1::kPitch});
+        f.template pair<VEC>(smp, next_frame, RowsToStaged{sX + (3 + f.lane_frame) * conv1::kPitch});
         conv_item(clip, item);
         clip = nclip;
         item = nitem;
     }
 }
 
-template <typename InT>
-int launch_fused(const void* pcm, int64_t n_wave, int64_t wave_stride, int64_t examples, const float* tables, const float* w,
-                 const float* bias, void* out, hipStream_t stream) {
-    const int64_t n_clips = n_wave * examples;
-    if (n_clips == 0) return MLA_OK;
-    MLA_REQUIRE(n_clips <= 0x7fffffff / kClipItems, MLA_E_SHAPE, "too many clips for one launch (%lld)", (long long)n_clips);
-    const bool vec = mla::aligned(pcm, 2 * sizeof(InT)) && (wave_stride % 2 == 0);
+// One launch of a persistent kernel: `per_cu` workgroups on every CU, but no more than `want` (the units there are to share out).
+template <typename Kern, typename... Args>
+int launch_persistent(Kern kern, const char* name, int threads, int per_cu, int lds_bytes, int64_t want, hipStream_t stream, Args... args) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t wgs = n_clips < cus ? n_clips : cus;
-    auto go = [&](auto kern) -> int {
-        MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesFused));
-        hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(kThreadsDyn), kLdsBytesFused, stream, static_cast<const InT*>(pcm), wave_stride,
-                           int(examples), int(n_clips), tables, w, bias, static_cast<mma::bf16_t*>(out));
-        MLA_LAUNCH_OK("logmel_conv1_kernel");
-        return MLA_OK;
-    };
-    return vec ? go(logmel_conv1_kernel<InT, true>) : go(logmel_conv1_kernel<InT, false>);
+    const int64_t wgs = want < per_cu * int64_t(cus) ? want : per_cu * int64_t(cus);
+    MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(threads), lds_bytes, stream, args...);
+    MLA_LAUNCH_OK(name);
+    return MLA_OK;
 }
+constexpr int64_t item_wgs(int64_t n_items) { return (n_items + 7) / 8; }      // an item for each of a workgroup's 8 waves
 
-template <typename InT, typename OutT>
-int launch_bags(const void* pcm, int64_t clips, int64_t row_stride, const int32_t* counts, int n_frames, int stride, const float* tables,
-                void* out, hipStream_t stream) {
-    const int64_t n_items = clips * logmel_bags::kClipItems;
+// fn(InT{}, vec): vec is std::true_type where a lane's sample pair can be one load, which needs every row to begin at a pair
+template <typename InT, typename Fn>
+int by_pair_loads(const void* pcm, int64_t row_stride, Fn&& fn) {
     const bool vec = mla::aligned(pcm, 2 * sizeof(InT)) && (row_stride % 2 == 0);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t wgs = (n_items + 7) / 8 < cus ? (n_items + 7) / 8 : cus;
-    auto go = [&](auto kern) -> int {
-        MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesDyn));
-        hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(kThreadsDyn), kLdsBytesDyn, stream, static_cast<const InT*>(pcm), row_stride,
-                           counts, int(n_items), n_frames, stride, tables, static_cast<OutT*>(out));
-        MLA_LAUNCH_OK("logmel_bags_kernel");
-        return MLA_OK;
-    };
-    return vec ? go(logmel_bags_kernel<InT, OutT, true>) : go(logmel_bags_kernel<InT, OutT, false>);
+    return vec ? fn(InT{}, std::true_type{}) : fn(InT{}, std::false_type{});
+}
+// The dtype dispatch of every entry: fn(InT{}, vec) for the fused entry, fn(InT{}, OutT{}, vec) for the others.
+template <typename Fn>
+int by_pcm(int pcm_dtype, const void* pcm, int64_t row_stride, Fn&& fn) {
+    return pcm_dtype == MLA_F32 ? by_pair_loads<float>(pcm, row_stride, fn) : by_pair_loads<int16_t>(pcm, row_stride, fn);
+}
+template <typename Fn>
+int by_dtypes(int pcm_dtype, int out_dtype, const void* pcm, int64_t row_stride, Fn&& fn) {
+    return by_pcm(pcm_dtype, pcm, row_stride, [&](auto in, auto vec) {
+        return out_dtype == MLA_F32 ? fn(in, float{}, vec) : fn(in, __hip_bfloat16{}, vec);
+    });
 }
 
-template <typename InT, typename OutT>
-int launch_timeline(const void* pcm, int64_t row_stride, const int64_t* desc, int n_rec, int64_t n_items, const float* tables, void* out,
-                    hipStream_t stream) {
-    const bool vec = mla::aligned(pcm, 2 * sizeof(InT)) && (row_stride % 2 == 0);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t wgs = (n_items + 7) / 8 < cus ? (n_items + 7) / 8 : cus;
-    auto go = [&](auto kern) -> int {
-        MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesDyn));
-        hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(kThreadsDyn), kLdsBytesDyn, stream, static_cast<const InT*>(pcm), row_stride,
-                           reinterpret_cast<const logmel_timeline::Rec*>(desc), n_rec, int(n_items), tables, static_cast<OutT*>(out));
-        MLA_LAUNCH_OK("logmel_timeline_kernel");
-        return MLA_OK;
-    };
-    return vec ? go(logmel_timeline_kernel<InT, OutT, true>) : go(logmel_timeline_kernel<InT, OutT, false>);
+// What every entry requires of its dtypes and of the pointers all of them take. Two steps, because the bags and timeline entries
+// refuse an unknown dtype even for an empty batch, whose pointers may be null. `spell`: those two entries name the dtypes they take.
+int check_dtypes(int pcm_dtype, int out_dtype, bool spell) {
+    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d%s", pcm_dtype, spell ? " is neither MLA_F32 nor MLA_I16" : "");
+    MLA_REQUIRE(out_dtype == MLA_F32 || out_dtype == MLA_BF16, MLA_E_DTYPE, "out_dtype %d%s", out_dtype, spell ? " is neither MLA_F32 nor MLA_BF16" : "");
+    return MLA_OK;
 }
-
-template <typename InT, typename OutT>
-int launch(const void* pcm, int64_t n_wave, int64_t wave_stride, int64_t examples, const float* tables,
-           void* out, bool wave_sync, bool static_wave, hipStream_t stream) {
-    const int64_t n_chunks = n_wave * examples * (kExFrames / kChunk);
-    if (n_chunks == 0) return MLA_OK;
-    const bool vec = mla::aligned(pcm, 2 * sizeof(InT)) && (wave_stride % 2 == 0);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t grid = n_chunks < kWgPerCu * int64_t(cus) ? n_chunks : kWgPerCu * int64_t(cus);
-    ChunkMap map{wave_stride, int(examples * (kExFrames / kChunk))};
-    auto go = [&](auto kern) -> int {
-        MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        hipLaunchKernelGGL(kern, dim3(unsigned(grid)), dim3(kThreads), kLdsBytes, stream,
-                           static_cast<const InT*>(pcm), map, n_chunks, tables, static_cast<OutT*>(out));
-        MLA_LAUNCH_OK("logmel_kernel");
-        return MLA_OK;
-    };
-    if (wave_sync && !static_wave) {            // shipped: one 512-thread workgroup per CU, waves pull 8-frame items from an LDS counter
-        const int64_t n_items = n_chunks * (kChunk / kItemFrames);
-        MLA_REQUIRE(n_items <= 0x7fffffff, MLA_E_SHAPE, "too many frames for one launch (%lld items)", (long long)n_items);
-        const int64_t wgs = (n_items + 7) / 8 < cus ? (n_items + 7) / 8 : cus;
-        auto god = [&](auto kern) -> int {
-            MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesDyn));
-            hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(kThreadsDyn), kLdsBytesDyn, stream,
-                               static_cast<const InT*>(pcm), map, n_items, tables, static_cast<OutT*>(out));
-            MLA_LAUNCH_OK("logmel_dyn_kernel");
-            return MLA_OK;
-        };
-        return vec ? god(logmel_dyn_kernel<InT, OutT, true>) : god(logmel_dyn_kernel<InT, OutT, false>);
-    }
-    if (static_wave) return vec ? go(logmel_kernel<InT, OutT, true, true>) : go(logmel_kernel<InT, OutT, false, true>);
-    return vec ? go(logmel_kernel<InT, OutT, true, false>) : go(logmel_kernel<InT, OutT, false, false>);
+int check_pointers(const void* pcm, int pcm_dtype, const float* tables, const void* out, const char* tables_text) {
+    MLA_REQUIRE(mla::aligned(out, 16), MLA_E_ARG, "out must be 16-byte aligned");
+    MLA_REQUIRE(mla::aligned(tables, 4), MLA_E_ARG, "%s", tables_text);
+    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
+    return MLA_OK;
 }
 
 }  // namespace
@@ -903,21 +793,27 @@ extern "C" int mla_logmel_examples(const void* pcm, int pcm_dtype, int64_t n_wav
     if (rc != MLA_OK) return rc;
     if (n_wave == 0 || examples == 0) return MLA_OK;
     MLA_REQUIRE(pcm && tables && out, MLA_E_ARG, "null pcm/tables/out");
-    MLA_REQUIRE(mla::aligned(out, 16) && mla::aligned(tables, 4), MLA_E_ARG, "out must be 16-byte aligned");
-    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d", pcm_dtype);
-    MLA_REQUIRE(out_dtype == MLA_F32 || out_dtype == MLA_BF16, MLA_E_DTYPE, "out_dtype %d", out_dtype);
-    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
-    // MLA_LOGMEL_SYNC: "block" = cross-check build of the group sync (static kernel, full barriers); "static" = the round-1
-    // schedule (static shares, wave-level fences) for A/B against the shipped dynamic kernel
+    if (const int bad = check_dtypes(pcm_dtype, out_dtype, false); bad != MLA_OK) return bad;
+    if (const int bad = check_pointers(pcm, pcm_dtype, tables, out, "out must be 16-byte aligned"); bad != MLA_OK) return bad;
+    const int64_t n_chunks = n_wave * examples * (kExFrames / kChunk), n_items = n_chunks * (kChunk / kItemFrames);
+    const ChunkMap map{wave_stride, int(examples * (kExFrames / kChunk))};
+    // MLA_LOGMEL_SYNC=block: the cross-check build of the group sync (static kernel, full barriers)
     const char* env = getenv("MLA_LOGMEL_SYNC");
-    const bool wave_sync = !(env && env[0] == 'b'), static_wave = env && env[0] == 's';
+    const bool block_sync = env && env[0] == 'b';
+    MLA_REQUIRE(block_sync || n_items <= 0x7fffffff, MLA_E_SHAPE, "too many frames for one launch (%lld items)", (long long)n_items);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (pcm_dtype == MLA_F32) {
-        return out_dtype == MLA_F32 ? launch<float, float>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s)
-                                    : launch<float, __hip_bfloat16>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s);
-    }
-    return out_dtype == MLA_F32 ? launch<int16_t, float>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s)
-                                : launch<int16_t, __hip_bfloat16>(pcm, n_wave, wave_stride, examples, tables, out, wave_sync, static_wave, s);
+    return by_dtypes(pcm_dtype, out_dtype, pcm, wave_stride, [&](auto in, auto o, auto vec) {
+        using InT = decltype(in);
+        using OutT = decltype(o);
+        constexpr bool kVec = decltype(vec)::value;
+        if (block_sync) {
+            return launch_persistent(logmel_kernel<InT, OutT, kVec>, "logmel_kernel", kThreads, kWgPerCu, kLdsBytes, n_chunks, s,
+                                     static_cast<const InT*>(pcm), map, n_chunks, tables, static_cast<OutT*>(out));
+        }
+        // shipped: one 512-thread workgroup per CU, waves pull 8-frame items from an LDS counter
+        return launch_persistent(logmel_dyn_kernel<InT, OutT, kVec>, "logmel_dyn_kernel", kThreadsDyn, 1, kLdsBytesDyn, item_wgs(n_items), s,
+                                 static_cast<const InT*>(pcm), map, n_items, tables, static_cast<OutT*>(out));
+    });
 }
 
 extern "C" int mla_logmel_bags(const void* pcm, int pcm_dtype, int64_t clips, int64_t n_samples, int64_t row_stride,
@@ -925,15 +821,13 @@ extern "C" int mla_logmel_bags(const void* pcm, int pcm_dtype, int64_t clips, in
                                void* out, int out_dtype, mla_stream_t stream) {
     MLA_REQUIRE(clips >= 0 && n_samples >= 0 && row_stride >= n_samples, MLA_E_ARG, "bad clips %lld / stride %lld < n_samples %lld",
                 (long long)clips, (long long)row_stride, (long long)n_samples);
-    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d is neither MLA_F32 nor MLA_I16", pcm_dtype);
-    MLA_REQUIRE(out_dtype == MLA_F32 || out_dtype == MLA_BF16, MLA_E_DTYPE, "out_dtype %d is neither MLA_F32 nor MLA_BF16", out_dtype);
+    if (const int bad = check_dtypes(pcm_dtype, out_dtype, true); bad != MLA_OK) return bad;
     MLA_REQUIRE(logmel_bags::config_ok(n_frames, stride), MLA_E_SHAPE,
                 "%d frames at stride %d: only (10, 32) and (4, 96) are compiled (dataset.py:352-361)", n_frames, stride);
     if (clips == 0) return MLA_OK;
     MLA_REQUIRE(pcm && counts && host_counts && tables && out, MLA_E_ARG, "null pcm/counts/host_counts/tables/out");
-    MLA_REQUIRE(mla::aligned(out, 16), MLA_E_ARG, "out must be 16-byte aligned");
-    MLA_REQUIRE(mla::aligned(tables, 4) && mla::aligned(counts, 4), MLA_E_ARG, "tables and counts must be 4-byte aligned");
-    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
+    if (const int bad = check_pointers(pcm, pcm_dtype, tables, out, "tables and counts must be 4-byte aligned"); bad != MLA_OK) return bad;
+    MLA_REQUIRE(mla::aligned(counts, 4), MLA_E_ARG, "tables and counts must be 4-byte aligned");
     MLA_REQUIRE(clips <= 0x7fffffff / logmel_bags::kClipItems, MLA_E_SHAPE, "too many clips for one launch (%lld)", (long long)clips);
     for (int64_t i = 0; i < clips; ++i) {
         const int n = host_counts[i];
@@ -943,12 +837,14 @@ extern "C" int mla_logmel_bags(const void* pcm, int pcm_dtype, int64_t clips, in
                     (long long)i, n, (long long)logmel_bags::samples_read(n), (long long)n_samples);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (pcm_dtype == MLA_F32) {
-        return out_dtype == MLA_F32 ? launch_bags<float, float>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s)
-                                    : launch_bags<float, __hip_bfloat16>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s);
-    }
-    return out_dtype == MLA_F32 ? launch_bags<int16_t, float>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s)
-                                : launch_bags<int16_t, __hip_bfloat16>(pcm, clips, row_stride, counts, n_frames, stride, tables, out, s);
+    const int64_t n_items = clips * logmel_bags::kClipItems;
+    return by_dtypes(pcm_dtype, out_dtype, pcm, row_stride, [&](auto in, auto o, auto vec) {
+        using InT = decltype(in);
+        using OutT = decltype(o);
+        return launch_persistent(logmel_bags_kernel<InT, OutT, decltype(vec)::value>, "logmel_bags_kernel", kThreadsDyn, 1, kLdsBytesDyn,
+                                 item_wgs(n_items), s, static_cast<const InT*>(pcm), row_stride, counts, int(n_items), n_frames, stride, tables,
+                                 static_cast<OutT*>(out));
+    });
 }
 
 extern "C" int mla_timeline_counts(int64_t n_samples, int64_t hop_slots, int64_t* windows, int64_t* slots, int64_t* samples_read) {
@@ -973,16 +869,14 @@ extern "C" int mla_logmel_timeline(const void* pcm, int pcm_dtype, int64_t recor
     MLA_REQUIRE(recordings >= 0 && n_samples >= 0 && row_stride >= n_samples && total_slots >= 0, MLA_E_ARG,
                 "bad recordings %lld / stride %lld < n_samples %lld / total_slots %lld", (long long)recordings, (long long)row_stride,
                 (long long)n_samples, (long long)total_slots);
-    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d is neither MLA_F32 nor MLA_I16", pcm_dtype);
-    MLA_REQUIRE(out_dtype == MLA_F32 || out_dtype == MLA_BF16, MLA_E_DTYPE, "out_dtype %d is neither MLA_F32 nor MLA_BF16", out_dtype);
+    if (const int bad = check_dtypes(pcm_dtype, out_dtype, true); bad != MLA_OK) return bad;
     if (recordings == 0) {
         MLA_REQUIRE(total_slots == 0, MLA_E_ARG, "no recordings but %lld slots", (long long)total_slots);
         return MLA_OK;
     }
     MLA_REQUIRE(pcm && desc && host_desc && tables && out, MLA_E_ARG, "null pcm/desc/host_desc/tables/out");
-    MLA_REQUIRE(mla::aligned(out, 16), MLA_E_ARG, "out must be 16-byte aligned");
-    MLA_REQUIRE(mla::aligned(tables, 4) && mla::aligned(desc, 8), MLA_E_ARG, "tables must be 4-byte and desc 8-byte aligned");
-    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
+    if (const int bad = check_pointers(pcm, pcm_dtype, tables, out, "tables must be 4-byte and desc 8-byte aligned"); bad != MLA_OK) return bad;
+    MLA_REQUIRE(mla::aligned(desc, 8), MLA_E_ARG, "tables must be 4-byte and desc 8-byte aligned");
     MLA_REQUIRE(recordings <= 0x7fffffff / logmel_timeline::kWindowItems, MLA_E_SHAPE, "too many recordings for one launch (%lld)",
                 (long long)recordings);
     const logmel_timeline::Rec* recs = reinterpret_cast<const logmel_timeline::Rec*>(host_desc);
@@ -1006,13 +900,13 @@ extern "C" int mla_logmel_timeline(const void* pcm, int pcm_dtype, int64_t recor
     MLA_REQUIRE(slot_prefix == total_slots, MLA_E_ARG, "the descriptors fill %lld slots, out has %lld", (long long)slot_prefix,
                 (long long)total_slots);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n_rec = int(recordings);
-    if (pcm_dtype == MLA_F32) {
-        return out_dtype == MLA_F32 ? launch_timeline<float, float>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s)
-                                    : launch_timeline<float, __hip_bfloat16>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s);
-    }
-    return out_dtype == MLA_F32 ? launch_timeline<int16_t, float>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s)
-                                : launch_timeline<int16_t, __hip_bfloat16>(pcm, row_stride, desc, n_rec, item_prefix, tables, out, s);
+    return by_dtypes(pcm_dtype, out_dtype, pcm, row_stride, [&](auto in, auto o, auto vec) {
+        using InT = decltype(in);
+        using OutT = decltype(o);
+        return launch_persistent(logmel_timeline_kernel<InT, OutT, decltype(vec)::value>, "logmel_timeline_kernel", kThreadsDyn, 1, kLdsBytesDyn,
+                                 item_wgs(item_prefix), s, static_cast<const InT*>(pcm), row_stride, reinterpret_cast<const logmel_timeline::Rec*>(desc),
+                                 int(recordings), int(item_prefix), tables, static_cast<OutT*>(out));
+    });
 }
 
 extern "C" int mla_logmel_conv1(const void* pcm, int pcm_dtype, int64_t n_wave, int64_t n_samples, int64_t wave_stride,
@@ -1024,11 +918,16 @@ extern "C" int mla_logmel_conv1(const void* pcm, int pcm_dtype, int64_t n_wave, 
     if (rc != MLA_OK) return rc;
     if (n_wave == 0 || examples == 0) return MLA_OK;
     MLA_REQUIRE(pcm && tables && w && bias && out, MLA_E_ARG, "null pcm/tables/w/bias/out");
-    MLA_REQUIRE(mla::aligned(out, 16) && mla::aligned(tables, 4) && mla::aligned(w, 4) && mla::aligned(bias, 4), MLA_E_ARG,
-                "out must be 16-byte aligned");
-    MLA_REQUIRE(pcm_dtype == MLA_F32 || pcm_dtype == MLA_I16, MLA_E_DTYPE, "pcm_dtype %d", pcm_dtype);
-    MLA_REQUIRE(mla::aligned(pcm, pcm_dtype == MLA_F32 ? 4 : 2), MLA_E_ARG, "pcm misaligned for its dtype");
+    if (const int bad = check_dtypes(pcm_dtype, MLA_BF16, false); bad != MLA_OK) return bad;
+    if (const int bad = check_pointers(pcm, pcm_dtype, tables, out, "out must be 16-byte aligned"); bad != MLA_OK) return bad;
+    MLA_REQUIRE(mla::aligned(w, 4) && mla::aligned(bias, 4), MLA_E_ARG, "out must be 16-byte aligned");
+    const int64_t n_clips = n_wave * examples;
+    MLA_REQUIRE(n_clips <= 0x7fffffff / kClipItems, MLA_E_SHAPE, "too many clips for one launch (%lld)", (long long)n_clips);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return pcm_dtype == MLA_F32 ? launch_fused<float>(pcm, n_wave, wave_stride, examples, tables, w, bias, out, s)
-                                : launch_fused<int16_t>(pcm, n_wave, wave_stride, examples, tables, w, bias, out, s);
+    return by_pcm(pcm_dtype, pcm, wave_stride, [&](auto in, auto vec) {
+        using InT = decltype(in);
+        return launch_persistent(logmel_conv1_kernel<InT, decltype(vec)::value>, "logmel_conv1_kernel", kThreadsDyn, 1, kLdsBytesFused, n_clips, s,
+                                 static_cast<const InT*>(pcm), wave_stride, int(examples), int(n_clips), tables, w, bias,
+                                 static_cast<mma::bf16_t*>(out));
+    });
 }

@@ -7,33 +7,10 @@
 #include <vector>
 
 #include "logmel_bags_core.h"
-#include "logmel_core.h"
-#include "logmel_tables.h"
+#include "logmel_hostsim_frame.h"
 
 using namespace logmel;
 using namespace logmel_bags;
-
-namespace {
-// one STFT frame -> 64 log-mel bands, lane by lane
-void frame_row(const LaneConsts* c, const float* tab, const float* frame, float* row) {
-    float xch[2 * 16 * kXchStride];
-    float re[16][16], im[16][16], vr[16][8], vi[16][8];
-    for (int j = 0; j < 16; ++j) phase1(c[j], j, frame, tab + kTabWindow, xch);
-    for (int j = 0; j < 16; ++j) phase2_read(j, xch, re[j], im[j]);
-    for (int j = 0; j < 16; ++j) phase2_fft(re[j], im[j]);
-    for (int j = 0; j < 16; ++j) phase3_view(j, re[j], im[j], vr[j], vi[j]);
-    float* mag = xch;                                          // magnitudes alias the dead exchange buffer
-    for (int j = 0; j < 16; ++j) {
-        const int partner = (16 - j) & 15;
-        phase3_pairs(j, re[j], im[j], vr[partner], vi[partner], mag, tab + kTabPw + kPwRow * j);
-    }
-    for (int j = 0; j < 16; ++j) {
-        float o[4];
-        phase4(c[j], j, mag, tab + kTabMelW + kMelRow * j, o);
-        for (int s = 0; s < 4; ++s) row[band_of(j, s)] = o[s];
-    }
-}
-}  // namespace
 
 // pcm[clips][row_stride] float32 at 16 kHz; counts[clips] in 0..4; out and writes: clips * n_frames * 64 * 96 elements (writes must
 // come in zeroed). Returns 0, -1 for a configuration the kernel refuses, -2 for a count outside 0..4 or beyond n_samples.

@@ -1,5 +1,5 @@
 """Front-end time against batch size (f32 PCM in, bf16 out): per-waveform cost falls with the launch size.
-    python scripts/fe_curve.py        (MLA_LOGMEL_SYNC=static selects the round-1 static kernel for A/B)"""
+    python scripts/fe_curve.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
