@@ -395,6 +395,7 @@ def test_maxpool2x2(ops, dtype):
 
 # ------------------------------------------------------------------------------------------- 4. ResNet trunk ----
 
+import pin_leftover_cases as PL                                                      # noqa: E402
 import resnet50_restated as RR                                                       # noqa: E402
 import test_resnet_kernels_gpu as RK                                                 # noqa: E402
 
@@ -528,20 +529,24 @@ def test_rn_bn_stats(ops, dtype):
 @pytest.mark.parametrize("dtype", RN_DTYPES, ids=name)
 @pytest.mark.parametrize("conf", ["repeat", "single"])
 def test_rn_stem(ops, dtype, conf):
-    """rn_stem on two 224 x 224 planes against float64 conv2d of the normalised channels (test_stem_borders' criterion: max error over
-    max value 1e-4 / 1e-2). A NaN pixel in the interior and one in a corner of plane 0 (taps outside the image are skipped: the
-    corner NaN reaches only the outputs whose window holds it); plane 1 keeps the clean run's bits. A NaN in a CORNER tap of one
-    filter makes that whole channel NaN, border pixels included: nn.Conv2d multiplies its zero padding with it."""
+    """rn_stem on two 224 x 224 planes against float64 conv2d of the normalised channels (the per-element derived bound of
+    test_rn_stem_every_element_within_its_derived_bound: 55 roundings on sum|terms|, plus half a bf16 ulp; it is below the 1e-4 / 1e-2
+    of the largest value that test_stem_borders grants, which is asserted). A NaN pixel in the interior and one in a corner of plane
+    0 (taps outside the image are skipped: the corner NaN reaches only the outputs whose window holds it); plane 1 keeps the clean
+    run's bits. A NaN in a CORNER tap of one filter makes that whole channel NaN, border pixels included: nn.Conv2d multiplies its
+    zero padding with it."""
     g = torch.Generator().manual_seed(5)
     x = torch.rand(2, 224, 224, generator=g)
     w = torch.randn(64, 3, 7, 7, generator=g) * 0.05
     tol = 1e-4 if dtype == F32 else 1e-2
 
     def check(x, w, what):
-        ref = F.conv2d(RR.normalize_input(x.double().reshape(2, 1, 1, 224, 224), conf), w.double(), stride=2, padding=3).permute(0, 2, 3, 1)
+        acc, terms = PL.stem_reference(x, w, conf)
+        ref, bound = PL.stem_bound(acc, terms, None, None, False, dtype)
         got = ops.rn_stem(x.cuda(), conf == "single", w.cuda(), dtype)
         top = float(ref[torch.isfinite(ref)].abs().max())
-        same_nonfinite(got, ref, what, finite=N.bounded(torch.full_like(ref, tol * top), what))
+        assert float(bound[torch.isfinite(bound)].max()) <= tol * top
+        same_nonfinite(got, ref, what, finite=N.bounded(bound, what))
         return got, ref
 
     clean, _ = check(x, w, "rn_stem clean")
@@ -587,7 +592,8 @@ def head_bn_forward(x, mean, var, gamma, beta, mode, period, act, keep, drop_sca
 @pytest.mark.parametrize("mode,period,rows,cols", [(0, 10, 70, 600), (1, 0, 37, 64)])
 def test_head_bn_stats_and_apply(ops, W, mode, period, rows, cols):
     """mla_bn_stats and mla_bn_apply in both layouts (channel = row % period, channel = column), acts 0 / 1 / 2, with and without a
-    keep mask. Statistics: a NaN poisons its own channel's mean and variance and no other. Apply, with the clean statistics: a NaN at
+    keep mask. Statistics: the clean run within the per-channel derived bounds of tests/test_pin_leftovers_gpu.py; a NaN poisons its
+    own channel's mean and variance and no other (the others keep the clean run's bits). Apply, with the clean statistics: a NaN at
     a DROPPED element stays NaN (F.dropout multiplies: NaN * 0), +inf gives +inf / +inf / 1, -inf gives -inf / 0 / 0, a dropped
     +inf gives NaN; a NaN in gamma, beta, mean or var makes exactly that channel NaN."""
     ch = period if mode == 0 else cols
@@ -599,6 +605,9 @@ def test_head_bn_stats_and_apply(ops, W, mode, period, rows, cols):
     bad = x.clone()
     bad[r0, c0], bad[r1, c1], bad[r2, c2], bad[r3, c3] = NAN, INF, -INF, INF
     mean, var = ops.bn_stats(x.cuda(), mode, period)
+    stats = PL.stats_reference(x, torch.zeros(ch), torch.ones(ch), mode, period)       # the clean run: test_pin_leftovers_gpu's criterion
+    for got, k in ((mean, "mean"), (var, "var")):
+        WH.within(got, stats[k], stats["b_" + k], "bn_stats mode %d clean %s" % (mode, k))
     mean_b, var_b = ops.bn_stats(torch.where(torch.isinf(bad), x, bad).cuda(), mode, period)
     other = torch.arange(ch, device="cuda") != channel_of(r0, c0)
     for clean, got in ((mean, mean_b), (var, var_b)):
