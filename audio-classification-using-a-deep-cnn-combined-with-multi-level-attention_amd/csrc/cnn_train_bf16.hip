@@ -310,8 +310,7 @@ template <int CIN, int COUT, int H, int W>
 int launch_wgrad_bf16(const bf16_t* dz, const bf16_t* ain, int64_t n, float* partial, int64_t partial_floats, float* dw, hipStream_t s) {
     using C = WBCfg<CIN, COUT, H, W>;
     const int tiles = C::TILES_CO * C::TILES_CI;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = mla::cu_count();
     int splits = cus / tiles < 1 ? 1 : cus / tiles;           // one persistent workgroup per CU
     if (splits > n) splits = int(n);
     const int64_t need = int64_t(splits) * COUT * 9 * CIN;

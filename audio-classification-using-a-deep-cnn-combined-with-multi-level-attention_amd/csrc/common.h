@@ -18,6 +18,14 @@ int fail(int code, const char* fmt, ...);   // formats into error_buffer(), retu
 
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// Compute units of the current device (256 when the query fails): what the launchers size persistent grids and choose GEMM tiles by.
+// Asked anew at every launch.
+inline int cu_count() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+}
+
 }  // namespace mla
 
 #define MLA_REQUIRE(cond, code, ...) \

@@ -904,8 +904,7 @@ int launch_conv(const void* in, const void* w, const float* bias, void* out, int
     const int64_t tiles = ((n_img + C::IMGS - 1) / C::IMGS) * C::TILES_Y;
     MLA_REQUIRE(tiles <= 0x7fffffff, MLA_E_SHAPE, "too many tiles");
     // persistent grid: one workgroup per CU and N-tile (two where LDS/VGPRs allow), a multiple of TILES_Y
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = mla::cu_count();
     constexpr int n_tiles_n = C::COUT / C::BN;
     constexpr int per_cu = (C::LDS_BYTES * 2 <= 160 * 1024 && C::MIN_WAVES >= 4) ? 2 : 1;
     int64_t gx = int64_t(cus) * per_cu / n_tiles_n;
@@ -1159,8 +1158,7 @@ extern "C" int mla_vggish_conv1(const void* x, int x_dtype, int64_t n, const flo
                 MLA_E_DTYPE, "conv1 dtypes %d -> %d", x_dtype, dtype);
     MLA_REQUIRE(dtype != MLA_BF16X3 || x_dtype == MLA_F32, MLA_E_DTYPE, "the split output is computed from float32 examples");
     MLA_REQUIRE(n * 12 <= 0x7fffffff, MLA_E_SHAPE, "batch too large");
-    int dev1 = 0, cus1 = 256;
-    if (hipGetDevice(&dev1) == hipSuccess) hipDeviceGetAttribute(&cus1, hipDeviceAttributeMultiprocessorCount, dev1);
+    const int cus1 = mla::cu_count();
     const int64_t blocks = n * 12 < int64_t(cus1) * 4 ? n * 12 : int64_t(cus1) * 4;      // persistent: 4 workgroups per CU (VGPR-limited)
     const int n_pix = int(n);
     hipStream_t s = static_cast<hipStream_t>(stream);

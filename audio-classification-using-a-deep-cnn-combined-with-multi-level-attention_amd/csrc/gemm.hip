@@ -476,9 +476,20 @@ int launch_ring(const void* a, int64_t lda, const void* w, int64_t ldw, const fl
     return MLA_OK;
 }
 
-template <typename T, typename TO>
-int dispatch(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, void* out, int64_t ldo,
-             int64_t M, int64_t N, int64_t K, bool relu, hipStream_t s, int seg = 0, int osplit = 0) {
+// fn(std::true_type | std::false_type): the run-time ReLU flag as the kernels' template argument
+template <typename Fn>
+int by_relu(bool relu, Fn&& fn) {
+    return relu ? fn(std::true_type{}) : fn(std::false_type{});
+}
+
+// Tile rows x tile columns of the kernel that dispatch<> launches. Every form keeps the K order per output element: same bits.
+enum class Tile { k64x128, k128x128, kRing, k128x256, k256x256, k320x256 };
+
+// DECIDING, apart from launching: the form for an (M, N, K) problem on `cus` compute units. m_tall: the rows that k256x256 covers
+// (M, unless the rows behind them run as 128-row tiles).
+template <typename T>
+Tile tile_form(int64_t M, int64_t N, int64_t K, int cus, int64_t& m_tall) {
+    m_tall = M;
     const bool wide = N > 128 && (N % 256 == 0 || N % 256 > 128);     // 256-wide tiles unless they waste > half a tile
     const bool tall = wide && M >= 4096 && N >= 1024;                  // 256 x 256 tiles once they still fill the chip
 #if MLA_GEMM_TILE320
@@ -487,65 +498,69 @@ int dispatch(const void* a, int64_t lda, const void* w, int64_t ldw, const float
         // rounds on 256 CUs (256 x 256: 640 tiles = 2.5 rounds), and the tile moves 72 KB per K stage for 1.25x the FLOPs of the
         // 64 KB one -- the GEMM is bound by the CU's L2 -> LDS fill rate (profiles/r02_conv_stamps.txt), so both count. Taken when
         // its rounds x bytes per stage beat the 256-row tiling's (K order per output element unchanged: bit-identical).
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         const int64_t n_tiles = (N + 255) / 256;
         const int64_t t256 = ((M + 255) / 256) * n_tiles, t320 = ((M + 319) / 320) * n_tiles;
         const int64_t full = t256 / cus, rest = t256 - full * cus;
         const double cost256 = 64.0 * double(full) + (rest == 0 ? 0.0 : (full >= 1 && 2 * rest <= cus && (full * cus) % n_tiles == 0 ? 48.0 : 64.0));
         const double cost320 = 72.0 * double((t320 + cus - 1) / cus);
-        if (cost320 < cost256)
-            return relu ? launch<T, TO, 10, 4, true>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit)
-                        : launch<T, TO, 10, 4, false>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+        if (cost320 < cost256) return Tile::k320x256;
     }
 #endif
     if (tall) {
         // Tile quantisation: 256 x 256 tiles run one per CU, so e.g. 640 tiles on 256 CUs take 3 rounds for 2.5 rounds of
         // work. When the last round would be at most half full, the rows of the whole rounds keep the tall tiles and the
         // remaining rows run as 128-row tiles (twice as many, same CUs busy): 2 + 0.5 rounds instead of 3.
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         const int64_t n_tiles = (N + 255) / 256, m_tiles = (M + 255) / 256;
         const int64_t full_rounds = m_tiles * n_tiles / cus, rest = m_tiles * n_tiles - full_rounds * cus;
-        int64_t m_tall = M;
         if (full_rounds >= 1 && rest > 0 && 2 * rest <= cus && (full_rounds * cus) % n_tiles == 0) m_tall = full_rounds * cus / n_tiles * 256;
-        int rc = relu ? launch<T, TO, 8, 4, true>(a, lda, w, ldw, bias, out, ldo, m_tall, N, K, s, 1, nullptr, seg, osplit)
-                      : launch<T, TO, 8, 4, false>(a, lda, w, ldw, bias, out, ldo, m_tall, N, K, s, 1, nullptr, seg, osplit);
-        if (rc != MLA_OK || m_tall == M) return rc;
-        const T* a2 = static_cast<const T*>(a) + m_tall * lda;
-        TO* out2 = static_cast<TO*>(out) + m_tall * ldo;
-        return relu ? launch<T, TO, 4, 4, true>(a2, lda, w, ldw, bias, out2, ldo, M - m_tall, N, K, s, 1, nullptr, seg, osplit)
-                    : launch<T, TO, 4, 4, false>(a2, lda, w, ldw, bias, out2, ldo, M - m_tall, N, K, s, 1, nullptr, seg, osplit);
+        return Tile::k256x256;
     }
-    // 128 x 256 tiles that would leave half the CUs idle (small batches: 1 020 rows x 4096 columns = 128 tiles) run as
-    // 128 x 128 tiles instead
     if (wide) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        // 128 x 256 tiles that would leave half the CUs idle (small batches: 1 020 rows x 4096 columns = 128 tiles) run as
+        // 128 x 128 tiles instead
         if (((M + 127) / 128) * ((N + 255) / 256) * 2 <= cus) {
 #if MLA_GEMM_RING
             if (K % mma::Elem<T>::kPerRow == 0 && K / mma::Elem<T>::kPerRow >= 8)       // long K streamed by few tiles: keep three stages in flight
-                return relu ? launch_ring<T, TO, true>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit)
-                            : launch_ring<T, TO, false>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+                return Tile::kRing;
 #endif
-            return relu ? launch<T, TO, 4, 2, true>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit)
-                        : launch<T, TO, 4, 2, false>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+            return Tile::k128x128;
         }
+        return Tile::k128x256;
     }
-    if (wide) return relu ? launch<T, TO, 4, 4, true>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit)
-                          : launch<T, TO, 4, 4, false>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
     // narrow layers (N <= 128: the embeddings' last Linear 4096 -> 128, the head's 128 -> 600 tail tiles) at batch sizes where
     // 128-row tiles leave most CUs idle: 64-row tiles double the workgroups (the K loop per output element is unchanged, so the
     // bits are too)
-    {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (((M + 127) / 128) * ((N + 127) / 128) < cus && M > 64)
-            return relu ? launch<T, TO, 2, 2, true>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit)
-                        : launch<T, TO, 2, 2, false>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
-    }
-    return relu ? launch<T, TO, 4, 2, true>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit)
-                : launch<T, TO, 4, 2, false>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+    if (((M + 127) / 128) * ((N + 127) / 128) < cus && M > 64)
+        return Tile::k64x128;
+    return Tile::k128x128;
+}
+
+template <typename T, typename TO>
+int dispatch(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, void* out, int64_t ldo,
+             int64_t M, int64_t N, int64_t K, bool relu, hipStream_t s, int seg = 0, int osplit = 0) {
+    int64_t m_tall;
+    const Tile form = tile_form<T>(M, N, K, mla::cu_count(), m_tall);
+    return by_relu(relu, [&](auto r) {
+        constexpr bool R = decltype(r)::value;
+        switch (form) {
+            case Tile::k64x128: return launch<T, TO, 2, 2, R>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+            case Tile::k128x128: return launch<T, TO, 4, 2, R>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+#if MLA_GEMM_RING
+            case Tile::kRing: return launch_ring<T, TO, R>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+#endif
+            case Tile::k128x256: return launch<T, TO, 4, 4, R>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+#if MLA_GEMM_TILE320
+            case Tile::k320x256: return launch<T, TO, 10, 4, R>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, 1, nullptr, seg, osplit);
+#endif
+            default: break;
+        }
+        // k256x256: the first m_tall rows, then 128-row tiles over what is left
+        const int rc = launch<T, TO, 8, 4, R>(a, lda, w, ldw, bias, out, ldo, m_tall, N, K, s, 1, nullptr, seg, osplit);
+        if (rc != MLA_OK || m_tall == M) return rc;
+        const T* a2 = static_cast<const T*>(a) + m_tall * lda;
+        TO* out2 = static_cast<TO*>(out) + m_tall * ldo;
+        return launch<T, TO, 4, 4, R>(a2, lda, w, ldw, bias, out2, ldo, M - m_tall, N, K, s, 1, nullptr, seg, osplit);
+    });
 }
 
 }  // namespace
@@ -567,8 +582,9 @@ extern "C" int mla_linear_splitk(const float* a, int64_t lda, const float* w, in
     MLA_REQUIRE(mla::aligned(a, 16) && mla::aligned(w, 16), MLA_E_ARG, "GEMM operands must be 16-byte aligned");
     MLA_REQUIRE(workspace_floats >= int64_t(splits) * M * N, MLA_E_ARG, "split-K workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return relu ? launch<float, float, 4, 2, true>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, splits, workspace)
-                : launch<float, float, 4, 2, false>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, splits, workspace);
+    return by_relu(relu != 0, [&](auto r) {
+        return launch<float, float, 4, 2, decltype(r)::value>(a, lda, w, ldw, bias, out, ldo, M, N, K, s, splits, workspace);
+    });
 }
 
 // Fixed K split for NARROW forward layers (N <= 128 with a long K: VGGish's last Linear 4096 -> 128): with one column tile there

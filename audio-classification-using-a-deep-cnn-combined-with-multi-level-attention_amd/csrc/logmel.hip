@@ -701,9 +701,8 @@ __global__ __launch_bounds__(kThreadsDyn, 1) void logmel_conv1_kernel(const InT*
 // One launch of a persistent kernel: `per_cu` workgroups on every CU, but no more than `want` (the units there are to share out).
 template <typename Kern, typename... Args>
 int launch_persistent(Kern kern, const char* name, int threads, int per_cu, int lds_bytes, int64_t want, hipStream_t stream, Args... args) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t wgs = want < per_cu * int64_t(cus) ? want : per_cu * int64_t(cus);
+    const int64_t slots = per_cu * int64_t(mla::cu_count());
+    const int64_t wgs = want < slots ? want : slots;
     MLA_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     hipLaunchKernelGGL(kern, dim3(unsigned(wgs)), dim3(threads), lds_bytes, stream, args...);
     MLA_LAUNCH_OK(name);
