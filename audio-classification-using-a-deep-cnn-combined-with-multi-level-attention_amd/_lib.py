@@ -134,6 +134,7 @@ def lib():
         L.mla_pool_bwd_codes_bf16.argtypes = [vp, vp, vp, i64, ci, ci, ci, vp, vp, vp]
         L.mla_conv1_bwd_workspace_floats.argtypes = []
         L.mla_conv1_bwd_workspace_floats.restype = i64
+        L.mla_conv1_dgrad.argtypes = [vp, vp, vp, vp, ci, i64, vp, vp]
         L.mla_transpose_bf16.argtypes = [vp, i64, vp, i64, i64, i64, vp]
         L.mla_col_sum_bf16.argtypes = [vp, i64, i64, i64, vp, vp, vp]
         L.mla_resample_length.restype = i64

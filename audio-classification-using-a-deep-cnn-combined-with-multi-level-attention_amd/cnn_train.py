@@ -120,22 +120,24 @@ def fc_backward(fcs, tape, d, grads, keys, want_dx, done=None):
     return d if want_dx else None
 
 
-def features_backward(feats, tape, d, grads, keys, done=None):
+def features_backward(feats, tape, d, grads, keys, done=None, want_dx=False):
     """Backward of features_forward. d: gradient of its (N, 6, 4, 512) result in the tape's dtype. Fills grads[keys[pos] + "weight" |
     "bias"] (pos 0..5 = conv1..conv6) where present; the chain of input gradients stops at the lowest layer that has an entry, and
-    conv1's backward (which recomputes the layer) runs only if conv1 itself has one."""
+    conv1's backward (which recomputes the layer) runs only if conv1 itself has one.
+    want_dx: the chain runs down to conv1 whatever has an entry (a frozen stack launches no weight or bias gradient at all) and
+    mla_conv1_dgrad makes the gradient of the input examples, which is returned: (N, 96, 64) float32."""
     convs = feats._convs
     wanted = [k + "weight" in grads or k + "bias" in grads for k in keys]
-    if not any(wanted):
-        return
-    lowest = wanted.index(True)
+    if not any(wanted) and not want_dx:
+        return None
+    lowest = 0 if want_dx else wanted.index(True)
     g = grads.get
     n = tape["x"].shape[0]
     d = d.reshape(n, 6, 4, 512)
     for layer in range(6, 1, -1):
         pos = layer - 1
         if pos < lowest:
-            return
+            return None
         cin, cout, H, W_, pooled = GEOM[layer]
         a_in, a = tape["layers"][layer]
         key = keys[pos]
@@ -151,13 +153,18 @@ def features_backward(feats, tape, d, grads, keys, done=None):
             wd = ops.repack_dgrad(convs[layer - 1].weight.detach().contiguous(), tape["dtype"])
             d = ops.conv3x3(dz, wd, None, cin, pool=False, act=False)
     if lowest > 0:          # conv1 is not in the update set: `d` is still the gradient of the lowest trained layer's OUTPUT, not conv1's
-        return
+        return None
     key = keys[0]
-    dw = g(key + "weight") if g(key + "weight") is not None else torch.empty((64, 1, 3, 3), dtype=torch.float32, device=d.device)
-    db = g(key + "bias") if g(key + "bias") is not None else torch.empty(64, dtype=torch.float32, device=d.device)
-    ops.conv1_bwd(tape["x"], convs[0].weight.detach().contiguous(), convs[0].bias.detach(), d.contiguous(), dw, db)
+    d = d.contiguous()
+    if wanted[0]:
+        dw = g(key + "weight") if g(key + "weight") is not None else torch.empty((64, 1, 3, 3), dtype=torch.float32, device=d.device)
+        db = g(key + "bias") if g(key + "bias") is not None else torch.empty(64, dtype=torch.float32, device=d.device)
+        ops.conv1_bwd(tape["x"], convs[0].weight.detach().contiguous(), convs[0].bias.detach(), d, dw, db)
     if done:
         done(0)
+    if not want_dx:
+        return None
+    return ops.conv1_dgrad(tape["x"], convs[0].weight.detach().contiguous(), convs[0].bias.detach().contiguous(), d)
 
 
 def backward(cnn_model, tape, d_out, grads, prefix, after_layer=None):

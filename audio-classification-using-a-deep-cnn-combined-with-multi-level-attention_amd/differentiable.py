@@ -19,9 +19,13 @@ Three stages, one Function each, chained by ordinary autograd (reshapes / transp
 ``TrainStep`` (train.py of this package) stays the fast path: one flat gradient buffer, fused Adam, SyncBN and bucketed
 all-reduce. This module trades that for the reference's calling convention.
 
-Not reproduced: the gradient with respect to the input examples (``waveform_to_examples`` returns a tensor with
-``requires_grad=True``, vggish_input.py:79-80; the reference computes that gradient and never reads it) -- the conv stack's
-Function returns ``None`` for it. Train and eval mode are both differentiable (eval: BatchNorm with its running statistics).
+The gradient with respect to the input examples (``waveform_to_examples`` returns a tensor with ``requires_grad=True``,
+vggish_input.py:79-80; the reference computes that gradient and never reads it) is opt-in: with ``set_input_grad(True)`` on the
+conv stack (or on ``VGGish`` / ``CNN`` / ``Ensemble``) an input that requires grad is recorded and ``FeaturesFn`` returns its
+gradient -- the conv2..conv6 data-gradient chain, then ``mla_conv1_dgrad`` -- with no weight-gradient launch for a frozen stack;
+``Ensemble.saliency`` is built on it. While the switch is off (the default) the input's ``requires_grad`` is ignored, so plain
+inference on ``waveform_to_examples`` results keeps no tape. Train and eval mode are both differentiable (eval: BatchNorm with
+its running statistics).
 """
 
 import torch
@@ -45,12 +49,14 @@ def _wanted(ctx, first, names):
 
 
 class FeaturesFn(torch.autograd.Function):
-    """apply(feats, dtype, x, *[w0, b0, w3, b3, ...]) -> (N, 6, 4, 512) NHWC activations in `dtype`."""
+    """apply(feats, dtype, x, *[w0, b0, w3, b3, ...]) -> (N, 6, 4, 512) NHWC activations in `dtype`. The backward returns x's
+    gradient (float32, x's shape) when x requires one: VGGFeatures.forward hands x over attached only while its input_grad
+    switch is on."""
 
     @staticmethod
     def forward(ctx, feats, dtype, x, *params):
         out, tape = cnn_train.features_forward(feats, x, dtype)
-        ctx.feats, ctx.tape, ctx.device = feats, tape, out.device
+        ctx.feats, ctx.tape, ctx.device, ctx.x_shape = feats, tape, out.device, tuple(x.shape)
         ctx.names = [("%d.%s" % (i, leaf), tuple(getattr(feats[i], leaf).shape)) for i in cnn_train.CONV_IDX for leaf in ("weight", "bias")]
         return out
 
@@ -63,8 +69,10 @@ class FeaturesFn(torch.autograd.Function):
         d = d_out.contiguous()
         if d.dtype != tape["dtype"]:
             d = ops.to_bf16(d.float().contiguous()) if tape["dtype"] == torch.bfloat16 else ops.to_f32(d)
-        cnn_train.features_backward(ctx.feats, tape, d, grads, ["%d." % i for i in cnn_train.CONV_IDX])
-        return (None, None, None) + tuple(grads.get(n) for n, _ in ctx.names)
+        dx = cnn_train.features_backward(ctx.feats, tape, d, grads, ["%d." % i for i in cnn_train.CONV_IDX], want_dx=ctx.needs_input_grad[2])
+        if dx is not None:
+            dx = dx.reshape(ctx.x_shape)
+        return (None, None, dx) + tuple(grads.get(n) for n, _ in ctx.names)
 
 
 class EmbeddingsFn(torch.autograd.Function):

@@ -87,7 +87,8 @@ def check_head_shape(classes, slots, hidden):
 
 class Ensemble(nn.Module):
     def __init__(self, input_conf: str, cnn_conf: Dict[str, Union[str, int]], model_conf: List[int], device,
-                 precision: str = "f32", trunk_backward: bool = False, classes: int = K, slots: int = T, hidden: int = H):
+                 precision: str = "f32", trunk_backward: bool = False, classes: int = K, slots: int = T, hidden: int = H,
+                 input_grad: bool = False):
         check_head_shape(classes, slots, hidden)
         super().__init__()
         self.classes, self.slots, self.hidden = classes, slots, hidden
@@ -106,7 +107,7 @@ class Ensemble(nn.Module):
             raise Exception("CNN type is not valid.")
         self.input = Input(input_conf=input_conf, cnn_type=self.cnn_type, device=device)
         self.mla = MultiLevelAttention(model_conf, self.emb_input_size, classes=classes, slots=slots, hidden=hidden)
-        self.cnn = CNN(**cnn_conf, precision=precision, trunk_backward=trunk_backward)
+        self.cnn = CNN(**cnn_conf, precision=precision, trunk_backward=trunk_backward, input_grad=input_grad)
 
     def set_precision(self, precision):
         self.cnn.set_precision(precision)
@@ -114,6 +115,12 @@ class Ensemble(nn.Module):
 
     def set_trunk_backward(self, flag):
         self.cnn.set_trunk_backward(flag)
+        return self
+
+    def set_input_grad(self, flag):
+        """Switch the gradient with respect to the input examples on or off (VGGish branch; default off): while on, an input
+        of forward() that requires grad receives its gradient from loss.backward() / torch.autograd.grad. Returns self."""
+        self.cnn.set_input_grad(flag)
         return self
 
     def forward(self, x):
@@ -268,6 +275,66 @@ class Ensemble(nn.Module):
         from . import dataset
         return self._timeline("score_timeline_audiofiles", dataset.audiofiles_to_slots, (paths,), hop_slots, max_slots)
 
+    def saliency(self, x, target=None, times_input=False):
+        """Which time-frequency cells made the model say so: x (B, slots, 1, 96, 64) log-mel examples -> (scores (B, classes),
+        detached; grad float32 of x's shape = d scores[b, target_b] / d x[b], multiplied by x with times_input). target: None
+        (each bag's top class), an int, or a (B,) integer tensor. Eval mode only: the bags are then independent, so ONE backward
+        of the sum of the picked scores gives every bag's map. The gradient is taken with respect to x alone
+        (torch.autograd.grad): no parameter's .grad, no buffer and no switch of the module is changed, and a frozen conv stack
+        launches no weight gradient."""
+        if self.cnn_type != "vggish":
+            raise NotImplementedError("saliency differentiates the VGGish branch down to its log-mel examples; cnn_type 'resnet' has no "
+                                      "input gradient: its trunk's backward exists for train-mode BatchNorm only and its stem has no "
+                                      "backward-data kernel")
+        if self.training:
+            raise RuntimeError("saliency runs in eval mode only: batch statistics would couple the bags of a batch (one backward "
+                               "could not give per-bag maps) and the running statistics would move; call eval() first")
+        if x.dim() != 5 or tuple(x.shape[1:]) != (self.slots, 1) + tuple(S_VGGISH_SHAPE):
+            raise ValueError("saliency takes (B, %d, 1, %d, %d) examples, got %s" % ((self.slots,) + tuple(S_VGGISH_SHAPE) + (tuple(x.shape),)))
+        bags = x.shape[0]
+        if target is None:
+            idx = None
+        elif isinstance(target, int) and not isinstance(target, bool):
+            if not 0 <= target < self.classes:
+                raise ValueError("target %d is outside the %d classes" % (target, self.classes))
+            idx = torch.full((bags,), target, dtype=torch.long, device=x.device)
+        elif torch.is_tensor(target):
+            if target.dim() != 1 or target.shape[0] != bags or target.dtype.is_floating_point or target.dtype in (torch.bool, torch.complex64, torch.complex128):
+                raise ValueError("target must hold one class index per bag: (%d,) integers, got %s %s" % (bags, tuple(target.shape), target.dtype))
+            idx = target.to(device=x.device, dtype=torch.long)
+            if bags and bool(((idx < 0) | (idx >= self.classes)).any()):
+                raise ValueError("target holds a class outside the %d classes" % self.classes)
+        else:
+            raise ValueError("target must be None, an int or a (B,) integer tensor, got %r" % (target,))
+        feats = self.cnn.cnn_model[0] if self.just_bottlenecks else self.cnn.cnn_model.features
+        xg = x.detach().requires_grad_(True)
+        was = feats.input_grad
+        feats.input_grad = True
+        try:
+            with torch.enable_grad():
+                scores = self.forward(xg)
+                if idx is None:
+                    idx = scores.detach().argmax(dim=1)
+                grad, = torch.autograd.grad(scores.gather(1, idx.view(-1, 1)).sum(), [xg])
+        finally:
+            feats.input_grad = was
+        grad = grad.float()
+        if times_input:
+            grad = grad * x.detach().float()
+        return scores.detach(), grad
+
+    def saliency_waveforms(self, pcm, target=None, times_input=False):
+        """saliency from (B, n_samples) 16 kHz PCM on the device, one bag of `slots` examples per row: the front-end of
+        forward_waveforms (float32 examples), then saliency -> (scores, examples (B, slots, 1, 96, 64), grad): the map is plotted
+        over the examples."""
+        self._waveforms_only_vggish()
+        from . import frontend
+        ex = frontend.waveforms_to_examples(pcm, out_dtype=torch.float32)
+        assert ex.shape[0] == pcm.shape[0] * self.slots, "each waveform must yield exactly T examples"
+        ex = ex.view(pcm.shape[0], self.slots, 1, S_VGGISH_SHAPE[0], S_VGGISH_SHAPE[1])
+        scores, grad = self.saliency(ex, target, times_input)
+        return scores, ex, grad
+
     def _librosa_bags(self, what, frames_fn, source, overlap):
         """The VGGish branch on the reference's librosa dataset path (load_hdf5(cnn_type="vggish", use_librosa=True), mnemonic
         vggish_10_s): HTK mel-dB bags written in the CNN's compute dtype, then the CNN and the head as _native_bags runs them."""
@@ -415,7 +482,8 @@ class Input(nn.Module):
 
 class CNN(nn.Module):
     def __init__(self, cnn_type="vggish", num_classes=10, use_pretrained=True, just_bottlenecks=False,
-                 cnn_trainable=False, first_cnn_layer_trainable=False, in_channels=3, precision="f32", trunk_backward=False):
+                 cnn_trainable=False, first_cnn_layer_trainable=False, in_channels=3, precision="f32", trunk_backward=False,
+                 input_grad=False):
         super().__init__()
         self.precision = precision
         # cnn_type="resnet": gradients into the trunk (cnn_trainable / first_cnn_layer_trainable, model.py:131-136) run on the
@@ -451,6 +519,7 @@ class CNN(nn.Module):
             raise Exception("Invalid CNN model name specified.")
         self.cnn_type = cnn_type
         self.just_bottlenecks = just_bottlenecks
+        self.set_input_grad(input_grad)
 
     def set_precision(self, precision):
         if self.cnn_type == "resnet" and precision not in ("f32", "bf16"):
@@ -465,6 +534,18 @@ class CNN(nn.Module):
         """Turn the HIP backward of the ResNet-50 trunk on or off (models built by the reference's own constructor call or by
         load_model); returns self. No effect for cnn_type="vggish", whose finetuning always runs."""
         self.trunk_backward = bool(flag)
+        return self
+
+    def set_input_grad(self, flag):
+        """Switch the gradient with respect to the input examples on or off (VGGFeatures.set_input_grad; default off); returns
+        self. cnn_type="resnet" has none."""
+        if self.cnn_type == "resnet":
+            if flag:
+                raise NotImplementedError("cnn_type 'resnet' has no input gradient: the trunk's backward exists for train-mode "
+                                          "BatchNorm only and the stem has no backward-data kernel")
+            return self
+        feats = self.cnn_model[0] if self.just_bottlenecks else self.cnn_model.features
+        feats.set_input_grad(flag)
         return self
 
     def forward(self, x):

@@ -781,6 +781,18 @@ def conv1_bwd(x, w, b, d_pooled, dw, db):
     _lib.check(_timed("conv1_bwd", fn, _p(x), _p(w), _p(b), _p(d_pooled), n, _p(ws), _p(dw), _p(db), _lib.stream_ptr()))
 
 
+def conv1_dgrad(x, w, b, d_pooled):
+    """Gradient of conv1 + ReLU + max-pool with respect to its input: x (n, 96, 64) f32, d_pooled (n, 48, 32, 64) f32 or bf16 ->
+    dx (n, 96, 64) f32 (mla_conv1_dgrad: the layer is recomputed, every element of dx is written once)."""
+    _chk(x, torch.float32); _chk(w, torch.float32); _chk(b, torch.float32); _chk(d_pooled)
+    n = x.shape[0]
+    assert tuple(x.shape) == (n, 96, 64) and tuple(d_pooled.shape) == (n, 48, 32, 64) and tuple(w.shape) == (64, 1, 3, 3) and b.numel() == 64
+    dx = torch.empty((n, 96, 64), dtype=torch.float32, device=x.device)
+    _lib.check(_timed("conv1_dgrad", _lib.lib().mla_conv1_dgrad, _p(x), _p(w), _p(b), _p(d_pooled), DT[d_pooled.dtype], n, _p(dx),
+                      _lib.stream_ptr()))
+    return dx
+
+
 # ---- ResNet-50 trunk (cnn_type="resnet"): NHWC activations in f32 / bf16, see include/mla_hip.h "ResNet-50 v1.5 trunk" ----
 
 def rn_repack(w, dtype):

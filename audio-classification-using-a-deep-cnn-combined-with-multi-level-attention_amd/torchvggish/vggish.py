@@ -102,6 +102,7 @@ class VGGFeatures(nn.Sequential):
     memory, so the reference's transpose/contiguous flatten (vggish.py:26-29) costs nothing."""
 
     precision = "f32"
+    input_grad = False
 
     def __init__(self, *layers):
         super().__init__(*layers)
@@ -145,12 +146,20 @@ class VGGFeatures(nn.Sequential):
         from .. import differentiable as D
         if isinstance(x, PcmInput):
             return self.forward_nhwc(x, _DTYPES[self.precision]).permute(0, 3, 1, 2)
-        if D.wants_grad(self):
+        # input_grad on: an input that requires grad is recorded too and receives its gradient (mla_conv1_dgrad); off, its
+        # requires_grad is ignored (every waveform_to_examples result has it set: plain inference must not keep a tape)
+        record_x = self.input_grad and torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad
+        if record_x or D.wants_grad(self):
             # a conv parameter requires grad and autograd is recording (the reference's loop, train.py:124-138, after
             # cnn_trainable=True / set_requires_grad): training forward with a tape, HIP backward kernels behind loss.backward()
             params = [t for i in (0, 3, 6, 8, 11, 13) for t in (self[i].weight, self[i].bias)]
-            return D.FeaturesFn.apply(self, D.grad_precision(self.precision), x, *params).permute(0, 3, 1, 2)
+            return D.FeaturesFn.apply(self, D.grad_precision(self.precision), x if record_x else x.detach(), *params).permute(0, 3, 1, 2)
         return self.forward_nhwc(x, _DTYPES[self.precision]).permute(0, 3, 1, 2)
+
+    def set_input_grad(self, flag):
+        """Switch the gradient with respect to the input examples on or off (default off); returns self."""
+        self.input_grad = bool(flag)
+        return self
 
 
 class Linear(nn.Module):
@@ -232,6 +241,11 @@ class VGG(nn.Module):
         assert precision in _DTYPES
         self.features.precision = precision
         self.embeddings.precision = precision
+        return self
+
+    def set_input_grad(self, flag):
+        """Gradient with respect to the input examples (VGGFeatures.set_input_grad); returns self."""
+        self.features.set_input_grad(flag)
         return self
 
     def forward(self, x):

@@ -482,6 +482,13 @@ int mla_pool_bwd_codes_bf16(const void* codes_u8, const void* d_pooled_bf16, voi
 int mla_conv1_bwd_bf16(const float* x, const float* w, const float* bias, const void* d_pooled_bf16, int64_t n, float* workspace,
                        float* dw, float* db, mla_stream_t stream);
 int64_t mla_conv1_bwd_workspace_floats(void);
+/* Gradient of features[0..2] (Conv2d(1,64)+ReLU+MaxPool) with respect to its INPUT: x (n,96,64) f32, w (64,1,3,3), bias (64),
+ * d_pooled (n,48,32,64) in d_dtype MLA_F32 or MLA_BF16 (16-byte aligned) -> dx (n,96,64) f32, every element written once (dx need
+ * not be zeroed). The layer is recomputed under mla_conv1_bwd's rules: bias after the pool, the first maximum in scan order takes
+ * the gradient, nothing flows where the pooled output is <= 0; with MLA_BF16, x and w are rounded to bf16 for the recompute as the
+ * bf16 forward rounds them. Deterministic (no atomics, the bits do not depend on n), no workspace. n == 0 is a no-op. */
+int mla_conv1_dgrad(const float* x, const float* w, const float* bias, const void* d_pooled, int d_dtype, int64_t n, float* dx,
+                    mla_stream_t stream);
 /* (rows, cols) bf16 -> (cols, ld_out >= rows) bf16, the padding columns zeroed: K-contiguous operands of the Linear backward */
 int mla_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int64_t cols, mla_stream_t stream);
 /* column sums of a bf16 (rows, cols) matrix -> f32 (bias gradient of a Linear); workspace: 64 * cols doubles */
