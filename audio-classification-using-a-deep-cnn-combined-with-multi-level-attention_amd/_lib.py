@@ -183,6 +183,8 @@ def lib():
         L.mla_rn_bn_bwd_apply.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, cf, vp, vp, vp, vp, ci, vp]
         L.mla_rn_maxpool_bwd.argtypes = [vp, vp, i64, i64, i64, i64, vp, ci, vp]
         L.mla_rn_avgpool_bwd.argtypes = [vp, i64, i64, i64, vp, ci, vp]
+        L.mla_rn_act_bwd.argtypes = [vp, vp, vp, i64, i64, vp, vp, ci, vp]
+        L.mla_rn_stem_dgrad.argtypes = [vp, i64, vp, vp, vp, ci, vp, ci, vp]
         _lib = L
     return _lib
 

@@ -11,9 +11,12 @@
 //   rn_bn_bwd_*              BatchNorm2d train-mode backward (+ fused ReLU mask, + residual-path gradient); rn_bn_bwd_sums_kernel
 //                            / rn_bn_bwd_coef_kernel split it around an all-reduce of [sum g, sum g xhat, rows] (SyncBN
 //                            across data-parallel ranks: the batch means of the global batch)
+//   rn_act_bwd_kernel        backward of the eval-mode epilogue (BatchNorm folded to scale / shift [+ residual] [ReLU]): mask and scale
+//   rn_stem_dgrad_kernel     stem data gradient down to the raw planes, the Input normalisation folded in (rn_stem_dgrad_core.h)
 //   rn_maxpool_bwd_kernel    MaxPool2d(3, 2, 1) backward as a gather (first maximum in torch's scan order)
 //   rn_avgpool_bwd_kernel    AdaptiveAvgPool2d(1) backward: dY / HW broadcast
 #include "rn_core.h"
+#include "rn_stem_dgrad_core.h"
 
 namespace {
 
@@ -469,6 +472,127 @@ __global__ __launch_bounds__(256) void rn_avgpool_bwd_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward of the eval-mode epilogue y = [relu](conv * scale + shift [+ residual]) over NHWC rows: the BatchNorm is a
+// per-channel constant there, so its backward is a mask and a scale. g = dy [* (y > 0)] (NaN in y gives 0, as torch's
+// threshold_backward); dpre = g * scale[c], the gradient of the conv output; dres (or null) = g, the residual's gradient.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void rn_act_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, const float* __restrict__ scale,
+                                                         int64_t n8, int C, T* __restrict__ dpre, T* __restrict__ dres) {
+    for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n8; i += int64_t(gridDim.x) * blockDim.x) {
+        const int64_t off = i * 8;
+        const int c = int(off % C);
+        float g[8], v[8];
+        load8<T>(dy + off, g);
+        if (y) {
+            float m[8];
+            load8<T>(y + off, m);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) g[k] = m[k] > 0.f ? g[k] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = g[k] * scale[c + k];
+        store8<T>(dpre + off, v);
+        if (dres) store8<T>(dres + off, g);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// stem data gradient: dy (n, 112, 112, 64) [behind the eval epilogue: y, scale] -> dx (n, 224, 224) f32 of the RAW planes, the
+// Input normalisation and channel configuration folded into the taps as the forward folds them. Persistent workgroups, item =
+// (image, 8 input rows); tiling, tap map and the gather are rn_stem_dgrad_core.h, which csrc/rn_stem_dgrad_hostsim.cpp runs on
+// the host. Every dx element is summed by one lane in a fixed order and stored once: no atomics, no workspace.
+// ------------------------------------------------------------------------------------------------
+namespace sd = rn_stem_dgrad;
+static_assert(sd::kImg == kImg && sd::kOut == kStemOut && sd::kC == kStemC && sd::kInv[0] == kNormInv[0] && sd::kInv[1] == kNormInv[1] &&
+                  sd::kInv[2] == kNormInv[2],
+              "rn_stem_dgrad_core.h restates the stem geometry of rn_core.h");
+
+template <typename T>
+__global__ __launch_bounds__(sd::kThreads) void rn_stem_dgrad_kernel(const T* __restrict__ dy, const T* __restrict__ y,
+                                                                     const float* __restrict__ scale, const float* __restrict__ w,
+                                                                     int single, int64_t n_items, float* __restrict__ dx) {
+    __shared__ __attribute__((aligned(16))) float sA[sd::kTaps * sd::kC];
+    __shared__ __attribute__((aligned(16))) float sG[sd::kSlots * sd::kOut * sd::kGroup];
+    const int t = threadIdx.x;
+    for (int i = t; i < sd::kC * sd::kTaps; i += sd::kThreads) {
+        const int o = i / sd::kTaps, tap = i - o * sd::kTaps;
+        sA[sd::a_index(o, tap)] = sd::fold_a(w[sd::w_index(o, 0, tap)], w[sd::w_index(o, 1, tap)], w[sd::w_index(o, 2, tap)], single);
+    }                                                            // made visible by the first pass's barrier
+
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int64_t n = item / sd::kTiles;
+        const int tile = int(item % sd::kTiles);
+        float acc[sd::kPixPerLane];
+#pragma unroll
+        for (int j = 0; j < sd::kPixPerLane; ++j) acc[j] = 0.f;
+
+        for (int grp = 0; grp < sd::kGroups; ++grp) {
+            // ---- stage g of the tile's 7 output rows, 16 channels
+            for (int i = t; i < sd::kStageLoads; i += sd::kThreads) {
+                int r, ox, c8;
+                sd::stage_of(i, &r, &ox, &c8);
+                const int oy = sd::slot_row(tile, r);
+                float g[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) g[k] = 0.f;
+                if (sd::row_live(oy)) {
+                    const int c = grp * sd::kGroup + c8;
+                    const int64_t off = sd::g_index(n, oy, ox) + c;
+                    load8<T>(dy + off, g);
+                    if (y) {
+                        float m[8];
+                        load8<T>(y + off, m);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) g[k] = sd::route(g[k], m[k], scale[c + k], true);
+                    }
+                }
+                float* dst = sG + sd::s_index(r, ox) + c8;
+                *reinterpret_cast<f32x4*>(dst) = f32x4{g[0], g[1], g[2], g[3]};
+                *reinterpret_cast<f32x4*>(dst + 4) = f32x4{g[4], g[5], g[6], g[7]};
+            }
+            __syncthreads();
+            // ---- gather: each pixel from its 3 or 4 x 3 or 4 output positions
+#pragma unroll
+            for (int j = 0; j < sd::kPixPerLane; ++j) {
+                int row, ix, ky0, nty, fy, kx0, ntx, fx;
+                sd::pixel_of(t + sd::kThreads * j, &row, &ix);
+                sd::axis_taps(row, &ky0, &nty, &fy);
+                sd::axis_taps(ix, &kx0, &ntx, &fx);
+                for (int jy = 0; jy < nty; ++jy) {
+                    const int r = fy - jy + 1;                   // slot of output row 4 tile + fy - jy
+                    if (!sd::row_live(sd::slot_row(tile, r))) continue;
+                    for (int jx = 0; jx < ntx; ++jx) {
+                        const int ox = fx - jx;
+                        if (ox < 0 || ox >= sd::kOut) continue;
+                        const int tap = (ky0 + 2 * jy) * 7 + kx0 + 2 * jx;
+                        float gv[sd::kGroup], av[sd::kGroup];
+#pragma unroll
+                        for (int k = 0; k < sd::kGroup / 4; ++k) {
+                            const f32x4 q = *reinterpret_cast<const f32x4*>(sG + sd::s_index(r, ox) + 4 * k);
+                            const f32x4 a = *reinterpret_cast<const f32x4*>(sA + sd::a_index(grp * sd::kGroup, tap) + 4 * k);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                gv[4 * k + e] = q[e];
+                                av[4 * k + e] = a[e];
+                            }
+                        }
+                        acc[j] = sd::gather(acc[j], gv, av);
+                    }
+                }
+            }
+            __syncthreads();                                     // the next pass (or item) overwrites sG
+        }
+#pragma unroll
+        for (int j = 0; j < sd::kPixPerLane; ++j) {
+            int row, ix;
+            sd::pixel_of(t + sd::kThreads * j, &row, &ix);
+            dx[(n * sd::kImg + tile * sd::kTileRows + row) * sd::kImg + ix] = acc[j];
+        }
+    }
+}
+
 // wgrad split count: enough workgroups to fill the GPU, a function of the shape only (never of the data or the launch)
 struct WgradPlan {
     int64_t kb_per;
@@ -733,5 +857,45 @@ extern "C" int mla_rn_avgpool_bwd(const float* d, int64_t n, int64_t hw, int64_t
         hipLaunchKernelGGL(rn_avgpool_bwd_kernel<T>, dim3(g), dim3(256), 0, s, d, n, int(hw), int(channels), static_cast<T*>(dx));
     });
     MLA_LAUNCH_OK("rn_avgpool_bwd_kernel");
+    return MLA_OK;
+}
+
+extern "C" int mla_rn_act_bwd(const void* dy, const void* y, const float* scale, int64_t rows, int64_t channels, void* dpre, void* dres, int dtype,
+                              mla_stream_t stream) {
+    MLA_REQUIRE(rows >= 0 && channels > 0 && channels % 8 == 0 && channels <= 65536, MLA_E_SHAPE,
+                "rn_act_bwd rows %lld channels %lld (channels: multiple of 8)", (long long)rows, (long long)channels);
+    MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_act_bwd dtype %d", dtype);
+    if (rows == 0) return MLA_OK;
+    MLA_REQUIRE(dy && scale && dpre, MLA_E_ARG, "null rn_act_bwd buffers");
+    MLA_REQUIRE(mla::aligned(dy, 16) && mla::aligned(y, 16) && mla::aligned(dpre, 16) && mla::aligned(dres, 16), MLA_E_ARG,
+                "rn_act_bwd buffers must be 16-byte aligned");
+    MLA_REQUIRE(rows <= (int64_t(1) << 40) / channels, MLA_E_SHAPE, "rn_act_bwd: %lld rows are too many for one launch", (long long)rows);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t n8 = rows * channels / 8;
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_act_bwd_kernel<T>, dim3(grid_for(n8)), dim3(256), 0, s, static_cast<const T*>(dy), static_cast<const T*>(y), scale,
+                           n8, int(channels), static_cast<T*>(dpre), static_cast<T*>(dres));
+    });
+    MLA_LAUNCH_OK("rn_act_bwd_kernel");
+    return MLA_OK;
+}
+
+extern "C" int mla_rn_stem_dgrad(const void* dy, int64_t n, const void* y, const float* scale, const float* w, int single, float* dx, int dtype,
+                                 mla_stream_t stream) {
+    MLA_REQUIRE(n >= 0 && (single == 0 || single == 1), MLA_E_ARG, "bad rn_stem_dgrad arguments: n = %lld, single = %d", (long long)n, single);
+    MLA_REQUIRE(dtype == MLA_F32 || dtype == MLA_BF16, MLA_E_DTYPE, "rn_stem_dgrad dtype %d (f32 or bf16)", dtype);
+    MLA_REQUIRE((y == nullptr) == (scale == nullptr), MLA_E_ARG, "rn_stem_dgrad: y and scale come together (both, or neither)");
+    if (n == 0) return MLA_OK;
+    MLA_REQUIRE(dy && w && dx, MLA_E_ARG, "bad rn_stem_dgrad arguments: null pointer");
+    MLA_REQUIRE(n <= (int64_t(1) << 32), MLA_E_SHAPE, "rn_stem_dgrad: %lld images are too many for one launch", (long long)n);
+    MLA_REQUIRE(mla::aligned(dy, 16) && mla::aligned(y, 16), MLA_E_ARG, "rn_stem_dgrad: dy and y must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rn_dispatch(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(rn_stem_dgrad_kernel<T>, dim3(sd::grid_of(n)), dim3(sd::kThreads), 0, s, static_cast<const T*>(dy),
+                           static_cast<const T*>(y), scale, w, single, sd::items_of(n), dx);
+    });
+    MLA_LAUNCH_OK("rn_stem_dgrad_kernel");
     return MLA_OK;
 }

@@ -275,6 +275,24 @@ class Ensemble(nn.Module):
         from . import dataset
         return self._timeline("score_timeline_audiofiles", dataset.audiofiles_to_slots, (paths,), hop_slots, max_slots)
 
+    def _saliency_target(self, target, bags, device):
+        """The `target` argument of the saliency entries -> None (each bag's top class, known after the forward) or (bags,) int64
+        class indices on `device`."""
+        if target is None:
+            return None
+        if isinstance(target, int) and not isinstance(target, bool):
+            if not 0 <= target < self.classes:
+                raise ValueError("target %d is outside the %d classes" % (target, self.classes))
+            return torch.full((bags,), target, dtype=torch.long, device=device)
+        if torch.is_tensor(target):
+            if target.dim() != 1 or target.shape[0] != bags or target.dtype.is_floating_point or target.dtype in (torch.bool, torch.complex64, torch.complex128):
+                raise ValueError("target must hold one class index per bag: (%d,) integers, got %s %s" % (bags, tuple(target.shape), target.dtype))
+            idx = target.to(device=device, dtype=torch.long)
+            if bags and bool(((idx < 0) | (idx >= self.classes)).any()):
+                raise ValueError("target holds a class outside the %d classes" % self.classes)
+            return idx
+        raise ValueError("target must be None, an int or a (B,) integer tensor, got %r" % (target,))
+
     def saliency(self, x, target=None, times_input=False):
         """Which time-frequency cells made the model say so: x (B, slots, 1, 96, 64) log-mel examples -> (scores (B, classes),
         detached; grad float32 of x's shape = d scores[b, target_b] / d x[b], multiplied by x with times_input). target: None
@@ -284,28 +302,15 @@ class Ensemble(nn.Module):
         launches no weight gradient."""
         if self.cnn_type != "vggish":
             raise NotImplementedError("saliency differentiates the VGGish branch down to its log-mel examples; cnn_type 'resnet' has no "
-                                      "input gradient: its trunk's backward exists for train-mode BatchNorm only and its stem has no "
-                                      "backward-data kernel")
+                                      "input gradient behind autograd: its trunk's backward there exists for train-mode BatchNorm only "
+                                      "and its stem has no backward-data step in it; the eval-mode maps of the ResNet branch are "
+                                      "saliency_images() / saliency_clips()")
         if self.training:
             raise RuntimeError("saliency runs in eval mode only: batch statistics would couple the bags of a batch (one backward "
                                "could not give per-bag maps) and the running statistics would move; call eval() first")
         if x.dim() != 5 or tuple(x.shape[1:]) != (self.slots, 1) + tuple(S_VGGISH_SHAPE):
             raise ValueError("saliency takes (B, %d, 1, %d, %d) examples, got %s" % ((self.slots,) + tuple(S_VGGISH_SHAPE) + (tuple(x.shape),)))
-        bags = x.shape[0]
-        if target is None:
-            idx = None
-        elif isinstance(target, int) and not isinstance(target, bool):
-            if not 0 <= target < self.classes:
-                raise ValueError("target %d is outside the %d classes" % (target, self.classes))
-            idx = torch.full((bags,), target, dtype=torch.long, device=x.device)
-        elif torch.is_tensor(target):
-            if target.dim() != 1 or target.shape[0] != bags or target.dtype.is_floating_point or target.dtype in (torch.bool, torch.complex64, torch.complex128):
-                raise ValueError("target must hold one class index per bag: (%d,) integers, got %s %s" % (bags, tuple(target.shape), target.dtype))
-            idx = target.to(device=x.device, dtype=torch.long)
-            if bags and bool(((idx < 0) | (idx >= self.classes)).any()):
-                raise ValueError("target holds a class outside the %d classes" % self.classes)
-        else:
-            raise ValueError("target must be None, an int or a (B,) integer tensor, got %r" % (target,))
+        idx = self._saliency_target(target, x.shape[0], x.device)
         feats = self.cnn.cnn_model[0] if self.just_bottlenecks else self.cnn.cnn_model.features
         xg = x.detach().requires_grad_(True)
         was = feats.input_grad
@@ -334,6 +339,52 @@ class Ensemble(nn.Module):
         ex = ex.view(pcm.shape[0], self.slots, 1, S_VGGISH_SHAPE[0], S_VGGISH_SHAPE[1])
         scores, grad = self.saliency(ex, target, times_input)
         return scores, ex, grad
+
+    def saliency_images(self, x, target=None, times_input=False):
+        """saliency for the ResNet branch: x (B, slots, 1, 224, 224) spectrogram images -> (scores (B, classes), detached; grad
+        float32 of x's shape = d scores[b, target_b] / d x[b], multiplied by x with times_input). target as in saliency(). Eval mode
+        only, for saliency()'s reason. The trunk runs its eval-mode forward with a tape and is walked back by hand
+        (resnet.trunk_input_backward: BatchNorm as the folded per-channel constant it is in eval mode, the stem's backward-data
+        kernel last); only the head (and the fc of just_bottlenecks=False) sits behind autograd, differentiated with respect to the
+        features alone. No parameter's .grad, no buffer and no switch of the module is changed, whatever requires grad; no weight
+        gradient is launched. The tape holds every activation of the batch: the caller splits large batches."""
+        if self.cnn_type != "resnet":
+            raise NotImplementedError("saliency_images differentiates the ResNet branch down to its 224 x 224 images; cnn_type 'vggish' "
+                                      "takes log-mel examples through saliency(), or 16 kHz PCM through saliency_waveforms()")
+        if self.training:
+            raise RuntimeError("saliency_images runs in eval mode only: batch statistics would couple the bags of a batch (one backward "
+                               "could not give per-bag maps) and the running statistics would move; call eval() first")
+        if x.dim() != 5 or tuple(x.shape[1:]) != (self.slots, 1) + tuple(S_RESNET_SHAPE):
+            raise ValueError("saliency_images takes (B, %d, 1, %d, %d) images, got %s" % ((self.slots,) + tuple(S_RESNET_SHAPE) + (tuple(x.shape),)))
+        idx = self._saliency_target(target, x.shape[0], x.device)
+        cnn_model = self.cnn.cnn_model
+        tape = {}
+        with torch.no_grad():
+            feats = resnet.trunk_forward(cnn_model, self.input(x), self.cnn.precision, False, self.cnn._rn_cache, tape=tape)
+        leaf = feats.detach().requires_grad_(True)
+        with torch.enable_grad():
+            emb = leaf if self.just_bottlenecks else differentiable.FcFn.apply(leaf, cnn_model.fc.weight, cnn_model.fc.bias)
+            scores = self.mla(emb.reshape(-1, self.slots, self.emb_input_size))
+            if idx is None:
+                idx = scores.detach().argmax(dim=1)
+            d_feats, = torch.autograd.grad(scores.gather(1, idx.view(-1, 1)).sum(), [leaf])
+        grad = resnet.trunk_input_backward(cnn_model, tape, d_feats.float().contiguous()).view(x.shape)
+        if times_input:
+            grad = grad * x.detach().float()
+        return scores.detach(), grad
+
+    def saliency_clips(self, pcm, target=None, times_input=False, overlap=True):
+        """saliency_images from (B, SAMPLES_NUM_RESNET) float32 PCM at 22 050 Hz on the device: the mel-dB images of
+        forward_clips (dataset.clips_to_images), then saliency_images -> (scores, images (B, T, 1, 224, 224), grad): the map is
+        plotted over the images."""
+        if self.cnn_type != "resnet":
+            raise NotImplementedError("saliency_clips feeds the ResNet branch's mel-dB images; cnn_type 'vggish' takes log-mel examples "
+                                      "through saliency(), or 16 kHz PCM through saliency_waveforms()")
+        self._ten_window_bags("saliency_clips")
+        from . import dataset
+        images = dataset.clips_to_images(pcm, overlap)
+        scores, grad = self.saliency_images(images, target, times_input)
+        return scores, images, grad
 
     def _librosa_bags(self, what, frames_fn, source, overlap):
         """The VGGish branch on the reference's librosa dataset path (load_hdf5(cnn_type="vggish", use_librosa=True), mnemonic
@@ -538,11 +589,12 @@ class CNN(nn.Module):
 
     def set_input_grad(self, flag):
         """Switch the gradient with respect to the input examples on or off (VGGFeatures.set_input_grad; default off); returns
-        self. cnn_type="resnet" has none."""
+        self. cnn_type="resnet" has none behind autograd (Ensemble.saliency_images walks its eval-mode trunk by hand)."""
         if self.cnn_type == "resnet":
             if flag:
-                raise NotImplementedError("cnn_type 'resnet' has no input gradient: the trunk's backward exists for train-mode "
-                                          "BatchNorm only and the stem has no backward-data kernel")
+                raise NotImplementedError("cnn_type 'resnet' has no input gradient behind autograd: the trunk's backward there exists "
+                                          "for train-mode BatchNorm only and the stem has no backward-data step in it; eval-mode maps: "
+                                          "Ensemble.saliency_images()")
             return self
         feats = self.cnn_model[0] if self.just_bottlenecks else self.cnn_model.features
         feats.set_input_grad(flag)

@@ -1033,3 +1033,38 @@ def rn_avgpool_bwd(d, shape, dtype):
     dx = torch.empty((n, H, W_, C), dtype=dtype, device=d.device)
     _lib.check(_timed("rn_avgpool_bwd", _lib.lib().mla_rn_avgpool_bwd, _p(d), n, H * W_, C, _p(dx), DT[dtype], _lib.stream_ptr()))
     return dx
+
+
+# ---- input gradient of the eval-mode trunk (saliency maps): the BatchNorm is a folded per-channel constant there ----
+
+def rn_act_bwd(dy, scale, y=None, want_dres=False):
+    """Backward of the eval epilogue y = [relu](conv * scale + shift [+ residual]): dy, y (the kept output; None = no ReLU) NHWC in
+    one dtype, scale (C,) f32 -> (dpre = dy (y > 0) scale, dres = dy (y > 0) when want_dres, else None)."""
+    _chk(dy); _chk(scale, torch.float32)
+    if y is not None:
+        _chk(y, dy.dtype)
+        assert y.shape == dy.shape, (y.shape, dy.shape)
+    C = dy.shape[-1]
+    assert scale.numel() == C, (scale.shape, C)
+    dpre = torch.empty_like(dy)
+    dres = torch.empty_like(dy) if want_dres else None
+    _lib.check(_timed("rn_act_bwd", _lib.lib().mla_rn_act_bwd, _p(dy), _p(y), _p(scale), dy.numel() // C, C, _p(dpre), _p(dres), DT[dy.dtype],
+                      _lib.stream_ptr()))
+    return dpre, dres
+
+
+def rn_stem_dgrad(dy, w, single, y=None, scale=None):
+    """dy (N, 112, 112, 64) f32 or bf16, stem weight (64, 3, 7, 7) f32 -> dx (N, 224, 224) f32, the gradient of the RAW planes
+    Input receives (repeat / single and the normalisation folded in). y, scale: the stem's fused eval output and BatchNorm scale
+    (both or neither); then dy is first masked by y > 0 and scaled."""
+    _chk(dy); _chk(w, torch.float32)
+    n = dy.shape[0]
+    assert tuple(dy.shape) == (n, 112, 112, 64) and tuple(w.shape) == (64, 3, 7, 7), (dy.shape, w.shape)
+    assert (y is None) == (scale is None), "y and scale come together"
+    if y is not None:
+        _chk(y, dy.dtype); _chk(scale, torch.float32)
+        assert y.shape == dy.shape and scale.numel() == 64, (y.shape, scale.shape)
+    dx = torch.empty((n, 224, 224), dtype=torch.float32, device=dy.device)
+    _lib.check(_timed("rn_stem_dgrad", _lib.lib().mla_rn_stem_dgrad, _p(dy), n, _p(y), _p(scale), _p(w), int(single), _p(dx), DT[dy.dtype],
+                      _lib.stream_ptr()))
+    return dx

@@ -174,7 +174,9 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None, tape=None
     data-parallel training step; in train mode its SyncBN setting decides whether the 53 BatchNorm2d statistics are those of
     the global batch (one all-reduce per layer) or of this rank's shard. tape: a dict that receives what ``trunk_backward``
     needs (train mode only): every BatchNorm's input (the raw conv output), batch statistics and output, and every block's
-    input; the BatchNorm outputs then go to new tensors instead of overwriting their inputs. Same results either way."""
+    input; the BatchNorm outputs then go to new tensors instead of overwriting their inputs. Same results either way. In eval
+    mode a tape receives what ``trunk_input_backward`` needs instead: the output of every fused conv (the stem's included), the
+    eval scale of every BatchNorm and every block's input; the kernels launched and the features are those of the untaped call."""
     if not isinstance(x, StemInput):
         raise TypeError("the ResNet trunk takes the output of model.Input (raw 224 x 224 planes)")
     if precision not in _DTYPES:
@@ -185,7 +187,6 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None, tape=None
     planes = x.planes
     assert planes.dim() == 3 and tuple(planes.shape[1:]) == S_RESNET_SHAPE
     _check_frozen(cnn_model)
-    assert tape is None or training, "the trunk backward differentiates the train-mode forward"
     dtype = _DTYPES[precision]
     blocks = [b for layer in layers for b in layer]
     convs = [c for b in blocks for c in ([b.conv1, b.conv2, b.conv3] + ([b.downsample[0]] if b.downsample is not None else []))]
@@ -231,13 +232,69 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None, tape=None
     tensors = [t for n in bns for t in (n.weight, n.bias, n.running_mean, n.running_var)]
     coef = cache["bn"].get(tensors, None, lambda: {id(n): ops.rn_bn_eval_coeffs(n) for n in bns})
     h = ops.rn_stem(planes, x.single, w1, dtype, *coef[id(bn1)], relu=True)
+    if tape is not None:                          # eval tape: the fused outputs are new tensors anyway, the tape only keeps them
+        tape.update(eval=True, dtype=dtype, planes=planes, single=x.single, stem=h, y={}, block_in={},
+                    scale={id(n): coef[id(n)][0] for n in bns})
     h = ops.rn_maxpool(h)
     for b in blocks:
-        o = ops.rn_conv(h, packed[id(b.conv1)], 1, *coef[id(b.bn1)], relu=True)
-        o = ops.rn_conv(o, packed[id(b.conv2)], b.stride, *coef[id(b.bn2)], relu=True)
+        a1 = ops.rn_conv(h, packed[id(b.conv1)], 1, *coef[id(b.bn1)], relu=True)
+        a2 = ops.rn_conv(a1, packed[id(b.conv2)], b.stride, *coef[id(b.bn2)], relu=True)
         idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride, *coef[id(b.downsample[1])]) if b.downsample is not None else h
-        h = ops.rn_conv(o, packed[id(b.conv3)], 1, *coef[id(b.bn3)], residual=idn, relu=True)
+        out = ops.rn_conv(a2, packed[id(b.conv3)], 1, *coef[id(b.bn3)], residual=idn, relu=True)
+        if tape is not None:
+            tape["block_in"][id(b)] = h
+            tape["y"].update({id(b.bn1): a1, id(b.bn2): a2, id(b.bn3): out})
+        h = out
+    if tape is not None:
+        tape["last_shape"] = tuple(h.shape)
     return ops.rn_avgpool(h)
+
+
+def trunk_input_backward(cnn_model, tape, d_feats):
+    """Backward of the EVAL-mode trunk forward recorded in `tape` down to the input: d_feats (N, 2048) f32, the gradient of the
+    features -> (N, 224, 224) f32, the gradient of the raw planes ``model.Input`` received. Every BatchNorm is a per-channel
+    scale and shift folded into its conv's epilogue there, so its backward is ``ops.rn_act_bwd`` (the ReLU mask from the kept
+    output, times the scale): avg-pool backward, the blocks in reverse (act_bwd then the conv's data gradient, the skip
+    gradient added by the dgrad's residual input), max-pool backward, ``ops.rn_stem_dgrad`` behind the stem's own epilogue. No
+    weight gradient and no batch-statistics backward is launched. Runs under no_grad whatever the parameters' requires_grad
+    flags say; no parameter's .grad and no buffer is touched. The tape is consumed (its tensors are released as the walk passes
+    them)."""
+    assert tape.get("eval"), "trunk_input_backward differentiates the eval-mode forward (trunk_forward(training=False, tape=...))"
+    conv1, bn1, layers, _ = parts(cnn_model)
+    blocks = [b for layer in layers for b in layer]
+    dtype, ys, scale = tape["dtype"], tape["y"], tape["scale"]
+    with torch.no_grad():
+        def dgrad(dy, conv, in_hw, residual=None):
+            return ops.rn_conv_dgrad(dy, ops.rn_repack_dgrad(conv.weight.detach().contiguous(), dtype), conv.stride[0], in_hw, residual)
+
+        d = ops.rn_avgpool_bwd(d_feats, tape["last_shape"], dtype)
+        for b in reversed(blocks):
+            h_in = tape["block_in"].pop(id(b))
+            a1, a2 = ys.pop(id(b.bn1)), ys.pop(id(b.bn2))
+            do3, g3 = ops.rn_act_bwd(d, scale[id(b.bn3)], y=ys.pop(id(b.bn3)), want_dres=True)
+            da2 = dgrad(do3, b.conv3, a2.shape[1:3])
+            del do3
+            do2, _ = ops.rn_act_bwd(da2, scale[id(b.bn2)], y=a2)
+            del da2, a2
+            da1 = dgrad(do2, b.conv2, a1.shape[1:3])
+            del do2
+            do1, _ = ops.rn_act_bwd(da1, scale[id(b.bn1)], y=a1)
+            del da1, a1
+            if b.downsample is not None:
+                dds, _ = ops.rn_act_bwd(g3, scale[id(b.downsample[1])])
+                skip = dgrad(dds, b.downsample[0], h_in.shape[1:3])
+                del dds
+            else:
+                skip = g3
+            del g3
+            d = dgrad(do1, b.conv1, h_in.shape[1:3], residual=skip)
+            del do1, skip, h_in
+        a0 = tape["stem"]
+        da0 = ops.rn_maxpool_bwd(a0, d)                           # d: gradient of the maxpool output
+        del d
+        dx = ops.rn_stem_dgrad(da0, conv1.weight.detach().contiguous(), tape["single"], y=a0, scale=scale[id(bn1)])
+    tape.clear()
+    return dx
 
 
 def trunk_backward(cnn_model, tape, d_feats, grads, dist=None):

@@ -722,6 +722,25 @@ int mla_rn_maxpool_bwd(const void* in, const void* dy, int64_t n, int64_t H, int
 /* Backward of mla_rn_avgpool (resnet.avgpool + CnnFlatten, model.py:188): d (n, channels) f32 -> dx (n, hw, channels) = d / hw. */
 int mla_rn_avgpool_bwd(const float* d, int64_t n, int64_t hw, int64_t channels, void* dx, int dtype, mla_stream_t stream);
 
+/* --- input gradient of the EVAL-mode trunk (saliency maps of the ResNet branch): under clf.eval() (train.py:113, :201) every
+ *     BatchNorm2d of model.py:129 is a per-channel constant folded into the conv epilogue, so its backward is a mask and a
+ *     scale; the conv data gradients are mla_rn_conv_dgrad, the pools mla_rn_maxpool_bwd / mla_rn_avgpool_bwd. --- */
+
+/* Backward of the eval epilogue y = [relu](conv * scale[c] + shift[c] [+ residual]) over NHWC rows x channels (channels a
+ * multiple of 8), dy / y / dpre / dres in dtype: g = dy * (y > 0), or dy itself when y is NULL (no ReLU: downsample.1); NaN in y
+ * gives 0, as torch's threshold_backward. dpre = g * scale[c], the gradient of the conv output: in f32 the product as written,
+ * in bf16 the same f32 value rounded once. dres (or NULL) receives g, the gradient of the residual. */
+int mla_rn_act_bwd(const void* dy, const void* y, const float* scale, int64_t rows, int64_t channels, void* dpre, void* dres, int dtype,
+                   mla_stream_t stream);
+/* Data gradient of the stem (Input.forward model.py:84-101 + resnet.conv1, 7x7 stride 2 pad 3) with respect to the RAW planes:
+ * dy (n, 112, 112, 64) in dtype, w (64, 3, 7, 7) f32 -> dx (n, 224, 224) f32, every element written once (nothing to zero, no
+ * workspace, no atomics; the bits do not depend on n). The channel configuration (single: x in channel 0 only, else repeated) and
+ * the three 1 / std_c are folded into the taps as mla_rn_stem folds them. y (n, 112, 112, 64) in dtype with scale[64], both or
+ * neither: the stem's fused eval output and its BatchNorm scale; then the gradient that enters the conv is dy * (y > 0) * scale[o]
+ * (NaN in y gives 0). dy and y 16-byte aligned. */
+int mla_rn_stem_dgrad(const void* dy, int64_t n, const void* y, const float* scale, const float* w, int single, float* dx, int dtype,
+                      mla_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
