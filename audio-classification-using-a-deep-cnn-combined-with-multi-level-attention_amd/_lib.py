@@ -68,6 +68,9 @@ def lib():
         L.mla_melspec_workspace_bytes.argtypes = [i64, i64, i64]
         L.mla_melspec_db.argtypes = [vp, i64, i64, i64, i64, i64, cf, vp, vp, vp, vp]
         L.mla_melspec_images.argtypes = [vp, vp, i64, i64, i64, i64, cf, i64, i64, i64, vp, vp]
+        L.mla_melspec_track_counts.argtypes = [i64, i64] + [ctypes.POINTER(i64)] * 4
+        L.mla_melspec_track_db.argtypes = [vp, i64, i64, i64, vp, vp, i64, cf, vp, vp, vp, vp, vp]
+        L.mla_melspec_track_images.argtypes = [vp, vp, i64, vp, vp, i64, cf, i64, i64, vp, vp]
         cd = ctypes.c_double
         L.mla_melspec_band_table_floats.restype = i64
         L.mla_melspec_band_table_floats.argtypes = [cd, i64, cd, cd, ci]

@@ -438,6 +438,131 @@ def audiofiles_to_slots(paths, hop_slots=3, out_dtype=torch.float32):
     return _slots(_pack_audiofiles(files, SR_VGGISH, most), n16, hop_slots, out_dtype)
 
 
+# ---- image timelines: the ResNet branch over recordings of any length (no counterpart in the reference, whose loader stops at 4 s) ----
+IMAGE_HOP_SECONDS = 1.0 / 3                       # one image of hop: 75 spectrogram columns of 98 samples at 22 050 Hz
+_TRACK_MAX_SAMPLES = 1 << 30                      # mla_melspec_track_db: a track's padded samples are indexed with int
+
+
+def image_timeline_counts(n, hop_images=3):
+    """(windows, kept images, track samples L, track columns C) of a recording of n samples at 22 050 Hz scored in 4 s windows
+    (88 200 samples, the reference's clip) that start hop_images / 3 s apart: frontend.melspec_track_counts. n >= 88 200: windows =
+    1 + (n - 88 200) // (7 350 * hop_images), a trailing stretch that fills no window is dropped; n < 88 200: one window, the
+    recording zero-filled as forward_recordings does. The track is the first L = 88 200 + 7 350 * hop_images * (windows - 1)
+    samples, C = 1 + L // 98 columns."""
+    return frontend.melspec_track_counts(n, hop_images)
+
+
+def _track_lengths(frames, rates, hop_images):
+    """Samples of every recording once it is at 22 050 Hz (the library's resampled length), checked: ValueError for a hop_images
+    that is no integer >= 1, for a track longer than 2**30 samples (naming the recording) and for a batch whose rows the clips
+    launch cannot tile. -> (lengths, samples per row: the longest track)."""
+    if int(hop_images) != hop_images or hop_images < 1:
+        raise ValueError("hop_images must be an integer >= 1 (the hop is hop_images / 3 s), got %r" % (hop_images,))
+    L = _lib.lib()
+    n22, most = np.zeros(len(frames), dtype=np.int64), SAMPLES_NUM_RESNET
+    for i, (n, r) in enumerate(zip(frames, rates)):
+        n22[i] = int(n) if float(r) == float(SR_RESNET) else int(L.mla_resample_length(int(n), float(r), float(SR_RESNET)))
+        track = frontend.melspec_track_counts(n22[i], hop_images)[2]
+        if track > _TRACK_MAX_SAMPLES:
+            raise ValueError("recording %d: a track of %d samples at 22 050 Hz is longer than 2**30 (about 13.5 hours): split the recording"
+                             % (i, track))
+        most = max(most, track)
+    if len(frames) * ((most + 255) // 256) > 0x7fffffff:
+        raise ValueError("%d recordings of up to %d samples at 22 050 Hz are more than one clips launch tiles (at most 2**31 - 1 tiles "
+                         "of 256 samples in the batch): split the batch" % (len(frames), most))
+    return n22, most
+
+
+def _tracks(clips, n22, hop_images):
+    """(the frontend.Track of the batch, start_seconds of every window)."""
+    track = frontend.melspec_track_db(clips, n22, hop_images)
+    starts = np.zeros(track.first_rows.shape[0], dtype=np.float64)
+    if starts.shape[0]:
+        index = track.recording_index
+        j = np.arange(index.shape[0]) - np.searchsorted(index, index)          # the window's number within its recording
+        starts = int(hop_images) * j / 3.0
+    return track, starts
+
+
+def _no_tracks():
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    none = np.zeros(0, dtype=np.int64)
+    return torch.empty((0, 1) + S_RESNET_SHAPE, dtype=torch.float32, device=dev), none, none, np.zeros(0, dtype=np.float64)
+
+
+def recordings_to_tracks(recordings, rates, hop_images=3):
+    """Recordings of ANY length as they are decoded -> (frontend.Track, start_seconds) in THREE launches whatever the batch is:
+    recordings_to_clips at 22 050 Hz into rows as long as the longest track, then frontend.melspec_track_db's two. The images are
+    not made: frontend.melspec_track_images(track, first, count) makes any range of them (Ensemble.score_image_timeline does, chunk
+    by chunk). Arguments, errors and limits: recordings_to_track_images. An empty sequence gives (None, no seconds)."""
+    recs, rates = _checked_recordings(recordings, rates, SR_RESNET)
+    n22, most = _track_lengths([x.shape[0] for x in recs], rates, hop_images)
+    if not recs:
+        return None, np.zeros(0, dtype=np.float64)
+    return _tracks(_pack_recordings(recs, rates, SR_RESNET, most), n22, hop_images)
+
+
+def wavfiles_to_tracks(paths, hop_images=3):
+    """16-bit WAV files -> recordings_to_tracks: read_wav16 on every path (other widths are refused)."""
+    return recordings_to_tracks(*_read_wav16s(paths), hop_images)
+
+
+def audiofiles_to_tracks(paths, hop_images=3):
+    """WAV files of any mixture of encodings read_audiofile accepts -> what recordings_to_tracks returns: the files' bytes are decoded,
+    mixed and resampled to 22 050 Hz by frontend.prepare_clips_raw. Bit-identical to wavfiles_to_tracks for 16-bit files."""
+    files = _checked_audiofiles(paths, SR_RESNET)
+    n22, most = _track_lengths([d[1][3] for d in files], [d[1][2] for d in files], hop_images)
+    if not files:
+        return None, np.zeros(0, dtype=np.float64)
+    return _tracks(_pack_audiofiles(files, SR_RESNET, most), n22, hop_images)
+
+
+def _track_images(track, starts):
+    if track is None:
+        return _no_tracks()
+    images = frontend.melspec_track_images(track, 0, track.descriptors.images)
+    return images, track.first_rows, track.recording_index, starts
+
+
+def recordings_to_track_images(recordings, rates, hop_images=3):
+    """Recordings of ANY length as they are decoded -> (images, first_rows, recording_index, start_seconds) in FOUR launches
+    whatever the batch is: recordings_to_clips at 22 050 Hz (channel mean, resampy 'kaiser_best' over the whole recording) into rows
+    as long as the longest track, then the track's spectrogram, its maximum and the images (csrc/melspec.hip).
+
+    A recording of n samples at 22 050 Hz is scored in windows of 88 200 samples, the reference's 4 s clip, that start
+    hop_images / 3 s apart: image_timeline_counts(n, hop_images). A trailing stretch that fills no window is dropped; a recording
+    shorter than one window is zero-filled and gives the ten images forward_recordings builds, bit for bit. images: (S, 1, 224, 224)
+    float32 on the device, the DISTINCT mel-dB images of all windows, each spectrogram column computed once; first_rows /
+    recording_index (host int64) and start_seconds (host float64) have one entry per window: images[first_rows[w] : first_rows[w]
+    + 10] are the ten images of the window that starts start_seconds[w] into recordings[recording_index[w]].
+
+    This is librosa's spectrogram of the whole TRACK (the recording up to the end of its last window), cut into images:
+    power_to_db(melspectrogram(track, sr=22050, n_mels=224, hop_length=98)) with the track centre-padded by reflection at its own
+    two ends and floored at the TRACK-wide maximum - 80 dB. Cropping 4 s pieces on the host and feeding them to
+    recordings_to_clips + clips_to_images reflects at each crop's ends and floors against each crop's own maximum, so two things
+    differ: the first image of a window in its columns 0..10 and the last in its columns 890..898 (the columns whose frames read
+    reflected samples), and a window quieter than the track's loudest one sits on a higher floor. Everything else is the same
+    samples through the same arithmetic, the same bits before the floor.
+
+    Memory: the spectrogram is 896 B per column, about 0.2 MB per second of audio, and an image is 200 KB: for long recordings
+    make the images in ranges (recordings_to_tracks + frontend.melspec_track_images), as Ensemble.score_image_timeline does.
+    recordings / rates: as recordings_to_clips takes them, with its errors. Limits: a track of at most 2**30 samples, about 13.5
+    hours, and at most 2**31 - 1 tiles of 256 samples in the batch; more raises ValueError. All errors come before anything is
+    copied or launched. An empty sequence gives (0, 1, 224, 224) images."""
+    return _track_images(*recordings_to_tracks(recordings, rates, hop_images))
+
+
+def wavfiles_to_track_images(paths, hop_images=3):
+    """16-bit WAV files -> recordings_to_track_images: read_wav16 on every path (other widths are refused)."""
+    return _track_images(*wavfiles_to_tracks(paths, hop_images))
+
+
+def audiofiles_to_track_images(paths, hop_images=3):
+    """WAV files of any mixture of encodings read_audiofile accepts -> what recordings_to_track_images returns, the files' bytes
+    decoded in the clips launch. Bit-identical to wavfiles_to_track_images for 16-bit files."""
+    return _track_images(*audiofiles_to_tracks(paths, hop_images))
+
+
 # ---- the VGGish branch on the librosa path: load_hdf5(cnn_type="vggish", use_librosa=True), dataset.py:232-243, :305-307, :316 -------
 SAMPLES_NUM_VGGISH_LIBROSA = SR_VGGISH * 4       # 64 000: the reference's SAMPLES_NUM_VGGISH (params.py:10), the rows of this path
 LIBROSA_N_MELS, LIBROSA_HOP, LIBROSA_FMIN, LIBROSA_FMAX, LIBROSA_TOP_DB = 64, 160, 125.0, 7500.0, 80.0

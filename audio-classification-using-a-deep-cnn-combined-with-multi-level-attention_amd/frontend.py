@@ -3,6 +3,7 @@
 PyTorch is used for device memory and streams only; all arithmetic is in csrc/logmel.hip.
 """
 
+import collections
 import ctypes
 
 import numpy as np
@@ -410,6 +411,104 @@ def melspec_images(db, ws, n_samples, hop_length, top_db, n_images, image_w, ima
     _lib.check(ops._timed("melspec_images", _lib.lib().mla_melspec_images, vp(db.data_ptr()), vp(ws.data_ptr()), clips, int(n_samples),
                           int(hop_length), n_mels, float(top_db), int(n_images), int(image_w), int(image_stride), vp(out.data_ptr()),
                           _lib.stream_ptr()))
+    return out
+
+
+# ---- the ResNet branch over time: tracks of recordings of any length and the distinct images of their windows ----
+TRACK_SR, TRACK_MELS, TRACK_HOP, TRACK_IMAGE_W, TRACK_IMAGE_STEP, TRACK_WINDOW_IMAGES = 22050, 224, 98, 224, 75, 10
+
+TrackDescriptors = collections.namedtuple("TrackDescriptors", "host device windows images columns runs most")
+Track = collections.namedtuple("Track", "db maxima descriptors first_rows recording_index")
+
+
+def melspec_track_counts(n, hop_images):
+    """(windows, kept images, track samples L, track columns C) of a recording of n samples at 22 050 Hz scored in 4 s windows
+    hop_images / 3 s apart (mla_melspec_track_counts, the single source of the arithmetic; include/mla_hip.h states it).
+    n >= 88 200: windows = 1 + (n - 88 200) // (7 350 * hop_images); n < 88 200: one window, the recording zero-filled.
+    L = 88 200 + 7 350 * hop_images * (windows - 1), C = 1 + L // 98. ValueError for n < 0 and for a hop_images that is no integer
+    >= 1."""
+    if int(hop_images) != hop_images or hop_images < 1:
+        raise ValueError("hop_images must be an integer >= 1 (the hop is hop_images / 3 s), got %r" % (hop_images,))
+    if n < 0:
+        raise ValueError("a recording cannot have %r samples" % (n,))
+    w, s, l, c = (ctypes.c_int64() for _ in range(4))
+    _lib.check(_lib.lib().mla_melspec_track_counts(int(n), int(hop_images), ctypes.byref(w), ctypes.byref(s), ctypes.byref(l), ctypes.byref(c)))
+    return w.value, s.value, l.value, c.value
+
+
+def melspec_track_descriptors(lengths, hop_images):
+    """The descriptors mla_melspec_track_db and mla_melspec_track_images take for recordings of lengths[i] samples at 22 050 Hz:
+    TrackDescriptors(host, device, windows, images, columns, runs, most) with host the (R, 6) int64 array -- track samples,
+    columns, first_run, db_offset, first_image, hop_images per recording --, device None (melspec_track_db uploads it), windows
+    the (R,) window counts, and the batch's kept images, columns, runs of 16 columns and longest track."""
+    q = int(hop_images)
+    desc = np.zeros((len(lengths), 6), dtype=np.int64)
+    windows = np.zeros(len(lengths), dtype=np.int64)
+    run, col, image, most = 0, 0, 0, 0
+    for i, n in enumerate(lengths):
+        w, s, l, c = melspec_track_counts(int(n), hop_images)
+        desc[i] = (l, c, run, TRACK_MELS * col, image, q)
+        windows[i] = w
+        run += (c + 15) // 16
+        col += c
+        image += s
+        most = max(most, l)
+    return TrackDescriptors(desc, None, windows, image, col, run, most)
+
+
+def melspec_track_db(pcm, lengths, hop_images):
+    """(R, n) float32 device rows at 22 050 Hz, row i a recording of lengths[i] samples zero-filled to at least 88 200 (what
+    dataset.recordings_to_clips(..., samples_num=the longest track) gives) -> Track(db, maxima, descriptors, first_rows,
+    recording_index) in TWO launches of csrc/melspec.hip whatever the batch is (melspec_track_db_kernel over the runs of all
+    tracks, melspec_track_max_kernel with one workgroup per recording).
+
+    db: flat float32, recording i's unclipped dB spectrogram of its track -- its first L_i samples, reflected at ITS ends -- as a
+    band-major (224, C_i) block at descriptors.host[i, 3]; maxima: (R,) its maximum, NaN where the track has one. first_rows /
+    recording_index: host int64, one entry per window, recordings in order and windows in order of time: the images of window w
+    are rows first_rows[w] .. first_rows[w] + 9 of melspec_track_images. lengths: host integers (a device tensor is read back
+    first); the descriptors travel in one pinned buffer and one copy. Memory: 896 B per column, about 0.2 MB per second of audio.
+    Nothing at or behind L_i of a row is read, and a recording's values are the same bits alone, in any batch and at any position."""
+    assert pcm.dim() == 2 and pcm.is_cuda and pcm.dtype == torch.float32 and (pcm.shape[1] <= 1 or pcm.stride(1) == 1)
+    R, n = pcm.shape
+    nv = _host_array(lengths, np.int64)
+    assert nv.shape[0] == R, "one length per row"
+    d = melspec_track_descriptors(nv, hop_images)
+    step = min(int(hop_images), TRACK_WINDOW_IMAGES)
+    recording_index = np.repeat(np.arange(R, dtype=np.int64), d.windows)
+    first_rows = np.concatenate([d.host[i, 4] + step * np.arange(d.windows[i], dtype=np.int64) for i in range(R)]) if R else np.zeros(0, np.int64)
+    db = torch.empty(TRACK_MELS * d.columns, dtype=torch.float32, device=pcm.device)
+    maxima = torch.empty(R, dtype=torch.float32, device=pcm.device)
+    if R == 0:
+        return Track(db, maxima, d, first_rows, recording_index)
+    ws = torch.empty(d.runs, dtype=torch.float32, device=pcm.device)
+    tab = melspec_tables(pcm.device, TRACK_SR, TRACK_MELS)
+    host = torch.empty(d.host.size, dtype=torch.int64, pin_memory=True)
+    host.numpy()[:] = d.host.reshape(-1)
+    d = d._replace(device=host.to(pcm.device, non_blocking=True))
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_track_db", _lib.lib().mla_melspec_track_db, vp(pcm.data_ptr()), R, n, pcm.stride(0) if R > 1 else n,
+                          vp(d.device.data_ptr()), d.host.ctypes.data_as(vp), d.columns, MELSPEC_AMIN, vp(tab.data_ptr()), vp(db.data_ptr()),
+                          vp(ws.data_ptr()), vp(maxima.data_ptr()), _lib.stream_ptr()))
+    return Track(db, maxima, d, first_rows, recording_index)
+
+
+def melspec_track_images(track, first, count, top_db=80.0):
+    """The kept images with global row in [first, first + count) of a Track -> (count, 1, 224, 224) float32 in ONE launch
+    (melspec_track_images_kernel): a select against the TRACK-wide maximum and a gather, out[i][0][b][x] = max(D_r[b][75 u + x],
+    max(D_r) - top_db), bit-determined by track.db. The range lets the caller make the images chunk by chunk: an image is 200 KB."""
+    d = track.descriptors
+    first, count = int(first), int(count)
+    if first < 0 or count < 0 or first + count > d.images:
+        raise ValueError("images %d .. %d leave the %d kept images of the track" % (first, first + count, d.images))
+    out = torch.empty((count, 1, TRACK_MELS, TRACK_IMAGE_W), dtype=torch.float32, device=track.db.device)
+    if count == 0:
+        return out
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_track_images", _lib.lib().mla_melspec_track_images, vp(track.db.data_ptr()), vp(track.maxima.data_ptr()),
+                          d.host.shape[0], vp(d.device.data_ptr()), d.host.ctypes.data_as(vp), d.columns, float(top_db), first, count,
+                          vp(out.data_ptr()), _lib.stream_ptr()))
     return out
 
 

@@ -12,6 +12,7 @@ ResNet-50 trunk on HIP kernels (``resnet.py``); its BatchNorm layers follow trai
 
 from typing import Dict, List, Union
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -239,7 +240,8 @@ class Ensemble(nn.Module):
         (ops.gather_bags), then the head. BatchNorm1d(T) of the head is per slot position, so only the CNN is shared."""
         if self.cnn_type != "vggish":
             raise NotImplementedError("%s scores the VGGish branch's log-mel bags over time; cnn_type 'resnet' has no timeline path: "
-                                      "crop 4 s pieces on the host and use forward_recordings()" % what)
+                                      "crop 4 s pieces on the host and use forward_recordings(), or score its mel-dB images over time "
+                                      "with %s()" % (what, what.replace("score_timeline", "score_image_timeline")))
         self._ten_window_bags(what)
         if self.training:
             raise RuntimeError("%s runs in eval mode only: batch statistics over the windows of one recording are no defined training "
@@ -274,6 +276,54 @@ class Ensemble(nn.Module):
         """score_timeline for WAV files of any PCM width or IEEE float (dataset.audiofiles_to_slots)."""
         from . import dataset
         return self._timeline("score_timeline_audiofiles", dataset.audiofiles_to_slots, (paths,), hop_slots, max_slots)
+
+    def _image_timeline(self, what, tracks_fn, source, hop_images, max_images):
+        """Recordings of any length scored over time on the ResNet branch: every recording's spectrogram once (dataset.recordings_to_tracks),
+        then per chunk of at most max_images DISTINCT images the images launch, Input and the CNN, the windows' bags gathered from the
+        embeddings (ops.gather_bags), then the head. BatchNorm1d(T) of the head is per slot position, so only the CNN is shared."""
+        if self.cnn_type != "resnet":
+            raise NotImplementedError("%s scores the ResNet branch's mel-dB images over time; cnn_type 'vggish' scores its log-mel bags "
+                                      "over time with %s()" % (what, what.replace("score_image_timeline", "score_timeline")))
+        self._ten_window_bags(what)
+        if self.training:
+            raise RuntimeError("%s runs in eval mode only: batch statistics over the windows of one recording are no defined training "
+                               "step, and the chunks of max_images would change them; call eval() first" % what)
+        if int(max_images) < 1:
+            raise ValueError("%s: max_images must be >= 1, got %r" % (what, max_images))
+        from . import frontend
+        track, starts = tracks_fn(*source, hop_images=hop_images)
+        if track is None:
+            return torch.empty((0, self.classes), dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu"), \
+                np.zeros(0, dtype=np.int64), starts
+        parts = []
+        for at in range(0, track.descriptors.images, int(max_images)):
+            chunk = frontend.melspec_track_images(track, at, min(int(max_images), track.descriptors.images - at))
+            parts.append(self.cnn(self.input(chunk.view(-1, 1, 1, S_RESNET_SHAPE[0], S_RESNET_SHAPE[1]))))
+        emb = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return self.mla(ops.gather_bags(emb, track.first_rows, T).view(-1, T, self.emb_input_size)), track.recording_index, starts
+
+    def score_image_timeline(self, recordings, rates, hop_images=3, max_images=256):
+        """The ResNet branch over recordings of ANY length (host arrays, (n,) or (n, channels), int16 or floating, any rates): one
+        score vector per 4 s window, the windows hop_images / 3 s apart (dataset.recordings_to_track_images states which, and how the
+        images differ from cropping 4 s pieces on the host: reflection at the track's ends only, the floor against the track-wide
+        maximum). -> (scores (windows of all recordings, classes) on the device, recording_index (int64, host), start_seconds
+        (float64, host)), recordings in order and windows in order of time. A recording of at most one window gives the one row
+        forward_recordings gives. The spectrogram is computed once and the CNN runs once per DISTINCT image, 3 W + 7 of them for W
+        windows at the default hop where cropping needs 10 W, max_images of them at a time: that bounds the image tensor (200 KB
+        each) and the trunk's activations; it is a bound on memory, not a tuned value. input_conf, precision and just_bottlenecks
+        act as in forward(); eval mode only."""
+        from . import dataset
+        return self._image_timeline("score_image_timeline", dataset.recordings_to_tracks, (recordings, rates), hop_images, max_images)
+
+    def score_image_timeline_wavfiles(self, paths, hop_images=3, max_images=256):
+        """score_image_timeline for 16-bit WAV files (dataset.wavfiles_to_tracks)."""
+        from . import dataset
+        return self._image_timeline("score_image_timeline_wavfiles", dataset.wavfiles_to_tracks, (paths,), hop_images, max_images)
+
+    def score_image_timeline_audiofiles(self, paths, hop_images=3, max_images=256):
+        """score_image_timeline for WAV files of any PCM width or IEEE float (dataset.audiofiles_to_tracks)."""
+        from . import dataset
+        return self._image_timeline("score_image_timeline_audiofiles", dataset.audiofiles_to_tracks, (paths,), hop_images, max_images)
 
     def _saliency_target(self, target, bags, device):
         """The `target` argument of the saliency entries -> None (each bag's top class, known after the forward) or (bags,) int64

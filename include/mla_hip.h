@@ -186,6 +186,55 @@ int mla_melspec_db(const float* pcm, int64_t clips, int64_t n_samples, int64_t c
 int mla_melspec_images(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
                        float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, float* out, mla_stream_t stream);
 
+/* ---- ResNet branch over time: a recording of any length scored in 4 s windows at a hop of hop_images / 3 s ----
+ * Extends create_spec(cnn_type="resnet") + split (dataset.py:309-316, :329-363) beyond the reference's loader, which cuts every
+ * recording at 4 s (dataset.py:233-237); the configuration is the reference's: 22 050 Hz, 224 bands, hop 98, ten images of 224
+ * columns 75 columns apart per 88 200-sample window.
+ * Host only, the single source of the arithmetic, exact for any int64 n_samples. An image step is 75 columns = 7 350 samples.
+ * With q = hop_images >= 1:
+ *   n >= 88 200: windows = 1 + (n - 88 200) / (7 350 q); a trailing stretch that fills no window is dropped;
+ *   n <  88 200: one window, the recording zero-filled to 88 200 samples (dataset.py:235-237).
+ * The TRACK is the first *samples = 88 200 + 7 350 q (windows - 1) samples, centre-padded by reflection at its own two ends, with
+ * *columns = 1 + samples / 98 spectrogram columns; D = power_to_db(melspectrogram(track), top_db=None) and the floor is taken
+ * against the TRACK-wide maximum: librosa's spectrogram of the whole track, cut into images. Image u is columns [75 u, 75 u + 224);
+ * it is kept iff u mod q < 10 and u <= q (windows - 1) + 9. *images is their number: q (windows - 1) + 10 for q <= 10, where
+ * window j is rows q j .. q j + 9 of the recording's kept images, and 10 * windows for q > 10, window j = rows 10 j .. 10 j + 9.
+ * Against cropping 4 s pieces on the host (mla_melspec_db + mla_melspec_images per crop), which reflects at each crop's ends and
+ * floors against each crop's maximum: columns 0..10 of a window's first image and 890..898 of its last differ, and a window
+ * quieter than the track's loudest sits on a higher floor; all else is the same samples through the same arithmetic. One window
+ * IS the crop. Any output pointer may be NULL. n_samples < 0, hop_images < 1 or > 2^30 -> MLA_E_ARG. */
+int mla_melspec_track_counts(int64_t n_samples, int64_t hop_images, int64_t* windows, int64_t* images, int64_t* samples,
+                             int64_t* columns);
+/* mla_melspec_db for a RAGGED batch: the unclipped dB spectrogram of every recording's track and its maximum, two launches
+ * whatever the batch is. pcm[recordings][row_stride] f32 at 22 050 Hz (the first n_samples of a row are valid input).
+ * desc[recordings][6] (DEVICE, int64) and host_desc, the same array on the HOST, read for validation before anything is launched.
+ * Per recording:
+ *   [0] samples      the track's samples, 88 200 + 7 350 q (windows - 1), at most 2^30
+ *   [1] cols         1 + samples / 98
+ *   [2] first_run    runs of 16 columns before it: per recording ceil(cols / 16)
+ *   [3] db_offset    floats of out_db before it: 224 * the columns before it
+ *   [4] first_image  kept images before it (mla_melspec_track_images' rows)
+ *   [5] q            hop_images of this recording
+ * out_db: total_columns * 224 floats, recording r's block at db_offset, band-major (224, cols). workspace: one float per run
+ * (the sum of ceil(cols / 16)), the runs' maxima; maxima[recordings]: max(D_r), NaN if a sample of the track is. `tables`: the
+ * device copy of mla_melspec_build_tables(22050, 224). A recording's values depend on its own track only, the same bits alone,
+ * in any batch and at any position; columns 11 .. cols - 12 are the bits mla_melspec_db gives any 88 200-sample crop that holds
+ * their frames' samples. Nothing at or behind `samples` of a row is read.
+ * Errors, all before any launch: null or misaligned pointer, q < 1, (samples, cols) that are no track, prefixes that are not the
+ * sums before them, total_columns that is not the sum, amin <= 0 -> MLA_E_ARG; a track longer than n_samples or than 2^30, more
+ * than 2^31 - 1 runs -> MLA_E_SHAPE. recordings == 0 returns MLA_OK. */
+int mla_melspec_track_db(const float* pcm, int64_t recordings, int64_t n_samples, int64_t row_stride, const int64_t* desc,
+                         const int64_t* host_desc, int64_t total_columns, float amin, const float* tables, float* out_db,
+                         float* workspace, float* maxima, mla_stream_t stream);
+/* mla_melspec_images over the tracks of mla_melspec_track_db (same desc / host_desc / total_columns): the kept images with global
+ * row in [first, first + count), so that a caller can make them chunk by chunk,
+ *   out[row - first][0][b][x] = max(D_r[b][75 u + x], maxima[r] - top_db)   (max keeps NaN)
+ * as float32, out 16-byte aligned. Every element of out is written exactly once.
+ * Errors, all before any launch: as mla_melspec_track_db for the descriptors; top_db < 0, first < 0, count < 0 -> MLA_E_ARG; a
+ * range that leaves the kept images -> MLA_E_SHAPE. count == 0 returns MLA_OK. */
+int mla_melspec_track_images(const float* db, const float* maxima, int64_t recordings, const int64_t* desc, const int64_t* host_desc,
+                             int64_t total_columns, float top_db, int64_t first, int64_t count, float* out, mla_stream_t stream);
+
 /* ---- VGGish branch, librosa path: dataset.create_spec(cnn_type="vggish", use_librosa=True) + split (dataset.py:305-307, :316,
  * :329-363): librosa.feature.melspectrogram(y, sr, n_mels=64, hop_length=160, center=False, htk=True, fmin=125, fmax=7500)
  * followed by librosa.power_to_db, for a batch of clips. center=False: no padding, frame f is y[f * hop .. f * hop + 2047],
