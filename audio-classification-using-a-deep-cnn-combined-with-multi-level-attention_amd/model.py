@@ -394,8 +394,8 @@ class Ensemble(nn.Module):
         """saliency for the ResNet branch: x (B, slots, 1, 224, 224) spectrogram images -> (scores (B, classes), detached; grad
         float32 of x's shape = d scores[b, target_b] / d x[b], multiplied by x with times_input). target as in saliency(). Eval mode
         only, for saliency()'s reason. The trunk runs its eval-mode forward with a tape and is walked back by hand
-        (resnet.trunk_input_backward: BatchNorm as the folded per-channel constant it is in eval mode, the stem's backward-data
-        kernel last); only the head (and the fc of just_bottlenecks=False) sits behind autograd, differentiated with respect to the
+        (resnet.trunk_input_backward: the reverse walk trunk_backward uses, with BatchNorm as the folded per-channel constant it is
+        in eval mode, the stem's backward-data kernel last); only the head (and the fc of just_bottlenecks=False) sits behind autograd, differentiated with respect to the
         features alone. No parameter's .grad, no buffer and no switch of the module is changed, whatever requires grad; no weight
         gradient is launched. The tape holds every activation of the batch: the caller splits large batches."""
         if self.cnn_type != "resnet":
@@ -658,8 +658,8 @@ class CNN(nn.Module):
                                               "run eval-mode forwards under torch.no_grad() as _evaluate / test_model do")
                 params = [p for _, p in resnet.trunk_params(self.cnn_model)]
                 feats = differentiable.TrunkFn.apply(self.cnn_model, x, self.precision, self._rn_cache, *params)
-                return feats if self.just_bottlenecks else resnet.fc_forward(self.cnn_model.fc, feats)
-            feats = resnet.trunk_forward(self.cnn_model, x, self.precision, self.training, self._rn_cache)
+            else:
+                feats = resnet.trunk_forward(self.cnn_model, x, self.precision, self.training, self._rn_cache)
             return feats if self.just_bottlenecks else resnet.fc_forward(self.cnn_model.fc, feats)
         x = self.cnn_model(x)
         if x.dtype == torch.bfloat16:      # bf16 bottlenecks (just_bottlenecks=True) feed the f32 head

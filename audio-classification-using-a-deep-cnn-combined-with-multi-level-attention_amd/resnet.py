@@ -11,6 +11,7 @@ are opt-in per model (``CNN.set_trunk_backward``) and raise while off; the ``fc`
 the reference) is differentiable (``fc_forward``).
 """
 
+import collections
 import math
 
 import torch
@@ -169,14 +170,20 @@ def _check_frozen(cnn_model):
                                       "CNN.set_trunk_backward(True) / Ensemble(..., trunk_backward=True)" % name)
 
 
+# What a taped forward keeps per BatchNorm2d (tape["bn"][id(bn)]). y: the unit's output where a ReLU follows (its mask), else
+# None. Train mode: x the raw conv output, mean / var its batch statistics, scale None. Eval mode, the BatchNorm folded into the
+# conv: scale the folded per-channel scale, x / mean / var None.
+BnRecord = collections.namedtuple("BnRecord", "x mean var y scale")
+
+
 def trunk_forward(cnn_model, x, precision, training, cache, dist=None, tape=None):
     """StemInput -> f32 (N, 2048) bottleneck features (avgpool + flatten) of the HIP trunk. dist: the ``ops.Dist`` of a
     data-parallel training step; in train mode its SyncBN setting decides whether the 53 BatchNorm2d statistics are those of
-    the global batch (one all-reduce per layer) or of this rank's shard. tape: a dict that receives what ``trunk_backward``
-    needs (train mode only): every BatchNorm's input (the raw conv output), batch statistics and output, and every block's
-    input; the BatchNorm outputs then go to new tensors instead of overwriting their inputs. Same results either way. In eval
-    mode a tape receives what ``trunk_input_backward`` needs instead: the output of every fused conv (the stem's included), the
-    eval scale of every BatchNorm and every block's input; the kernels launched and the features are those of the untaped call."""
+    the global batch (one all-reduce per layer) or of this rank's shard. tape: a dict that receives what the backward of this
+    forward needs (``trunk_backward`` in train mode, ``trunk_input_backward`` in eval mode, which also sets tape["eval"]): every
+    block's input in tape["block_in"] and one ``BnRecord`` per BatchNorm2d in tape["bn"], both keyed by the module's id, the
+    stem's bn1 included. The kernels launched and the features are those of the untaped call; in train mode the BatchNorm
+    outputs then go to new tensors instead of overwriting their inputs."""
     if not isinstance(x, StemInput):
         raise TypeError("the ResNet trunk takes the output of model.Input (raw 224 x 224 planes)")
     if precision not in _DTYPES:
@@ -193,162 +200,88 @@ def trunk_forward(cnn_model, x, precision, training, cache, dist=None, tape=None
     packed = cache["w"].get([c.weight for c in convs], dtype,
                             lambda: {id(c): ops.rn_repack(c.weight.detach().contiguous(), dtype) for c in convs})
     w1 = conv1.weight.detach().contiguous()
+    if tape is not None:
+        tape.update(dtype=dtype, planes=planes, single=x.single, bn={}, block_in={})
+
+    def conv_of(h, conv, scale=None, shift=None, residual=None, relu=False):
+        if conv is conv1:                         # the stem: it reads the raw planes, and nothing is added to it
+            return ops.rn_stem(planes, x.single, w1, dtype, scale, shift, relu)
+        return ops.rn_conv(h, packed[id(conv)], conv.stride[0], scale, shift, residual, relu)
+
     if training:
         cache["bn"].key = None                    # the running statistics change below, behind torch's version counters
         dist = dist or ops._local()
-        stats = lambda t, bn: ops.rn_bn_stats_sync(t, bn, dist)     # noqa: E731
-        if tape is not None:
-            tape.update(dtype=dtype, planes=planes, single=x.single, bn={}, block_in={})
 
-            def bn_apply(t, bn, residual=None, relu=False):
-                scale, shift, mean, var = ops.rn_bn_stats_sync(t, bn, dist, want_stats=True)
-                y = ops.rn_bn_apply(t, scale, shift, residual=residual, relu=relu, out=torch.empty_like(t))
-                tape["bn"][id(bn)] = (t, mean, var, y if relu else None)
-                return y
-        else:
-            def bn_apply(t, bn, residual=None, relu=False):
-                return ops.rn_bn_apply(t, *stats(t, bn), residual=residual, relu=relu)
-        h = ops.rn_stem(planes, x.single, w1, dtype)
-        h = bn_apply(h, bn1, relu=True)
-        h = ops.rn_maxpool(h)
-        for b in blocks:
-            if tape is not None:
-                tape["block_in"][id(b)] = h
-            o = ops.rn_conv(h, packed[id(b.conv1)], 1)
-            o = bn_apply(o, b.bn1, relu=True)
-            o = ops.rn_conv(o, packed[id(b.conv2)], b.stride)
-            o = bn_apply(o, b.bn2, relu=True)
-            if b.downsample is not None:
-                idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride)
-                idn = bn_apply(idn, b.downsample[1])
-            else:
-                idn = h
-            o = ops.rn_conv(o, packed[id(b.conv3)], 1)
-            h = bn_apply(o, b.bn3, residual=idn, relu=True)
+        def unit(h, conv, bn, residual=None, relu=False):
+            t = conv_of(h, conv)
+            if tape is None:
+                return ops.rn_bn_apply(t, *ops.rn_bn_stats_sync(t, bn, dist), residual=residual, relu=relu)
+            scale, shift, mean, var = ops.rn_bn_stats_sync(t, bn, dist, want_stats=True)
+            y = ops.rn_bn_apply(t, scale, shift, residual=residual, relu=relu, out=torch.empty_like(t))
+            tape["bn"][id(bn)] = BnRecord(t, mean, var, y if relu else None, None)
+            return y
+    else:
+        bns = [bn1] + [n for b in blocks for n in ([b.bn1, b.bn2, b.bn3] + ([b.downsample[1]] if b.downsample is not None else []))]
+        tensors = [t for n in bns for t in (n.weight, n.bias, n.running_mean, n.running_var)]
+        coef = cache["bn"].get(tensors, None, lambda: {id(n): ops.rn_bn_eval_coeffs(n) for n in bns})
         if tape is not None:
-            tape["last_shape"] = tuple(h.shape)
-        return ops.rn_avgpool(h)
-    bns = [bn1] + [n for b in blocks for n in ([b.bn1, b.bn2, b.bn3] + ([b.downsample[1]] if b.downsample is not None else []))]
-    tensors = [t for n in bns for t in (n.weight, n.bias, n.running_mean, n.running_var)]
-    coef = cache["bn"].get(tensors, None, lambda: {id(n): ops.rn_bn_eval_coeffs(n) for n in bns})
-    h = ops.rn_stem(planes, x.single, w1, dtype, *coef[id(bn1)], relu=True)
-    if tape is not None:                          # eval tape: the fused outputs are new tensors anyway, the tape only keeps them
-        tape.update(eval=True, dtype=dtype, planes=planes, single=x.single, stem=h, y={}, block_in={},
-                    scale={id(n): coef[id(n)][0] for n in bns})
-    h = ops.rn_maxpool(h)
+            tape["eval"] = True
+
+        def unit(h, conv, bn, residual=None, relu=False):
+            scale, shift = coef[id(bn)]
+            y = conv_of(h, conv, scale, shift, residual, relu)
+            if tape is not None:                  # the fused outputs are new tensors anyway, the tape only keeps them
+                tape["bn"][id(bn)] = BnRecord(None, None, None, y if relu else None, scale)
+            return y
+
+    h = ops.rn_maxpool(unit(None, conv1, bn1, relu=True))
     for b in blocks:
-        a1 = ops.rn_conv(h, packed[id(b.conv1)], 1, *coef[id(b.bn1)], relu=True)
-        a2 = ops.rn_conv(a1, packed[id(b.conv2)], b.stride, *coef[id(b.bn2)], relu=True)
-        idn = ops.rn_conv(h, packed[id(b.downsample[0])], b.stride, *coef[id(b.downsample[1])]) if b.downsample is not None else h
-        out = ops.rn_conv(a2, packed[id(b.conv3)], 1, *coef[id(b.bn3)], residual=idn, relu=True)
         if tape is not None:
             tape["block_in"][id(b)] = h
-            tape["y"].update({id(b.bn1): a1, id(b.bn2): a2, id(b.bn3): out})
-        h = out
+        o = unit(h, b.conv1, b.bn1, relu=True)
+        o = unit(o, b.conv2, b.bn2, relu=True)
+        idn = unit(h, b.downsample[0], b.downsample[1]) if b.downsample is not None else h
+        h = unit(o, b.conv3, b.bn3, residual=idn, relu=True)
+        del o, idn                                # nothing of a block but its output is held into the next one
     if tape is not None:
         tape["last_shape"] = tuple(h.shape)
     return ops.rn_avgpool(h)
 
 
-def trunk_input_backward(cnn_model, tape, d_feats):
-    """Backward of the EVAL-mode trunk forward recorded in `tape` down to the input: d_feats (N, 2048) f32, the gradient of the
-    features -> (N, 224, 224) f32, the gradient of the raw planes ``model.Input`` received. Every BatchNorm is a per-channel
-    scale and shift folded into its conv's epilogue there, so its backward is ``ops.rn_act_bwd`` (the ReLU mask from the kept
-    output, times the scale): avg-pool backward, the blocks in reverse (act_bwd then the conv's data gradient, the skip
-    gradient added by the dgrad's residual input), max-pool backward, ``ops.rn_stem_dgrad`` behind the stem's own epilogue. No
-    weight gradient and no batch-statistics backward is launched. Runs under no_grad whatever the parameters' requires_grad
-    flags say; no parameter's .grad and no buffer is touched. The tape is consumed (its tensors are released as the walk passes
-    them)."""
-    assert tape.get("eval"), "trunk_input_backward differentiates the eval-mode forward (trunk_forward(training=False, tape=...))"
-    conv1, bn1, layers, _ = parts(cnn_model)
-    blocks = [b for layer in layers for b in layer]
-    dtype, ys, scale = tape["dtype"], tape["y"], tape["scale"]
-    with torch.no_grad():
-        def dgrad(dy, conv, in_hw, residual=None):
-            return ops.rn_conv_dgrad(dy, ops.rn_repack_dgrad(conv.weight.detach().contiguous(), dtype), conv.stride[0], in_hw, residual)
-
-        d = ops.rn_avgpool_bwd(d_feats, tape["last_shape"], dtype)
-        for b in reversed(blocks):
-            h_in = tape["block_in"].pop(id(b))
-            a1, a2 = ys.pop(id(b.bn1)), ys.pop(id(b.bn2))
-            do3, g3 = ops.rn_act_bwd(d, scale[id(b.bn3)], y=ys.pop(id(b.bn3)), want_dres=True)
-            da2 = dgrad(do3, b.conv3, a2.shape[1:3])
-            del do3
-            do2, _ = ops.rn_act_bwd(da2, scale[id(b.bn2)], y=a2)
-            del da2, a2
-            da1 = dgrad(do2, b.conv2, a1.shape[1:3])
-            del do2
-            do1, _ = ops.rn_act_bwd(da1, scale[id(b.bn1)], y=a1)
-            del da1, a1
-            if b.downsample is not None:
-                dds, _ = ops.rn_act_bwd(g3, scale[id(b.downsample[1])])
-                skip = dgrad(dds, b.downsample[0], h_in.shape[1:3])
-                del dds
-            else:
-                skip = g3
-            del g3
-            d = dgrad(do1, b.conv1, h_in.shape[1:3], residual=skip)
-            del do1, skip, h_in
-        a0 = tape["stem"]
-        da0 = ops.rn_maxpool_bwd(a0, d)                           # d: gradient of the maxpool output
-        del d
-        dx = ops.rn_stem_dgrad(da0, conv1.weight.detach().contiguous(), tape["single"], y=a0, scale=scale[id(bn1)])
-    tape.clear()
-    return dx
-
-
-def trunk_backward(cnn_model, tape, d_feats, grads, dist=None):
-    """Backward of the train-mode trunk forward recorded in `tape`: d_feats (N, 2048) f32, the gradient of the features ->
-    the f32 gradients of the trunk parameters in `grads` ({id(parameter): tensor to write}); only those are computed. The
-    blocks are walked in reverse (at a block input the main-path and skip-path gradients are summed by the conv epilogue)
-    down to the lowest unit holding a requested parameter; weight gradients nobody asked for are skipped. The tape is
-    consumed (its tensors are released as the walk passes them). dist: the ``ops.Dist`` the forward ran under; with SyncBN
-    active every BatchNorm2d backward all-reduces its two batch sums (one message per layer the walk passes), so dx is that of
-    the global batch. Convs, weight gradients, stem and pools are per-sample linear: they stay local, and `grads` holds this
-    rank's part of every parameter gradient (the caller's gradient all-reduce sums the parts)."""
-    conv1, bn1, layers, _ = parts(cnn_model)
-    blocks = [b for layer in layers for b in layer]
-    units = [[conv1, bn1]] + [[b] for b in blocks]                 # unit 0: stem; unit k: blocks[k - 1]
-    wanted = [any(id(p) in grads for m in u for p in m.parameters()) for u in units]
-    if not any(wanted):
-        return
-    lowest = wanted.index(True)
-    dtype, bns = tape["dtype"], tape["bn"]
-    dist = dist or ops._local()
-    g = grads.get
-    d = ops.rn_avgpool_bwd(d_feats, tape["last_shape"], dtype)
+def _blocks_backward(blocks, tape, d_feats, lowest, bn_bwd, wgrad):
+    """What ``trunk_backward`` and ``trunk_input_backward`` share: the avg-pool backward of d_feats, then the blocks in reverse
+    from the last one down to ``blocks[max(lowest, 1) - 1]`` (unit 0 is the stem, unit k is blocks[k - 1]) -> the gradient of
+    the max-pool output, or None when lowest > 0 (nothing under the lowest block is wanted, so its input gradients are not
+    computed). bn_bwd(bn, dy, want_dres) -> (d_pre, d_res) is the backward of one BatchNorm [+ residual] [+ ReLU]; it pops
+    bn's record from tape["bn"]. wgrad(x, dy, conv) takes the conv's weight gradient, or does nothing. At a block input the
+    main-path and skip-path gradients are summed by the conv1 data gradient's residual input. The ``del`` statements bound
+    the peak memory of both callers: every gradient and kept output is released as soon as the walk has passed it."""
+    dtype, records = tape["dtype"], tape["bn"]
 
     def dgrad(dy, conv, in_hw, residual=None):
         return ops.rn_conv_dgrad(dy, ops.rn_repack_dgrad(conv.weight.detach().contiguous(), dtype), conv.stride[0], in_hw, residual)
 
-    def wgrad(x, dy, conv):
-        if id(conv.weight) in grads:
-            ops.rn_conv_wgrad(x, dy, conv.stride[0], grads[id(conv.weight)])
-
-    def bn_bwd(bn, dy, want_dres=False):
-        x, mean, var, y = bns.pop(id(bn))
-        return ops.rn_bn_bwd_sync(x, dy, mean, var, bn, dist, y=y, want_dres=want_dres, dgamma=g(id(bn.weight)), dbeta=g(id(bn.bias)))
-
+    d = ops.rn_avgpool_bwd(d_feats, tape["last_shape"], dtype)
     for k in range(len(blocks), max(lowest, 1) - 1, -1):
         b = blocks[k - 1]
         h_in = tape["block_in"].pop(id(b))
-        a2 = bns[id(b.bn2)][3]
-        do3, g3 = bn_bwd(b.bn3, d, want_dres=True)
+        a2 = records[id(b.bn2)].y
+        do3, g3 = bn_bwd(b.bn3, d, True)
         wgrad(a2, do3, b.conv3)
         da2 = dgrad(do3, b.conv3, a2.shape[1:3])
         del do3
-        a1 = bns[id(b.bn1)][3]
-        do2, _ = bn_bwd(b.bn2, da2)
-        del da2
+        a1 = records[id(b.bn1)].y
+        do2, _ = bn_bwd(b.bn2, da2, False)
+        del da2, a2
         wgrad(a1, do2, b.conv2)
         da1 = dgrad(do2, b.conv2, a1.shape[1:3])
         del do2
-        do1, _ = bn_bwd(b.bn1, da1)
-        del da1
+        do1, _ = bn_bwd(b.bn1, da1, False)
+        del da1, a1
         wgrad(h_in, do1, b.conv1)
         below = lowest < k                                        # a unit under this block wants a gradient
         if b.downsample is not None:
-            dds, _ = bn_bwd(b.downsample[1], g3)
+            dds, _ = bn_bwd(b.downsample[1], g3, False)
             wgrad(h_in, dds, b.downsample[0])
             skip = dgrad(dds, b.downsample[0], h_in.shape[1:3]) if below else None
             del dds
@@ -357,10 +290,71 @@ def trunk_backward(cnn_model, tape, d_feats, grads, dist=None):
         del g3
         d = dgrad(do1, b.conv1, h_in.shape[1:3], residual=skip) if below else None
         del do1, skip, h_in
+    return d
+
+
+def trunk_input_backward(cnn_model, tape, d_feats):
+    """Backward of the EVAL-mode trunk forward recorded in `tape` down to the input: d_feats (N, 2048) f32, the gradient of the
+    features -> (N, 224, 224) f32, the gradient of the raw planes ``model.Input`` received. Every BatchNorm is a per-channel
+    scale and shift folded into its conv's epilogue there, so its backward is ``ops.rn_act_bwd`` (the ReLU mask from the
+    record's kept output, times its scale): the whole of ``_blocks_backward`` with that and without weight gradients, then the
+    max-pool backward and ``ops.rn_stem_dgrad`` behind the stem's own epilogue (bn1's record). No weight gradient and no
+    batch-statistics backward is launched. Runs under no_grad whatever the parameters' requires_grad flags say; no parameter's
+    .grad and no buffer is touched. The tape is consumed (its tensors are released as the walk passes them)."""
+    assert tape.get("eval"), "trunk_input_backward differentiates the eval-mode forward (trunk_forward(training=False, tape=...))"
+    conv1, bn1, layers, _ = parts(cnn_model)
+    records = tape["bn"]
+
+    def bn_bwd(bn, dy, want_dres):
+        r = records.pop(id(bn))
+        return ops.rn_act_bwd(dy, r.scale, y=r.y, want_dres=want_dres)
+
+    with torch.no_grad():
+        d = _blocks_backward([b for layer in layers for b in layer], tape, d_feats, 0, bn_bwd, lambda x, dy, conv: None)
+        stem = records.pop(id(bn1))
+        da0 = ops.rn_maxpool_bwd(stem.y, d)                       # d: gradient of the maxpool output
+        del d
+        dx = ops.rn_stem_dgrad(da0, conv1.weight.detach().contiguous(), tape["single"], y=stem.y, scale=stem.scale)
+    tape.clear()
+    return dx
+
+
+def trunk_backward(cnn_model, tape, d_feats, grads, dist=None):
+    """Backward of the train-mode trunk forward recorded in `tape`: d_feats (N, 2048) f32, the gradient of the features ->
+    the f32 gradients of the trunk parameters in `grads` ({id(parameter): tensor to write}); only those are computed.
+    ``_blocks_backward`` walks down to the lowest unit holding a requested parameter with the train-mode BatchNorm backward
+    (batch statistics and kept output from the record); weight gradients nobody asked for are skipped. Then, where the stem is
+    wanted, the max-pool backward, bn1's backward and the stem's weight gradient. The tape is
+    consumed (its tensors are released as the walk passes them). dist: the ``ops.Dist`` the forward ran under; with SyncBN
+    active every BatchNorm2d backward all-reduces its two batch sums (one message per layer the walk passes), so dx is that of
+    the global batch. Convs, weight gradients, stem and pools are per-sample linear: they stay local, and `grads` holds this
+    rank's part of every parameter gradient (the caller's gradient all-reduce sums the parts)."""
+    assert not tape.get("eval"), "trunk_backward differentiates the train-mode forward (trunk_forward(training=True, tape=...))"
+    conv1, bn1, layers, _ = parts(cnn_model)
+    blocks = [b for layer in layers for b in layer]
+    units = [[conv1, bn1]] + [[b] for b in blocks]                 # unit 0: stem; unit k: blocks[k - 1]
+    wanted = [any(id(p) in grads for m in u for p in m.parameters()) for u in units]
+    if not any(wanted):
+        tape.clear()
+        return
+    lowest = wanted.index(True)
+    records = tape["bn"]
+    dist = dist or ops._local()
+    g = grads.get
+
+    def wgrad(x, dy, conv):
+        if id(conv.weight) in grads:
+            ops.rn_conv_wgrad(x, dy, conv.stride[0], grads[id(conv.weight)])
+
+    def bn_bwd(bn, dy, want_dres):
+        r = records.pop(id(bn))
+        return ops.rn_bn_bwd_sync(r.x, dy, r.mean, r.var, bn, dist, y=r.y, want_dres=want_dres, dgamma=g(id(bn.weight)),
+                                  dbeta=g(id(bn.bias)))
+
+    d = _blocks_backward(blocks, tape, d_feats, lowest, bn_bwd, wgrad)
     if lowest == 0:                                               # d: gradient of the maxpool output
-        a0 = bns[id(bn1)][3]
-        da0 = ops.rn_maxpool_bwd(a0, d)
-        dh0, _ = bn_bwd(bn1, da0)
+        da0 = ops.rn_maxpool_bwd(records[id(bn1)].y, d)
+        dh0, _ = bn_bwd(bn1, da0, False)
         del da0
         if id(conv1.weight) in grads:
             ops.rn_stem_wgrad(tape["planes"], tape["single"], dh0, grads[id(conv1.weight)])

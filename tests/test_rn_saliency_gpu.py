@@ -153,8 +153,12 @@ def test_taped_eval_forward_changes_nothing(precision):
         taped, names_taped = profiled(lambda: run(tape))
     assert names == eval_forward_names() and names_taped == names
     assert torch.equal(plain, taped)
-    assert tape["eval"] and len(tape["y"]) == 48 and len(tape["block_in"]) == 16 and len(tape["scale"]) == 53
-    assert tuple(tape["stem"].shape) == (4, 112, 112, 64) and tape["single"] is False and tape["planes"] is x.planes
+    records = tape["bn"]
+    assert tape["eval"] and len(records) == 53 and len(tape["block_in"]) == 16
+    assert sum(r.y is not None for r in records.values()) == 49          # the 48 block units with a ReLU, and the stem
+    assert all(r.scale is not None and r.x is None and r.mean is None and r.var is None for r in records.values())
+    stem = records[id(RN.parts(ens.cnn.cnn_model)[1])]
+    assert tuple(stem.y.shape) == (4, 112, 112, 64) and tape["single"] is False and tape["planes"] is x.planes
     with torch.no_grad():
         assert torch.equal(ens(C.images().cuda()), ens.mla(plain.reshape(-1, C.SLOTS, 2048)))
 
