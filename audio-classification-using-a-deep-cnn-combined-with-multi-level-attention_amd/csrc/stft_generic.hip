@@ -113,7 +113,7 @@ extern "C" int mla_dataset_frames(const float* examples, int64_t clips, int ex_p
                                   int stride, float* out, mla_stream_t stream) {
     MLA_REQUIRE(out && clips >= 0 && ex_per_clip >= 0 && ex_per_clip <= 4 && n_frames >= 1 && frame_len >= 1 && stride >= 0,
                 MLA_E_ARG, "bad dataset_frames arguments (a clip may hold at most 4 examples, dataset.py:321-322)");
-    MLA_REQUIRE((n_frames - 1) * stride + frame_len <= 384, MLA_E_SHAPE, "frames leave the 384-column spectrogram");
+    MLA_REQUIRE((int64_t(n_frames) - 1) * stride + frame_len <= 384, MLA_E_SHAPE, "frames leave the 384-column spectrogram");
     MLA_REQUIRE(examples || ex_per_clip == 0, MLA_E_ARG, "null examples");
     const int64_t total = clips * n_frames * 64 * frame_len;
     if (total == 0) return MLA_OK;

@@ -201,6 +201,91 @@ def test_argument_errors_are_reported_before_any_launch(L):
     expect(E_SHAPE, lib.mla_conv_wgrad(fake, fake, 3, 24, 16, 64, 128, fake, 1 << 30, fake, None), "not compiled")
 
 
+def test_dropin_front_end_argument_errors_are_reported_before_any_launch(L):
+    """The stand-alone entries of csrc/stft_generic.hip (mla_stft_magnitude, mla_mel_log, mla_dataset_frames, mla_postprocess,
+    mla_resample, mla_resample_length): every refusal is decided on the host, and work of zero size returns MLA_OK without a launch."""
+    lib = L.lib()
+    vp = ctypes.c_void_p
+    fake = vp(0x1000)                                # aligned, never dereferenced: no call below reaches a launch
+    E_ARG, E_SHAPE, E_SHORT = -1, -2, -3
+
+    def expect(code, rc, needle=None):
+        assert rc == code, (rc, lib.mla_last_error())
+        if needle:
+            assert needle in lib.mla_last_error().decode(), lib.mla_last_error()
+
+    def stft(n, win, hop, fft, signal=fake, window=fake, twiddle=fake, out=fake):
+        return lib.mla_stft_magnitude(signal, n, window, twiddle, win, hop, fft, out, None)
+
+    for fft in (3, 6, 400, 1000, 4095):
+        expect(E_SHAPE, stft(16000, 2, 1, fft), "power-of-two")
+    expect(E_SHAPE, stft(16000, 400, 160, 256), "power-of-two")              # fft < win
+    expect(E_SHAPE, stft(16000, 2, 1, 1))                                    # fft 1 is a power of two, below 2
+    expect(E_SHAPE, stft(16000, 400, 160, 8192), "4096")                     # above kMaxFft
+    expect(E_SHAPE, stft(16000, 0, 160, 512))
+    expect(E_SHAPE, stft(16000, 400, 0, 512))
+    for null in ("signal", "window", "twiddle", "out"):
+        expect(E_ARG, stft(16000, 400, 160, 512, **{null: None}), "null")
+    assert stft(399, 400, 160, 512) == 0 and stft(0, 1, 1, 2) == 0           # n < win: zero frames
+
+    def mel_log(frames, bins, bands, spec=fake, mel=fake, out=fake):
+        return lib.mla_mel_log(spec, mel, frames, bins, bands, 0.01, out, None)
+
+    expect(E_ARG, mel_log(3, 0, 64))
+    expect(E_ARG, mel_log(3, 257, 0))
+    expect(E_ARG, mel_log(-1, 257, 64))
+    expect(E_ARG, mel_log(3, 257, 64, spec=None))
+    expect(E_ARG, mel_log(3, 257, 64, mel=None))
+    expect(E_ARG, mel_log(3, 257, 64, out=None))
+    assert mel_log(0, 257, 64) == 0
+
+    def frames(clips, ex, n_frames, frame_len, stride, examples=fake, out=fake):
+        return lib.mla_dataset_frames(examples, clips, ex, n_frames, frame_len, stride, out, None)
+
+    expect(E_ARG, frames(1, 5, 10, 96, 32), "at most 4")
+    expect(E_ARG, frames(1, -1, 10, 96, 32))
+    expect(E_ARG, frames(-1, 4, 10, 96, 32))
+    expect(E_ARG, frames(1, 4, 0, 96, 32))
+    expect(E_ARG, frames(1, 4, 10, 0, 32))
+    expect(E_ARG, frames(1, 4, 10, 96, -1))
+    expect(E_ARG, frames(1, 4, 10, 96, 32, out=None))
+    expect(E_SHAPE, frames(1, 4, 10, 97, 32), "384")                         # (10 - 1) * 32 + 97 = 385
+    expect(E_SHAPE, frames(1, 4, 385, 1, 1), "384")
+    expect(E_SHAPE, frames(1, 4, 65537, 1, 65536), "384")                    # 65536 * 65536 wraps to 0 in 32 bits
+    expect(E_SHAPE, frames(1, 4, 2, 1, 2147483647), "384")
+    expect(E_ARG, frames(1, 4, 10, 96, 32, examples=None), "null examples")
+    assert frames(0, 0, 10, 96, 32, examples=None) == 0                       # null examples go with ex_per_clip = 0
+    assert frames(0, 4, 10, 96, 32) == 0
+
+    def postprocess(rows, x=fake, ev=fake, mu=fake, out=fake):
+        return lib.mla_postprocess(x, ev, mu, rows, out, None)
+
+    assert postprocess(0) == 0
+    expect(E_ARG, postprocess(-1))
+    for null in ("x", "ev", "mu", "out"):
+        expect(E_ARG, postprocess(3, **{null: None}))
+
+    def resample(n_in, sr_in, sr_out, n_out, nwin=32769, num_table=512, x=fake, win=fake, delta=fake, y=fake):
+        return lib.mla_resample(x, n_in, sr_in, sr_out, win, delta, nwin, num_table, y, n_out, None)
+
+    expect(E_SHAPE, resample(44100, 44100.0, 16000.0, 16001), "n_out")
+    expect(E_SHAPE, resample(44100, 44100.0, 16000.0, 15999), "n_out")
+    expect(E_SHORT, resample(1, 44100.0, 16000.0, 0), "too short")
+    expect(E_SHORT, resample(0, 44100.0, 16000.0, 0))
+    expect(E_SHAPE, resample(2048, 16000.0 * 1024, 16000.0, 2), "resolution")  # int(512 / 1024) = 0 table entries per input sample
+    expect(E_ARG, resample(44100, 0.0, 16000.0, 16000))
+    expect(E_ARG, resample(44100, 44100.0, -1.0, 16000))
+    expect(E_ARG, resample(-1, 44100.0, 16000.0, 0))
+    expect(E_ARG, resample(44100, 44100.0, 16000.0, 16000, nwin=1))
+    expect(E_ARG, resample(44100, 44100.0, 16000.0, 16000, num_table=0))
+    for null in ("x", "win", "delta", "y"):
+        expect(E_ARG, resample(44100, 44100.0, 16000.0, 16000, **{null: None}), "null")
+    assert lib.mla_resample_length(44100, 44100.0, 16000.0) == 16000 and lib.mla_resample_length(3, 44100.0, 16000.0) == 1
+    assert lib.mla_resample_length(1, 44100.0, 16000.0) == 0
+    for n_in, a, b in ((100, 0.0, 16000.0), (100, 44100.0, 0.0), (100, -44100.0, 16000.0), (100, float("nan"), 16000.0), (-1, 44100.0, 16000.0)):
+        assert lib.mla_resample_length(n_in, a, b) == -1
+
+
 def _build_c_example(L, tmp_path):
     """gcc -std=c99 on examples/c_abi_logmel.c against include/mla_hip.h + libmla_hip.so: the header is plain C."""
     L.lib()
