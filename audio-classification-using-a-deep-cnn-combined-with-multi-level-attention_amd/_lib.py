@@ -50,6 +50,9 @@ def lib():
         L.mla_logmel_build_tables.argtypes = [vp]
         L.mla_logmel_reference_tables.argtypes = [vp, vp]
         L.mla_logmel_examples.argtypes = [vp, ci, i64, i64, i64, vp, vp, ci, vp]
+        L.mla_logmel_bwd_table_floats.restype = i64
+        L.mla_logmel_bwd_build_tables.argtypes = [vp]
+        L.mla_logmel_examples_bwd.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, i64, vp]
         L.mla_logmel_conv1.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, vp]
         L.mla_logmel_bags.argtypes = [vp, ci, i64, i64, i64, vp, vp, ci, ci, vp, vp, ci, vp]
         L.mla_timeline_counts.argtypes = [i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]

@@ -14,6 +14,8 @@ Three stages, one Function each, chained by ordinary autograd (reshapes / transp
 * ``FeaturesFn``   -- the conv stack (vggish.py:108-118): ``VGGFeatures.forward``
 * ``EmbeddingsFn`` -- the three Linear + ReLU layers (vggish.py:13-19): ``VGGEmbeddings.forward``
 * ``HeadFn``       -- the whole multi-level-attention head (model.py:258-269): ``MultiLevelAttention.forward``
+* ``LogMelFn``     -- the log-mel front-end in front of them, opt-in (``frontend.waveforms_to_examples_differentiable``): carries
+  the examples' gradient on to the waveform
 * ``TrunkFn`` / ``FcFn`` -- the ResNet-50 trunk (train mode, when its trunk backward is on) and its fc (model.py:128-149)
 
 ``TrainStep`` (train.py of this package) stays the fast path: one flat gradient buffer, fused Adam, SyncBN and bucketed
@@ -73,6 +75,29 @@ class FeaturesFn(torch.autograd.Function):
         if dx is not None:
             dx = dx.reshape(ctx.x_shape)
         return (None, None, dx) + tuple(grads.get(n) for n, _ in ctx.names)
+
+
+class LogMelFn(torch.autograd.Function):
+    """apply(pcm): (W, n) float32 device PCM -> (W * N, 96, 64) float32 log-mel examples, the launch and the bits of
+    frontend.waveforms_to_examples; the backward is frontend.waveforms_to_examples_backward on the saved waveform (the spectra are
+    recomputed, nothing else is kept). See that function for the conditioning of the gradient."""
+
+    @staticmethod
+    def forward(ctx, pcm):
+        from . import frontend
+        if pcm.dtype != torch.float32:
+            raise TypeError("LogMelFn differentiates with respect to a float32 waveform, got %s" % (pcm.dtype,))
+        x = pcm.detach()
+        if x.dim() == 2 and x.stride(1) != 1:
+            x = x.contiguous()
+        ctx.save_for_backward(x)
+        return frontend.waveforms_to_examples(x, out_dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, d_examples):
+        from . import frontend
+        x, = ctx.saved_tensors
+        return frontend.waveforms_to_examples_backward(x, d_examples.float().contiguous())
 
 
 class EmbeddingsFn(torch.autograd.Function):

@@ -256,6 +256,65 @@ def waveforms_to_examples(pcm, out_dtype=torch.float32, out=None):
     return out
 
 
+_bwd_tables = {}
+
+
+def device_bwd_tables(device):
+    """Constant tables of the log-mel backward kernel (transposed mel step, split twiddles), built by the library in float64."""
+    key = str(device)
+    if key not in _bwd_tables:
+        L = _lib.lib()
+        host = np.zeros(int(L.mla_logmel_bwd_table_floats()), dtype=np.float32)
+        _lib.check(L.mla_logmel_bwd_build_tables(host.ctypes.data_as(ctypes.c_void_p)))
+        _bwd_tables[key] = torch.from_numpy(host).to(device)
+    return _bwd_tables[key]
+
+
+def waveforms_to_examples_backward(pcm, grad_examples, out=None):
+    """The gradient of ``waveforms_to_examples(pcm)`` (float32 examples) with respect to the waveform: (W, n) device PCM (float32, or
+    int16 meaning pcm / 32768: the gradient is with respect to that float value) and grad_examples (W * N, 96, 64) float32 ->
+    (W, n) float32, one launch of csrc/logmel_bwd.hip. The frames' spectra are recomputed from `pcm`. Every element of the result
+    is stored exactly once -- samples behind the last used frame get 0.0 -- so `out`, when given ((W, n) float32, unit stride
+    along the samples), needs no zeroing; the result is deterministic and a row's bits do not depend on the batch.
+
+    Conditioning: the function passes a bin's gradient along its unit phasor X_k / |X_k|, which float32 only knows where |X_k| is
+    well above the frame's rounding noise. On noise-like audio the result is within ~1e-6 of the float64 gradient; on a pure tone,
+    whose bins lie at 1e-17 of the peak, any float32 evaluation (torch's included) is tens of percent off. NaN / Inf in either
+    input are outside the contract."""
+    assert pcm.dim() == 2 and pcm.is_cuda and pcm.stride(1) == 1 and pcm.dtype in (torch.float32, torch.int16)
+    n_wave, n_samples = pcm.shape
+    _, n_ex = counts(n_samples)
+    g = grad_examples
+    assert g.is_cuda and g.dtype == torch.float32 and g.numel() == n_wave * n_ex * 96 * 64, "grad_examples must be (W * N, 96, 64) float32"
+    g = g.contiguous()
+    if out is None:
+        out = torch.empty((n_wave, n_samples), dtype=torch.float32, device=pcm.device)
+    else:
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n_wave, n_samples) and (n_samples == 0 or out.stride(1) == 1)
+    if n_wave == 0:
+        return out
+    pcm_code = {torch.float32: _lib.F32, torch.int16: _lib.I16}[pcm.dtype]
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("logmel_bwd", _lib.lib().mla_logmel_examples_bwd,
+                          vp(pcm.data_ptr()), pcm_code, n_wave, n_samples, pcm.stride(0) if n_wave > 1 else n_samples,
+                          vp(device_tables(pcm.device).data_ptr()), vp(device_bwd_tables(pcm.device).data_ptr()),
+                          vp(g.data_ptr()) if g.numel() else None, vp(out.data_ptr()), out.stride(0) if n_wave > 1 else n_samples,
+                          _lib.stream_ptr()))
+    return out
+
+
+def waveforms_to_examples_differentiable(pcm):
+    """``waveforms_to_examples`` behind autograd: (W, n) float32 device PCM that may require grad -> (W * N, 96, 64) float32
+    examples attached to the graph (differentiable.LogMelFn: the forward is the same launch and gives the same bits, the backward
+    is waveforms_to_examples_backward). With ``set_input_grad(True)`` on the model the reference's literal loop fills pcm.grad:
+
+        ex = waveforms_to_examples_differentiable(pcm); loss = crit(clf(ex.view(B, T, 1, 96, 64)), y); loss.backward()
+    """
+    from . import differentiable
+    return differentiable.LogMelFn.apply(pcm)
+
+
 def logmel_bags(pcm, counts, n_frames=10, stride=32, out_dtype=torch.float32, out=None):
     """(B, n) device rows of 16 kHz mono PCM (float32 or int16) holding counts[c] <= 4 whole 0.96 s examples each -> the
     (B, n_frames, 1, 64, 96) bag tensor of the reference's native VGGish dataset path (dataset.py:318-324 create_spec + :329-363

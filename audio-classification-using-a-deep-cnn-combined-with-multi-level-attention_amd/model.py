@@ -390,6 +390,24 @@ class Ensemble(nn.Module):
         scores, grad = self.saliency(ex, target, times_input)
         return scores, ex, grad
 
+    def waveform_saliency(self, pcm, target=None, times_input=False):
+        """Which SAMPLES made the model say so: (B, n_samples) 16 kHz PCM on the device (float32, or int16 meaning pcm / 32768), one
+        bag of `slots` examples per row -> (scores (B, classes), detached; grad (B, n_samples) float32 = d scores[b, target_b] /
+        d pcm[b], multiplied by the float waveform with times_input). It is saliency_waveforms' map over the float32 examples carried
+        one link further by the log-mel backward kernel (frontend.waveforms_to_examples_backward, which also states how the
+        gradient is conditioned); scores, target and the eval-mode / VGGish-only rules are saliency's. No parameter's .grad, no
+        buffer and no switch of the module is changed."""
+        self._waveforms_only_vggish()
+        if self.training:
+            raise RuntimeError("waveform_saliency runs in eval mode only, as saliency does: batch statistics would couple the bags of a "
+                               "batch; call eval() first")
+        from . import frontend
+        scores, _, grad = self.saliency_waveforms(pcm, target, False)
+        grad = frontend.waveforms_to_examples_backward(pcm, grad.reshape(-1, S_VGGISH_SHAPE[0], S_VGGISH_SHAPE[1]))
+        if times_input:
+            grad = grad * (pcm.float() / 32768.0 if pcm.dtype == torch.int16 else pcm.float())
+        return scores, grad
+
     def saliency_images(self, x, target=None, times_input=False):
         """saliency for the ResNet branch: x (B, slots, 1, 224, 224) spectrogram images -> (scores (B, classes), detached; grad
         float32 of x's shape = d scores[b, target_b] / d x[b], multiplied by x with times_input). target as in saliency(). Eval mode

@@ -87,6 +87,26 @@ int mla_logmel_examples(const void* pcm, int pcm_dtype, int64_t n_wave, int64_t 
                         int64_t wave_stride, const float* tables, void* out, int out_dtype,
                         mla_stream_t stream);
 
+/* Gradient of mla_logmel_examples (MLA_F32 output) with respect to the WAVEFORM: the adjoint of frame -> Hann -> |rfft 512|
+ * (mel_features.py:71-92) -> mel -> log(. + 0.01) (mel_features.py:220-223) -> 96-frame examples (vggish_input.py:56-76).
+ * pcm / pcm_dtype / n_wave / n_samples / wave_stride / tables as for mla_logmel_examples (for MLA_I16 the gradient is with respect
+ * to the float value pcm / 32768); bwd_tables: device copy of the mla_logmel_bwd_table_floats() floats mla_logmel_bwd_build_tables
+ * writes (the transposed mel step, bin -> its <= 2 bands, and the split twiddles; built in double precision on the host from the
+ * same mel matrix); d_examples (n_wave * examples, 96, 64) f32 = dL / d out; d_wave[n_wave][d_wave_stride] f32 = dL / d pcm.
+ * The frames' spectra are recomputed. One launch, no workspace, no atomics: every d_wave[w][s], s < n_samples, is stored exactly
+ * once (the caller zeroes nothing), a sample's <= 3 frames are summed in ascending frame order, samples from
+ * 160 (96 examples - 1) + 400 on get exactly 0, and a row's bits depend neither on n_wave nor on the strides. |X_k| = 0 passes no
+ * gradient (torch's sgn(0) = 0), never NaN or Inf. Conditioning: X_k / |X_k| is only meaningful in float32 where |X_k| is well
+ * above the frame's rounding noise; on signals with bins far below their peak (a pure tone) ANY float32 evaluation is far from the
+ * float64 gradient. That belongs to the function, not to this kernel.
+ * Errors, all before any launch: null pointer, negative size, stride < n_samples -> MLA_E_ARG; n_samples < 240 -> MLA_E_SHORT;
+ * pcm_dtype -> MLA_E_DTYPE. n_wave == 0 returns MLA_OK and touches nothing; examples == 0 writes zeros (d_examples may be null). */
+int64_t mla_logmel_bwd_table_floats(void);
+int     mla_logmel_bwd_build_tables(float* host_out);
+int mla_logmel_examples_bwd(const void* pcm, int pcm_dtype, int64_t n_wave, int64_t n_samples, int64_t wave_stride,
+                            const float* tables, const float* bwd_tables, const float* d_examples, float* d_wave,
+                            int64_t d_wave_stride, mla_stream_t stream);
+
 /* Stand-alone stages for ARBITRARY configurations of the reference API (any window / hop /
  * power-of-two fft_length <= 4096, any mel layout); the VGGish configuration on the hot path
  * uses mla_logmel_examples instead.
