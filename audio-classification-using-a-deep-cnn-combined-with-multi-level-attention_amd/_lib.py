@@ -71,6 +71,10 @@ def lib():
         L.mla_melspec_workspace_bytes.argtypes = [i64, i64, i64]
         L.mla_melspec_db.argtypes = [vp, i64, i64, i64, i64, i64, cf, vp, vp, vp, vp]
         L.mla_melspec_images.argtypes = [vp, vp, i64, i64, i64, i64, cf, i64, i64, i64, vp, vp]
+        L.mla_melspec_bwd_workspace_bytes.restype = i64
+        L.mla_melspec_bwd_workspace_bytes.argtypes = [i64, i64, i64, i64]
+        L.mla_melspec_images_bwd.argtypes = [vp, vp, vp, i64, i64, i64, i64, cf, i64, i64, i64, ci, vp, vp]
+        L.mla_melspec_db_bwd.argtypes = [vp, i64, i64, i64, i64, i64, cf, vp, vp, vp, vp, i64, vp]
         L.mla_melspec_track_counts.argtypes = [i64, i64] + [ctypes.POINTER(i64)] * 4
         L.mla_melspec_track_db.argtypes = [vp, i64, i64, i64, vp, vp, i64, cf, vp, vp, vp, vp, vp]
         L.mla_melspec_track_images.argtypes = [vp, vp, i64, vp, vp, i64, cf, i64, i64, vp, vp]

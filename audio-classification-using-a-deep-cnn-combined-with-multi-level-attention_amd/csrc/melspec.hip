@@ -27,6 +27,7 @@
 #include <hip/hip_bf16.h>
 
 #include "common.h"
+#include "melspec_args.h"
 #include "melspec_core.h"
 #include "melspec_tables.h"
 #include "melspec_track_core.h"
@@ -272,21 +273,6 @@ extern "C" int mla_melspec_build_tables(double sr, int64_t n_mels, float* host_o
     return melspec::build_tables(sr, n_mels, host_out) == 0 ? MLA_OK : ::mla::fail(MLA_E_ARG, "melspec tables could not be built");
 }
 
-namespace {
-int check_signal(int64_t n_samples, int64_t hop, int64_t n_mels) {
-    MLA_REQUIRE(hop >= 1, MLA_E_ARG, "melspec hop %lld < 1", (long long)hop);
-    MLA_REQUIRE(n_mels >= 1 && n_mels <= kMaxMels, MLA_E_ARG, "melspec n_mels %lld outside [1, %d]", (long long)n_mels, kMaxMels);
-    MLA_REQUIRE(n_samples >= kMinSamples, MLA_E_SHORT, "melspec needs at least %d samples per clip for reflect padding by %d (got %lld)",
-                kMinSamples, kPad, (long long)n_samples);
-    MLA_REQUIRE(n_samples <= (1 << 30), MLA_E_SHAPE, "melspec clips longer than 2^30 samples are not supported (got %lld)", (long long)n_samples);
-    return MLA_OK;
-}
-int64_t runs_of(int64_t n_samples, int64_t hop) {
-    const int64_t frames = 1 + n_samples / hop, per = run_frames(hop);
-    return (frames + per - 1) / per;
-}
-}  // namespace
-
 extern "C" int64_t mla_melspec_workspace_bytes(int64_t clips, int64_t n_samples, int64_t hop) {
     if (clips < 0 || n_samples < 0 || hop < 1) return -1;
     return clips * runs_of(n_samples, hop) * int64_t(sizeof(float));
@@ -311,15 +297,6 @@ extern "C" int mla_melspec_db(const float* pcm, int64_t clips, int64_t n_samples
 }
 
 namespace {
-int check_images(int64_t frames, float top_db, int64_t n_images, int64_t image_w, int64_t image_stride) {
-    MLA_REQUIRE(top_db >= 0.f, MLA_E_ARG, "melspec top_db must be non-negative (got %g)", double(top_db));
-    MLA_REQUIRE(n_images >= 1 && image_w >= 1 && image_stride >= 0, MLA_E_ARG, "bad melspec image arguments (%lld images of width %lld, stride %lld)",
-                (long long)n_images, (long long)image_w, (long long)image_stride);
-    MLA_REQUIRE(image_w <= frames && image_stride <= frames && (n_images - 1) * image_stride + image_w <= frames, MLA_E_SHAPE,
-                "images leave the %lld-column spectrogram (%lld images of width %lld, stride %lld)", (long long)frames, (long long)n_images,
-                (long long)image_w, (long long)image_stride);
-    return MLA_OK;
-}
 template <typename OutT>
 int launch_images(const float* db, const float* workspace, int64_t clips, int64_t frames, int64_t runs, int64_t n_mels, float top_db,
                   int64_t n_images, int64_t image_w, int64_t image_stride, OutT* out, mla_stream_t stream) {

@@ -83,18 +83,48 @@ def clips_to_images(pcm, overlap=True):
     """(clips, SAMPLES_NUM_RESNET) float32 device PCM at SR_RESNET -> (clips, T, 1, 224, 224) float32, the tensor load_hdf5
     stores for cnn_type="resnet" (dataset.py:243-254) and Ensemble consumes; bit-identical to create_spec + split per clip.
     Rows are exactly SAMPLES_NUM_RESNET samples: the caller cuts longer clips and zero-fills shorter ones, as load_hdf5 means to."""
+    pcm = _resnet_rows(pcm, "clips_to_images")
+    hop, step = _image_geometry(overlap)
+    db, ws = frontend.melspec_db_unclipped(pcm, SR_RESNET, S_RESNET_SHAPE[0], hop)
+    return frontend.melspec_images(db, ws, SAMPLES_NUM_RESNET, hop, 80.0, T, S_RESNET_SHAPE[1], step)
+
+
+def _resnet_rows(pcm, what):
     assert pcm.dim() == 2 and pcm.is_cuda
     if pcm.shape[1] != SAMPLES_NUM_RESNET:
-        raise ValueError("clips_to_images takes rows of exactly %d samples (%d s at %d Hz), got %d"
-                         % (SAMPLES_NUM_RESNET, SAMPLES_NUM_RESNET // SR_RESNET, SR_RESNET, pcm.shape[1]))
-    if pcm.dtype != torch.float32:
-        pcm = pcm.float()
-    y_size, x_size = S_RESNET_SHAPE
+        raise ValueError("%s takes rows of exactly %d samples (%d s at %d Hz), got %d"
+                         % (what, SAMPLES_NUM_RESNET, SAMPLES_NUM_RESNET // SR_RESNET, SR_RESNET, pcm.shape[1]))
+    return pcm if pcm.dtype == torch.float32 else pcm.float()
+
+
+def _image_geometry(overlap):
+    """(hop length, columns between the starts of two images) of clips_to_images."""
+    x_size = S_RESNET_SHAPE[1]
     hop = resnet_hop_length(SAMPLES_NUM_RESNET, x_size, overlap)
     width = frontend.melspec_frames(SAMPLES_NUM_RESNET, hop)
-    step = (width - x_size) // (T - 1) if overlap else x_size
+    return hop, (width - x_size) // (T - 1) if overlap else x_size
+
+
+def clips_to_images_backward(pcm, grad_images, overlap=True, floor_grad=True):
+    """The gradient of ``clips_to_images(pcm, overlap)`` with respect to the waveform: (clips, SAMPLES_NUM_RESNET) float32 device PCM
+    and grad_images (clips, T, 1, 224, 224) float32 -> (clips, SAMPLES_NUM_RESNET) float32. The spectrogram and its maxima are
+    computed again (the forward's first launch, same bits), then the two launches of csrc/melspec_bwd.hip:
+    frontend.melspec_images_backward (which explains floor_grad) and frontend.melspec_db_backward. float32 whatever the model's
+    precision; deterministic, and a clip's gradient does not depend on the batch."""
+    pcm = _resnet_rows(pcm, "clips_to_images_backward")
+    hop, step = _image_geometry(overlap)
+    y_size, x_size = S_RESNET_SHAPE
     db, ws = frontend.melspec_db_unclipped(pcm, SR_RESNET, y_size, hop)
-    return frontend.melspec_images(db, ws, SAMPLES_NUM_RESNET, hop, 80.0, T, x_size, step)
+    d_db = frontend.melspec_images_backward(grad_images.float(), db, ws, SAMPLES_NUM_RESNET, hop, 80.0, T, x_size, step, floor_grad)
+    return frontend.melspec_db_backward(pcm, d_db, SR_RESNET, y_size, hop)
+
+
+def clips_to_images_differentiable(pcm, overlap=True):
+    """``clips_to_images`` behind autograd: (clips, SAMPLES_NUM_RESNET) float32 device PCM that may require grad -> images attached
+    to the graph (differentiable.MelDbImagesFn: the forward is the same two launches and gives the same bits, the backward is the
+    two launches of clips_to_images_backward with the floor's own gradient, as torch.autograd would give it)."""
+    from . import differentiable
+    return differentiable.MelDbImagesFn.apply(pcm, overlap)
 
 
 def _host_recording(x, index):

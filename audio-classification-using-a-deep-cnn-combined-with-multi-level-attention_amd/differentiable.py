@@ -16,6 +16,8 @@ Three stages, one Function each, chained by ordinary autograd (reshapes / transp
 * ``HeadFn``       -- the whole multi-level-attention head (model.py:258-269): ``MultiLevelAttention.forward``
 * ``LogMelFn``     -- the log-mel front-end in front of them, opt-in (``frontend.waveforms_to_examples_differentiable``): carries
   the examples' gradient on to the waveform
+* ``MelDbImagesFn`` -- the ResNet branch's mel-dB image front-end, opt-in (``dataset.clips_to_images_differentiable``): carries the
+  images' gradient on to the waveform
 * ``TrunkFn`` / ``FcFn`` -- the ResNet-50 trunk (train mode, when its trunk backward is on) and its fc (model.py:128-149)
 
 ``TrainStep`` (train.py of this package) stays the fast path: one flat gradient buffer, fused Adam, SyncBN and bucketed
@@ -98,6 +100,37 @@ class LogMelFn(torch.autograd.Function):
         from . import frontend
         x, = ctx.saved_tensors
         return frontend.waveforms_to_examples_backward(x, d_examples.float().contiguous())
+
+
+class MelDbImagesFn(torch.autograd.Function):
+    """apply(pcm, overlap): (clips, SAMPLES_NUM_RESNET) float32 device PCM -> (clips, T, 1, 224, 224) float32 mel-dB images, the two
+    launches and the bits of dataset.clips_to_images; the backward is the two launches of csrc/melspec_bwd.hip on the saved
+    waveform, spectrogram and maxima (the frames' spectra are recomputed), with the floor's own gradient as torch.autograd gives it."""
+
+    @staticmethod
+    def forward(ctx, pcm, overlap):
+        from . import dataset, frontend
+        if pcm.dtype != torch.float32:
+            raise TypeError("MelDbImagesFn differentiates with respect to a float32 waveform, got %s" % (pcm.dtype,))
+        x = dataset._resnet_rows(pcm.detach(), "clips_to_images_differentiable")
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        hop, step = dataset._image_geometry(overlap)
+        y_size, x_size = dataset.S_RESNET_SHAPE
+        db, ws = frontend.melspec_db_unclipped(x, dataset.SR_RESNET, y_size, hop)
+        ctx.save_for_backward(x, db, ws)
+        ctx.geometry = (hop, step)
+        return frontend.melspec_images(db, ws, dataset.SAMPLES_NUM_RESNET, hop, 80.0, dataset.T, x_size, step)
+
+    @staticmethod
+    def backward(ctx, d_images):
+        from . import dataset, frontend
+        x, db, ws = ctx.saved_tensors
+        hop, step = ctx.geometry
+        y_size, x_size = dataset.S_RESNET_SHAPE
+        d_db = frontend.melspec_images_backward(d_images.float().contiguous(), db, ws, dataset.SAMPLES_NUM_RESNET, hop, 80.0, dataset.T, x_size,
+                                                step, True)
+        return frontend.melspec_db_backward(x, d_db, dataset.SR_RESNET, y_size, hop), None
 
 
 class EmbeddingsFn(torch.autograd.Function):

@@ -473,6 +473,79 @@ def melspec_images(db, ws, n_samples, hop_length, top_db, n_images, image_w, ima
     return out
 
 
+def melspec_images_backward(grad_images, db, ws, n_samples, hop_length, top_db, n_images, image_w, image_stride, floor_grad=True, out=None):
+    """The gradient of ``melspec_images`` with respect to `db`: grad_images (clips, n_images, 1, n_mels, image_w) float32, with the
+    `db` and `ws` of melspec_db_unclipped -> d_db (clips, n_mels, frames). Overlapping images add; a cell below the floor passes
+    nothing. floor_grad=True (torch.autograd's answer) adds the floor's own gradient, the sum over the clipped cells, to the cell
+    that holds the clip's maximum (the first in (band, column) order where several do); floor_grad=False treats the floor as a
+    constant. One launch of csrc/melspec_bwd.hip; every element is stored exactly once, so `out`, when given (contiguous, db's shape),
+    needs no zeroing."""
+    clips, n_mels, frames = db.shape
+    g = grad_images
+    assert g.is_cuda and g.dtype == torch.float32 and g.numel() == clips * int(n_images) * n_mels * int(image_w), \
+        "grad_images must be (clips, n_images, 1, n_mels, image_w) float32"
+    g = g.contiguous()
+    if out is None:
+        out = torch.empty((clips, n_mels, frames), dtype=torch.float32, device=db.device)
+    else:
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(db.shape) and out.is_contiguous()
+    d_db = out
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_images_bwd", _lib.lib().mla_melspec_images_bwd, vp(g.data_ptr()), vp(db.data_ptr()), vp(ws.data_ptr()), clips,
+                          int(n_samples), int(hop_length), n_mels, float(top_db), int(n_images), int(image_w), int(image_stride),
+                          int(bool(floor_grad)), vp(d_db.data_ptr()), _lib.stream_ptr()))
+    return d_db
+
+
+def melspec_db_backward(pcm, d_db, sr, n_mels, hop_length, out=None):
+    """The gradient of ``melspec_db_unclipped`` with respect to the waveform: (clips, n) float32 device PCM and d_db (clips, n_mels,
+    frames) -> d_pcm (clips, n) float32. The frames' spectra are recomputed from `pcm`; a band whose power is at or below amin
+    passes nothing (an all-zero clip gives exact zeros). Every sample is stored exactly once, so `out`, when given ((clips, n)
+    float32, unit stride along the samples), needs no zeroing; deterministic, and a row's bits do not depend on the batch."""
+    assert pcm.dim() == 2 and pcm.is_cuda and pcm.dtype == torch.float32 and (pcm.shape[1] <= 1 or pcm.stride(1) == 1)
+    clips, n = pcm.shape
+    L = _lib.lib()
+    ws_bytes = int(L.mla_melspec_bwd_workspace_bytes(clips, n, int(hop_length), int(n_mels)))
+    frames = melspec_frames(n, hop_length)
+    if ws_bytes < 0 or frames < 0:
+        raise ValueError("hop_length must be a positive integer (got %r)" % (hop_length,))
+    assert d_db.is_cuda and d_db.dtype == torch.float32 and tuple(d_db.shape) == (clips, int(n_mels), frames), "d_db must be (clips, n_mels, frames) float32"
+    d_db = d_db.contiguous()
+    if out is None:
+        out = torch.empty((clips, n), dtype=torch.float32, device=pcm.device)
+    else:
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (clips, n) and (n <= 1 or out.stride(1) == 1)
+    tab = melspec_tables(pcm.device, sr, n_mels)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=pcm.device)
+    vp = ctypes.c_void_p
+    from . import ops
+    _lib.check(ops._timed("melspec_db_bwd", L.mla_melspec_db_bwd, vp(pcm.data_ptr()), clips, n, pcm.stride(0) if clips > 1 else n, int(hop_length),
+                          int(n_mels), MELSPEC_AMIN, vp(tab.data_ptr()), vp(d_db.data_ptr()), vp(ws.data_ptr()), vp(out.data_ptr()),
+                          out.stride(0) if clips > 1 else n, _lib.stream_ptr()))
+    return out
+
+
+def melspectrogram_db_backward(pcm, grad_db, sr, n_mels, hop_length, top_db=80.0, floor_grad=True, center=True, htk=False, fmin=0.0, fmax=None):
+    """The gradient of ``melspectrogram_db(pcm, sr, n_mels, hop_length, top_db)`` with respect to `pcm`: grad_db (clips, n_mels,
+    frames) float32 -> (clips, n) float32; top_db=None differentiates the unclipped spectrogram. The forward's two kernels run again
+    (the spectrogram and its maxima are not kept), then the two backward launches. Built for the centred spectrogram with librosa's
+    default Slaney basis only: the HTK / center=False path of the VGGish librosa branch is out of scope."""
+    if not center or htk or fmin != 0.0 or (fmax is not None and float(fmax) != float(sr) / 2):
+        raise NotImplementedError("melspectrogram_db_backward differentiates the centred spectrogram with librosa's default mel basis "
+                                  "(center=True, htk=False, fmin=0, fmax=sr/2); the HTK / center=False path of the VGGish librosa branch "
+                                  "is out of scope")
+    if pcm.shape[1] < 1025:
+        raise ValueError("melspectrogram_db_backward needs at least 1025 samples per clip (got %d)" % pcm.shape[1])
+    if top_db is not None and top_db < 0:
+        raise ValueError("top_db must be non-negative")
+    if top_db is None:
+        return melspec_db_backward(pcm, grad_db, sr, n_mels, hop_length)
+    db, ws = melspec_db_unclipped(pcm, sr, n_mels, hop_length)
+    d_db = melspec_images_backward(grad_db, db, ws, pcm.shape[1], hop_length, top_db, 1, db.shape[2], 0, floor_grad)
+    return melspec_db_backward(pcm, d_db, sr, n_mels, hop_length)
+
+
 # ---- the ResNet branch over time: tracks of recordings of any length and the distinct images of their windows ----
 TRACK_SR, TRACK_MELS, TRACK_HOP, TRACK_IMAGE_W, TRACK_IMAGE_STEP, TRACK_WINDOW_IMAGES = 22050, 224, 98, 224, 75, 10
 

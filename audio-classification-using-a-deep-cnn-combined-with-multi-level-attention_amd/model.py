@@ -396,7 +396,7 @@ class Ensemble(nn.Module):
         d pcm[b], multiplied by the float waveform with times_input). It is saliency_waveforms' map over the float32 examples carried
         one link further by the log-mel backward kernel (frontend.waveforms_to_examples_backward, which also states how the
         gradient is conditioned); scores, target and the eval-mode / VGGish-only rules are saliency's. No parameter's .grad, no
-        buffer and no switch of the module is changed."""
+        buffer and no switch of the module is changed. The ResNet branch's counterpart is clip_saliency()."""
         self._waveforms_only_vggish()
         if self.training:
             raise RuntimeError("waveform_saliency runs in eval mode only, as saliency does: batch statistics would couple the bags of a "
@@ -453,6 +453,27 @@ class Ensemble(nn.Module):
         images = dataset.clips_to_images(pcm, overlap)
         scores, grad = self.saliency_images(images, target, times_input)
         return scores, images, grad
+
+    def clip_saliency(self, pcm, target=None, times_input=False, overlap=True, floor_grad=True):
+        """Which SAMPLES made the ResNet branch say so: (B, SAMPLES_NUM_RESNET) float32 PCM at 22 050 Hz on the device -> (scores
+        (B, classes), detached; grad (B, SAMPLES_NUM_RESNET) float32 = d scores[b, target_b] / d pcm[b], multiplied by the waveform
+        with times_input). It is saliency_clips' map over the mel-dB images carried one link further by the mel-dB backward kernels
+        (dataset.clips_to_images_backward; floor_grad=False treats power_to_db's top_db floor as a constant instead of passing its
+        gradient to the clip's loudest cell). scores, target and the eval-mode / ResNet-only rules are saliency_images'; the
+        front-end and its backward are float32 in every precision mode. No parameter's .grad, no buffer and no switch of the
+        module is changed."""
+        if self.cnn_type != "resnet":
+            raise NotImplementedError("clip_saliency differentiates the ResNet branch down to its 22 050 Hz clips; cnn_type 'vggish' takes "
+                                      "16 kHz PCM through waveform_saliency()")
+        if self.training:
+            raise RuntimeError("clip_saliency runs in eval mode only, as saliency_images does: batch statistics would couple the bags of a "
+                               "batch; call eval() first")
+        from . import dataset
+        scores, _, grad = self.saliency_clips(pcm, target, False, overlap)
+        grad = dataset.clips_to_images_backward(pcm, grad, overlap, floor_grad)
+        if times_input:
+            grad = grad * pcm.float()
+        return scores, grad
 
     def _librosa_bags(self, what, frames_fn, source, overlap):
         """The VGGish branch on the reference's librosa dataset path (load_hdf5(cnn_type="vggish", use_librosa=True), mnemonic

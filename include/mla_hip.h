@@ -206,6 +206,31 @@ int mla_melspec_db(const float* pcm, int64_t clips, int64_t n_samples, int64_t c
 int mla_melspec_images(const float* db, const float* workspace, int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels,
                        float top_db, int64_t n_images, int64_t image_w, int64_t image_stride, float* out, mla_stream_t stream);
 
+/* ---- the gradient of mla_melspec_db + mla_melspec_images with respect to the waveform ----
+ * float32, deterministic, no atomics; a clip's gradient depends on that clip alone (not on the batch, the strides or the grid).
+ * Errors of the three entries, all before any launch, with the codes and texts of the forward entries: null or misaligned
+ * pointer, hop < 1, n_mels outside [1, 1024], a stride < n_samples, amin <= 0, top_db < 0 -> MLA_E_ARG; n_samples < 1025 ->
+ * MLA_E_SHORT; images that leave the spectrogram -> MLA_E_SHAPE. clips == 0 returns MLA_OK and touches nothing. */
+
+/* Bytes of the workspace mla_melspec_db_bwd needs: per clip and run of up to 32 frames one span of overlap-added frame gradients
+ * (-1 for bad arguments). */
+int64_t mla_melspec_bwd_workspace_bytes(int64_t clips, int64_t n_samples, int64_t hop, int64_t n_mels);
+/* grad_images[clips][n_images][1][n_mels][image_w] = dL / d out of mla_melspec_images, with the `db` and `workspace` the forward
+ * produced for the same clips -> d_db[clips][n_mels][frames] = dL / d db: overlapping images add; a cell below the floor
+ * max(db[c]) - top_db passes nothing and a cell above it passes its gradient. With floor_grad != 0 the floor's own gradient, the
+ * sum over the clipped cells, is added to the cell that holds the maximum (the first in (band, column) order where several do;
+ * torch spreads it evenly); with floor_grad == 0 the floor is a constant. Every element of d_db is stored exactly once. */
+int mla_melspec_images_bwd(const float* grad_images, const float* db, const float* workspace, int64_t clips, int64_t n_samples,
+                           int64_t hop, int64_t n_mels, float top_db, int64_t n_images, int64_t image_w, int64_t image_stride,
+                           int floor_grad, float* d_db, mla_stream_t stream);
+/* pcm as mla_melspec_db took it, d_db[clips][n_mels][frames] -> d_pcm[clips][d_stride] = dL / d pcm (the first n_samples of each
+ * row are stored, each exactly once: the caller zeroes nothing; nothing at or behind n_samples is touched). The frames' spectra
+ * are recomputed from pcm; `tables` are mla_melspec_build_tables' (the transposed mel step needs no table of its own);
+ * bwd_workspace holds mla_melspec_bwd_workspace_bytes. A band with S <= amin passes nothing: an all-zero clip gives exact zeros. */
+int mla_melspec_db_bwd(const float* pcm, int64_t clips, int64_t n_samples, int64_t clip_stride, int64_t hop, int64_t n_mels,
+                       float amin, const float* tables, const float* d_db, float* bwd_workspace, float* d_pcm, int64_t d_stride,
+                       mla_stream_t stream);
+
 /* ---- ResNet branch over time: a recording of any length scored in 4 s windows at a hop of hop_images / 3 s ----
  * Extends create_spec(cnn_type="resnet") + split (dataset.py:309-316, :329-363) beyond the reference's loader, which cuts every
  * recording at 4 s (dataset.py:233-237); the configuration is the reference's: 22 050 Hz, 224 bands, hop 98, ten images of 224
