@@ -24,6 +24,12 @@ class MlaError(RuntimeError):
         self.code = code
 
 
+class AdamGroup(ctypes.Structure):
+    """mla_adam_group_t"""
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("decoupled", ctypes.c_int), ("amsgrad", ctypes.c_int)]
+
+
 def declared_symbols():
     """Function names declared in include/mla_hip.h."""
     text = open(HEADER).read()
@@ -160,6 +166,12 @@ def lib():
         L.mla_adam_step_dev.argtypes = [vp, vp, vp, vp, i64, cf, cf, cf, vp, vp]
         L.mla_adam_prepare.argtypes = [vp, cf, cf, cf, i64, vp]
         L.mla_counter_add.argtypes = [vp, i64, vp]
+        L.mla_adam_groups_table.argtypes = [vp, vp, i64, ci, vp, i64, vp]
+        L.mla_adam_groups_prepare.argtypes = [vp, vp, ci, i64, vp]
+        L.mla_adam_grouped_step.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, ci, vp, vp]
+        L.mla_grad_norm_workspace_bytes.restype = i64
+        L.mla_grad_norm_workspace_bytes.argtypes = []
+        L.mla_grad_norm.argtypes = [vp, i64, cf, vp, vp, vp]
         L.mla_comm_unique_id.argtypes = [vp]
         L.mla_comm_init_rank.argtypes = [ctypes.POINTER(vp), ci, vp, ci]
         L.mla_comm_destroy.argtypes = [vp]

@@ -4,6 +4,7 @@
 // backward (transposes feeding the MFMA GEMM, column sums for bias gradients), and the Adam
 // update (train.py:369 optim.Adam: betas 0.9/0.999, eps 1e-8, no weight decay, no amsgrad) over
 // one flat parameter buffer. The helpers come in f32 and bf16 (the bf16 finetune step's Linear layers).
+#include "adam_groups.h"
 #include "common.h"
 #include "mma_core.h"
 
@@ -183,6 +184,152 @@ __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__
 
 __global__ void set2_kernel(float* dst, float a, float b) { dst[0] = a; dst[1] = b; }
 
+// ---- the grouped step: torch.optim.Adam / AdamW with parameter groups over the same flat buffers, ONE launch for all groups ----
+// Which group owns a quad of four elements comes from the table of adam_groups.h (one lookup per workgroup chunk, then a walk
+// along the runs the chunk crosses); what the group asks for from its row of `groups` (mla_adam_groups_prepare). adam_update's
+// arithmetic, on values, extended by what torch's single-tensor step does around it -- with every option off the same operations
+// in the same order, so the same bits:
+//   g <- coef g (clip_grad_norm_'s factor, read from device memory; g itself is not written back)
+//   g <- g + wd p (L2) | p <- p (1 - lr wd) (decoupled) ; m, v as before ; vmax <- max(vmax, v) and sqrt(vmax) in the denominator (amsgrad)
+struct GroupRow { float step_size, inv_sqrt_bc2, b1, b2, eps, decay; int flags; };
+
+__device__ __forceinline__ GroupRow load_group(const float* __restrict__ groups, int64_t grp) {
+    typedef float f32x4_t __attribute__((ext_vector_type(4)));
+    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(groups + grp * adam_groups::kGroupFloats);
+    const f32x4_t b = *reinterpret_cast<const f32x4_t*>(groups + grp * adam_groups::kGroupFloats + 4);
+    return GroupRow{a.x, a.y, a.z, a.w, b.x, b.y, int(b.z)};
+}
+
+__device__ __forceinline__ void adam_update_ext(float& p, float g, float& m, float& v, float& vmax, const GroupRow& s, bool ams, bool clip, float coef) {
+#pragma clang fp contract(off)
+    float gi = g;
+    if (clip) gi = coef * gi;
+    if (s.flags & adam_groups::kL2) gi = gi + s.decay * p;
+    float pi = p;
+    if (s.flags & adam_groups::kDecoupled) pi = pi * s.decay;
+    const float mi = fmaf(s.b1, m, (1.f - s.b1) * gi);
+    const float vi = fmaf(s.b2, v, (1.f - s.b2) * (gi * gi));
+    m = mi;
+    v = vi;
+    float vd = vi;
+    if (ams) {
+        vd = (vi > vmax || vi != vi) ? vi : vmax;               // torch.maximum: a NaN stays
+        vmax = vd;
+    }
+    const float den = fmaf(sqrtf(vd), s.inv_sqrt_bc2, s.eps);
+    p = pi - s.step_size * mi / den;
+}
+
+__global__ __launch_bounds__(256) void adam_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, float* __restrict__ vmax, int64_t n,
+                                                           const int64_t* __restrict__ table, int64_t n_runs, int64_t n_chunks, int64_t n_pads,
+                                                           const float* __restrict__ groups, int n_groups, const float* __restrict__ coef_dev) {
+    typedef float f32x4_t __attribute__((ext_vector_type(4)));
+    const int64_t* run_end = table;
+    const int64_t* run_group = run_end + n_runs;
+    const int64_t* chunk_run = run_group + n_runs;
+    const int64_t* chunk_pad = chunk_run + n_chunks;
+    const int64_t* pad = chunk_pad + n_chunks + 1;
+    const bool clip = coef_dev != nullptr;
+    const float coef = clip ? *coef_dev : 1.f;
+    for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        // every index read from the table is clamped to its section: whatever the table holds, no access leaves the buffers
+        int64_t r0 = chunk_run[c];
+        r0 = r0 < 0 ? 0 : (r0 >= n_runs ? n_runs - 1 : r0);
+        int64_t pad0 = chunk_pad[c], pad1 = chunk_pad[c + 1];
+        pad0 = pad0 < 0 ? 0 : (pad0 > n_pads ? n_pads : pad0);
+        pad1 = pad1 < pad0 ? pad0 : (pad1 > n_pads ? n_pads : pad1);
+        // the chunk's data first (nothing in it depends on the table), then the walk along the runs: the table's dependent loads
+        // run under the data's latency instead of in front of it (at the head's 0.8 M elements that chain was a fifth of the launch)
+        constexpr int kQuads = adam_groups::kAdamChunk / 1024;
+        const int64_t q0 = c * adam_groups::kAdamChunk + int64_t(threadIdx.x) * 4;
+        f32x4_t pv[kQuads], gv[kQuads], mv[kQuads], vv[kQuads];
+        _Pragma("unroll") for (int u = 0; u < kQuads; ++u) {
+            const int64_t q = q0 + u * 1024;
+            if (q >= n) continue;                               // n is a multiple of 4
+            pv[u] = *reinterpret_cast<const f32x4_t*>(p + q);
+            gv[u] = *reinterpret_cast<const f32x4_t*>(g + q);
+            mv[u] = *reinterpret_cast<const f32x4_t*>(m + q);
+            vv[u] = *reinterpret_cast<const f32x4_t*>(v + q);
+        }
+        _Pragma("unroll") for (int u = 0; u < kQuads; ++u) {
+            const int64_t q = q0 + u * 1024;
+            if (q >= n) continue;
+            int64_t r = r0;
+            while (r + 1 < n_runs && q >= run_end[r]) ++r;
+            int64_t grp = run_group[r];
+            grp = grp < 0 ? 0 : (grp >= n_groups ? n_groups - 1 : grp);
+            const GroupRow s = load_group(groups, grp);
+            int valid = 4;                                      // a quad that ends a tensor of 4 k + 1 | 2 | 3 elements: the rest is padding
+            for (int64_t k = pad0; k < pad1; ++k)
+                if (pad[2 * k] == q) valid = int(pad[2 * k + 1]);
+            const bool ams = (s.flags & adam_groups::kAmsgrad) && vmax != nullptr;   // (the launcher's callers pair the flag with the buffer)
+            f32x4_t xv = {0.f, 0.f, 0.f, 0.f};
+            if (ams) xv = *reinterpret_cast<const f32x4_t*>(vmax + q);
+            float pe[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w}, me[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
+            float ve[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w}, xe[4] = {xv.x, xv.y, xv.z, xv.w};
+            const float ge[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w};
+            _Pragma("unroll") for (int e = 0; e < 4; ++e)
+                if (e < valid) adam_update_ext(pe[e], ge[e], me[e], ve[e], xe[e], s, ams, clip, coef);
+            *reinterpret_cast<f32x4_t*>(p + q) = f32x4_t{pe[0], pe[1], pe[2], pe[3]};
+            *reinterpret_cast<f32x4_t*>(m + q) = f32x4_t{me[0], me[1], me[2], me[3]};
+            *reinterpret_cast<f32x4_t*>(v + q) = f32x4_t{ve[0], ve[1], ve[2], ve[3]};
+            if (ams) *reinterpret_cast<f32x4_t*>(vmax + q) = f32x4_t{xe[0], xe[1], xe[2], xe[3]};
+        }
+    }
+}
+
+struct GroupTable { float v[adam_groups::kMaxGroups * adam_groups::kGroupFloats]; };
+
+__global__ __launch_bounds__(256) void set_groups_kernel(float* __restrict__ dst, GroupTable tab, int count) {
+    for (int i = threadIdx.x; i < count; i += 256) dst[i] = tab.v[i];
+}
+
+// L2 norm of the flat gradient, deterministic: block b adds the squares of its quads (b, b + grid, ...) in double, lanes
+// combine through LDS in a fixed tree; grid = adam_groups::norm_blocks(n), a function of n alone. The finishing block adds the
+// partial sums the same way and writes [norm, coef], coef = min(1, max_norm / (norm + 1e-6)) as torch's clip_grad_norm_ forms it
+// in float32 (a NaN norm gives a NaN coefficient, like torch.clamp).
+__device__ __forceinline__ double block_sum_256(double acc, double* part) {
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    return part[0];
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partial) {
+    __shared__ double part[256];
+    typedef float f32x4_t __attribute__((ext_vector_type(4)));
+    double acc = 0.0;
+    for (int64_t q = (int64_t(blockIdx.x) * 256 + threadIdx.x) * 4; q < n; q += int64_t(gridDim.x) * 1024) {
+        if (q + 4 <= n) {
+            const f32x4_t x = *reinterpret_cast<const f32x4_t*>(g + q);
+            acc += double(x.x) * double(x.x); acc += double(x.y) * double(x.y);
+            acc += double(x.z) * double(x.z); acc += double(x.w) * double(x.w);
+        } else {
+            for (int64_t i = q; i < n; ++i) acc += double(g[i]) * double(g[i]);
+        }
+    }
+    const double s = block_sum_256(acc, part);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partial, int blocks, float max_norm,
+                                                               float* __restrict__ out2) {
+    __shared__ double part[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < blocks; i += 256) acc += partial[i];
+    const double s = block_sum_256(acc, part);
+    if (threadIdx.x == 0) {
+        const float norm = float(sqrt(s));
+        const float c = max_norm / (norm + 1e-6f);
+        out2[0] = norm;
+        out2[1] = c > 1.f ? 1.f : c;
+    }
+}
+
 __global__ void counter_add_kernel(int64_t* counter, int64_t delta) { *counter += delta; }
 
 // splitmix64 finaliser; the same three lines as weights.py _mix (uint64 wrap-around arithmetic only)
@@ -330,6 +477,71 @@ extern "C" int mla_adam_step_dev(float* p, const float* g, float* m, float* v, i
     hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n, beta1, beta2,
                        eps, scal2_dev);
     MLA_LAUNCH_OK("adam (scalars on the device)");
+    return MLA_OK;
+}
+
+extern "C" int mla_adam_groups_table(const int64_t* numel, const int32_t* group, int64_t n_tensors, int n_groups, int64_t* table,
+                                     int64_t capacity, int64_t* counts5) {
+    MLA_REQUIRE(numel && group && counts5 && n_tensors >= 1, MLA_E_ARG, "bad adam_groups_table arguments");
+    adam_groups::Counts c;
+    const int bad = adam_groups::count(numel, group, n_tensors, n_groups, &c);
+    MLA_REQUIRE(bad != 3, MLA_E_SHAPE, "%d optimizer groups: the grouped Adam step takes 1 to %d", n_groups, adam_groups::kMaxGroups);
+    MLA_REQUIRE(bad == 0, MLA_E_ARG, bad == 1 ? "a tensor without elements" : "a group index outside [0, n_groups)");
+    counts5[0] = c.total; counts5[1] = c.runs; counts5[2] = c.pads; counts5[3] = c.chunks; counts5[4] = c.words;
+    if (!table) return MLA_OK;                                   // the sizes only
+    MLA_REQUIRE(capacity >= c.words, MLA_E_ARG, "adam_groups_table: %lld words of room, %lld needed", (long long)capacity, (long long)c.words);
+    adam_groups::build(numel, group, n_tensors, c, table);
+    return MLA_OK;
+}
+
+extern "C" int mla_adam_groups_prepare(float* groups_dev, const mla_adam_group_t* groups, int n_groups, int64_t step, mla_stream_t stream) {
+    MLA_REQUIRE(groups_dev && groups && step >= 1 && n_groups >= 1, MLA_E_ARG, "bad adam_groups_prepare arguments");
+    MLA_REQUIRE(n_groups <= adam_groups::kMaxGroups, MLA_E_SHAPE, "%d optimizer groups: the grouped Adam step takes 1 to %d", n_groups,
+                adam_groups::kMaxGroups);
+    MLA_REQUIRE(mla::aligned(groups_dev, 16), MLA_E_ARG, "the group rows must be 16-byte aligned");
+    GroupTable tab;
+    for (int i = 0; i < n_groups; ++i) {
+        const mla_adam_group_t& h = groups[i];
+        const adam_groups::Scalars s = adam_groups::scalars(h.lr, h.beta1, h.beta2, h.eps, h.weight_decay, h.decoupled != 0, h.amsgrad != 0, step);
+        for (int k = 0; k < adam_groups::kGroupFloats; ++k) tab.v[i * adam_groups::kGroupFloats + k] = s.v[k];
+    }
+    for (int i = n_groups * adam_groups::kGroupFloats; i < adam_groups::kMaxGroups * adam_groups::kGroupFloats; ++i) tab.v[i] = 0.f;
+    hipLaunchKernelGGL(set_groups_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), groups_dev, tab,
+                       n_groups * adam_groups::kGroupFloats);
+    MLA_LAUNCH_OK("adam_groups_prepare");
+    return MLA_OK;
+}
+
+extern "C" int mla_adam_grouped_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const int64_t* table_dev,
+                                     int64_t table_words, int64_t n_runs, int64_t n_pads, const float* groups_dev, int n_groups,
+                                     const float* coef_dev, mla_stream_t stream) {
+    MLA_REQUIRE(p && g && m && v && table_dev && groups_dev && n >= 0 && n_runs >= 1 && n_pads >= 0, MLA_E_ARG, "bad grouped adam arguments");
+    MLA_REQUIRE(n_groups >= 1 && n_groups <= adam_groups::kMaxGroups, MLA_E_SHAPE, "%d optimizer groups: the grouped Adam step takes 1 to %d",
+                n_groups, adam_groups::kMaxGroups);
+    MLA_REQUIRE(n % 4 == 0, MLA_E_SHAPE, "the flat buffers hold tensors padded to 4 floats: n = %lld is no multiple of 4", (long long)n);
+    MLA_REQUIRE(mla::aligned(p, 16) && mla::aligned(g, 16) && mla::aligned(m, 16) && mla::aligned(v, 16) && mla::aligned(vmax, 16) &&
+                mla::aligned(groups_dev, 16) && mla::aligned(table_dev, 8), MLA_E_ARG, "the flat buffers must be 16-byte aligned");
+    if (n == 0) return MLA_OK;
+    const int64_t chunks = adam_groups::chunks_of(n);
+    MLA_REQUIRE(adam_groups::words_of(n_runs, chunks, n_pads) <= table_words, MLA_E_ARG, "the table is shorter than its sections: %lld words",
+                (long long)table_words);
+    hipLaunchKernelGGL(adam_grouped_kernel, dim3(unsigned(chunks < adam_groups::kAdamMaxGrid ? chunks : adam_groups::kAdamMaxGrid)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), p, g, m, v, vmax, n, table_dev, n_runs, chunks, n_pads, groups_dev, n_groups, coef_dev);
+    MLA_LAUNCH_OK("adam (grouped)");
+    return MLA_OK;
+}
+
+extern "C" int64_t mla_grad_norm_workspace_bytes(void) { return int64_t(adam_groups::kNormMaxGrid) * int64_t(sizeof(double)); }
+
+extern "C" int mla_grad_norm(const float* g, int64_t n, float max_norm, void* workspace, float* norm_coef_dev, mla_stream_t stream) {
+    MLA_REQUIRE(g && workspace && norm_coef_dev && n >= 1, MLA_E_ARG, "bad grad_norm arguments");
+    MLA_REQUIRE(mla::aligned(g, 16) && mla::aligned(workspace, 8), MLA_E_ARG, "grad_norm: the gradient must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int blocks = int(adam_groups::norm_blocks(n));
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(unsigned(blocks)), dim3(256), 0, s, g, n, static_cast<double*>(workspace));
+    MLA_LAUNCH_OK("grad_norm partial");
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, static_cast<const double*>(workspace), blocks, max_norm, norm_coef_dev);
+    MLA_LAUNCH_OK("grad_norm finish");
     return MLA_OK;
 }
 

@@ -651,6 +651,60 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step):
                                         int(step), _lib.stream_ptr()))
 
 
+def adam_groups_table(numels, groups, n_groups):
+    """The host half of the grouped Adam step (no device): tensor sizes (flat-buffer order) and their group indices -> dict with
+    the padded `total`, the counts `runs`, `pads`, `chunks`, and `table`, the int64 CPU tensor mla_adam_grouped_step reads from
+    device memory (run_end[runs] | run_group[runs] | chunk_run[chunks] | chunk_pad[chunks + 1] | (quad, valid)[pads])."""
+    L = _lib.lib()
+    n = len(numels)
+    assert n == len(groups) and n >= 1
+    numel = (ctypes.c_int64 * n)(*[int(k) for k in numels])
+    grp = (ctypes.c_int32 * n)(*[int(k) for k in groups])
+    counts = (ctypes.c_int64 * 5)()
+    _lib.check(L.mla_adam_groups_table(numel, grp, n, int(n_groups), None, 0, counts))
+    table = torch.zeros(counts[4], dtype=torch.int64)
+    _lib.check(L.mla_adam_groups_table(numel, grp, n, int(n_groups), ctypes.c_void_p(table.data_ptr()), table.numel(), counts))
+    return {"total": counts[0], "runs": counts[1], "pads": counts[2], "chunks": counts[3], "table": table}
+
+
+def adam_groups_prepare(rows, groups, step):
+    """Write the per-group rows of step `step` (an ordinary launch, enqueued in front of the step or the graph replay).
+    rows: float32 device tensor of len(groups) * 8; groups: dicts with lr, betas, eps, weight_decay, decoupled, amsgrad."""
+    assert rows.dtype == torch.float32 and rows.is_cuda and rows.numel() >= 8 * len(groups)
+    arr = (_lib.AdamGroup * max(len(groups), 1))()
+    for a, g in zip(arr, groups):
+        a.lr, a.beta1, a.beta2, a.eps = float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+        a.weight_decay, a.decoupled, a.amsgrad = float(g["weight_decay"]), int(bool(g["decoupled"])), int(bool(g["amsgrad"]))
+    _lib.check(_lib.lib().mla_adam_groups_prepare(_p(rows), arr, len(groups), int(step), _lib.stream_ptr()))
+
+
+def adam_grouped_step(p, g, m, v, vmax, table, n_runs, n_pads, rows, n_groups, coef=None, counter=None):
+    """The Adam / AdamW step of every group in one launch (graph-capturable). table: adam_groups_table's tensor on the device;
+    rows: adam_groups_prepare's; vmax: the amsgrad buffer or None; coef: None or the 1-element device tensor the gradient is
+    scaled by (grad_norm's coefficient); counter: None or the device step counter, advanced by one."""
+    assert table.dtype == torch.int64 and table.is_cuda and rows.is_cuda and rows.numel() >= 8 * n_groups
+    assert all(t.dtype == torch.float32 and t.is_cuda and t.numel() == p.numel() for t in (p, g, m, v) + ((vmax,) if vmax is not None else ()))
+    assert coef is None or (coef.is_cuda and coef.dtype == torch.float32 and coef.numel() == 1)
+    L = _lib.lib()
+    _lib.check(_timed("adam_grouped", L.mla_adam_grouped_step, _p(p), _p(g), _p(m), _p(v), _p(vmax), p.numel(), _p(table), table.numel(),
+                      int(n_runs), int(n_pads), _p(rows), int(n_groups), _p(coef), _lib.stream_ptr()))
+    if counter is not None:
+        _lib.check(L.mla_counter_add(_p(counter), 1, _lib.stream_ptr()))
+
+
+def grad_norm(g, max_norm, out=None, workspace=None):
+    """-> float32 device pair [||g||_2, min(1, max_norm / (norm + 1e-6))]: torch.nn.utils.clip_grad_norm_'s norm and factor of a
+    flat float32 gradient; deterministic (double-precision sums in a fixed order), graph-capturable, no host sync."""
+    _chk(g, torch.float32)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=g.device)
+    if workspace is None:
+        workspace = torch.empty(_lib.lib().mla_grad_norm_workspace_bytes() // 8, dtype=torch.float64, device=g.device)
+    assert out.dtype == torch.float32 and out.numel() == 2 and workspace.numel() * workspace.element_size() >= _lib.lib().mla_grad_norm_workspace_bytes()
+    _lib.check(_timed("grad_norm", _lib.lib().mla_grad_norm, _p(g), g.numel(), float(max_norm), _p(workspace), _p(out), _lib.stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------ finetune (CNN gradients) ----
 
 def conv3x3(x, w_packed, b, cout, pool, act):

@@ -66,7 +66,7 @@ class TrainStep:
     """
 
     def __init__(self, clf, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, params=None, sync_bn=True, graph=None,
-                 trunk_data_parallel=False):
+                 optimizer=None, max_grad_norm=None, trunk_data_parallel=False):
         """``params``: the parameters the caller's optimizer holds (``optimizer.param_groups[...]["params"]``); None =
         every parameter that requires grad. Exactly the tensors in ``params`` that require grad are updated, as
         ``optimizer.step()`` does in the reference (train.py:138; torch's Adam skips parameters whose ``.grad`` is None,
@@ -75,8 +75,24 @@ class TrainStep:
         :96-97, so its "finetune" run only ever steps the MLA head) -- the updated model is the same.
         ``trunk_data_parallel``: allow ResNet trunk parameters in the update set under a process group (off: that combination is
         refused). The step then equals the single-process step on the global batch: SyncBN in the trunk's forward AND backward
-        (``ops.rn_bn_bwd_sync``), gradients summed by one flat all-reduce. The head keeps its equal-shard contract."""
+        (``ops.rn_bn_bwd_sync``), gradients summed by one flat all-reduce. The head keeps its equal-shard contract.
+        ``optimizer``: a ``torch.optim.Adam`` / ``AdamW`` whose ``param_groups`` define the update set (instead of ``params``) AND
+        how each group is stepped: ``lr``, ``betas``, ``eps``, ``weight_decay`` (L2, or decoupled for AdamW), ``amsgrad``. The
+        groups are read again at every call, so an LR scheduler or ``group["lr"] = ...`` acts on the next step, graph replays
+        included; the torch optimizer itself is never stepped. All groups are stepped by ONE launch (``ops.adam_grouped_step``).
+        ``max_grad_norm`` (needs ``optimizer``): ``clip_grad_norm_`` on the all-reduced flat gradient before the update;
+        ``grad_norm`` / ``clip_coef`` are the device values of the last step, ``grads`` keep the unclipped gradients."""
         self.clf, self.lr, self.betas, self.eps, self.t = clf, lr, betas, eps, 0
+        self.groups = None                                  # the optimizer's param_groups (the live list): the grouped step
+        if optimizer is not None:
+            if params is not None:
+                raise ValueError("give either params= or optimizer= (its param_groups are the update set), not both")
+            self.groups = self._check_optimizer(optimizer)
+        elif max_grad_norm is not None:
+            raise ValueError("max_grad_norm belongs to the grouped step: pass optimizer= (a torch.optim.Adam over the parameters will do)")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError("max_grad_norm must be positive, not %r" % (max_grad_norm,))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         # sync_bn=False: per-shard BatchNorm statistics under data parallelism (DistributedDataParallel semantics) instead of the
         # global-batch statistics that reproduce the reference's single-process step; see ops.Dist
         self.dist = ops.Dist(process_group, sync_bn=sync_bn)
@@ -87,6 +103,14 @@ class TrainStep:
         self._graph, self._eager_shape, self._dev_t = None, None, -1
         self.captures = 0                                   # graphs recorded so far (a re-capture after a disturbance counts)
         held = None if params is None else {id(p) for p in params}
+        group_of = {}
+        if self.groups is not None:
+            for gi, grp in enumerate(self.groups):
+                for q in grp["params"]:
+                    if id(q) in group_of:
+                        raise ValueError("a parameter is in two optimizer groups (%d and %d)" % (group_of[id(q)], gi))
+                    group_of[id(q)] = gi
+            held = set(group_of)
         named = [(n, p) for n, p in clf.named_parameters()
                  if p.requires_grad and ".fcf." not in n and (held is None or id(p) in held)]
         if not named:
@@ -130,6 +154,18 @@ class TrainStep:
         self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)       # completed steps: the dropout call counter of the graph-captured step
         self.adam_scal = torch.zeros(2, dtype=torch.float32, device=dev)    # Adam's step-dependent scalars, written in front of each replay
+        if self.groups is not None:
+            # the grouped step: which group owns which stretch of the flat buffers (built once, on the host), the per-group rows
+            # (rewritten in front of every step), the amsgrad maximum (only when a group asks for it), clip_grad_norm_'s pair
+            self._layout = [(p.numel(), group_of[id(p)]) for _, p in named]
+            tab = ops.adam_groups_table([k for k, _ in self._layout], [g for _, g in self._layout], len(self.groups))
+            assert tab["total"] == total
+            self._table, self._n_runs, self._n_pads = tab["table"].to(dev), tab["runs"], tab["pads"]
+            self.group_rows = torch.zeros(8 * len(self.groups), dtype=torch.float32, device=dev)
+            self.flat_vmax = torch.zeros(total, dtype=torch.float32, device=dev) if any(g["amsgrad"] for g in self._group_scalars()) else None
+            self._clip = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)           # [norm, coef] of the last step
+            self.grad_norm, self.clip_coef = self._clip[0:1], self._clip[1:2]
+            self._norm_ws = torch.zeros(1024, dtype=torch.float64, device=dev) if self.max_grad_norm is not None else None
         self.grads, self._seated, off = {}, [], 0
         spans = {}                                        # bucket id -> [first float, one past the last] of the flat buffers
         for n, p in named:
@@ -190,14 +226,80 @@ class TrainStep:
     def state_dict(self):
         """Optimizer state as plain tensors (Adam moments over the flat buffer + step count): what
         ``optimizer.state_dict()`` holds in the reference's checkpoints (train.py:249-258)."""
+        if self.groups is not None:
+            # the grouped step: per-group scalars (rows of lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad), the layout
+            # they belong to (numel and group of every tensor of the flat buffers) and, with amsgrad, the running maximum
+            sd = {"adam_m": self.flat_m.clone(), "adam_v": self.flat_v.clone(), "step": torch.tensor(self.t),
+                  "groups": torch.tensor([[g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], float(g["decoupled"]),
+                                           float(g["amsgrad"])] for g in self._group_scalars()], dtype=torch.float64),
+                  "layout": torch.tensor(self._layout, dtype=torch.int64)}
+            if self.flat_vmax is not None:
+                sd["adam_vmax"] = self.flat_vmax.clone()
+            return sd
         return {"adam_m": self.flat_m.clone(), "adam_v": self.flat_v.clone(), "step": torch.tensor(self.t),
                 "lr": torch.tensor(self.lr), "betas": torch.tensor(self.betas), "eps": torch.tensor(self.eps)}
 
     def load_state_dict(self, sd):
+        if self.groups is not None:
+            if "layout" not in sd or "groups" not in sd:
+                raise ValueError("this checkpoint was written by a step without optimizer groups; this step was built with optimizer=")
+            if sd["layout"].cpu().tolist() != [list(t) for t in self._layout] or sd["groups"].shape[0] != len(self.groups):
+                raise ValueError("this checkpoint was written for another layout of optimizer groups (other trainable tensors, or "
+                                 "tensors assigned to other groups): %d tensors in %d groups there, %d in %d here"
+                                 % (sd["layout"].shape[0], sd["groups"].shape[0], len(self._layout), len(self.groups)))
+            rows = sd["groups"].cpu().tolist()
+            if ("adam_vmax" in sd) != (self.flat_vmax is not None):
+                raise ValueError("this checkpoint %s the amsgrad maximum and this step %s it" % (
+                    ("holds", "lacks") if "adam_vmax" in sd else ("lacks", "keeps")))
+            for g, (lr, b1, b2, eps, wd, dec, ams) in zip(self.groups, rows):      # as optimizer.load_state_dict restores its groups
+                g["lr"], g["betas"], g["eps"], g["weight_decay"], g["amsgrad"] = lr, (b1, b2), eps, wd, bool(ams)
+                if "decoupled_weight_decay" in g or dec:
+                    g["decoupled_weight_decay"] = bool(dec)
+            self.flat_m.copy_(sd["adam_m"]); self.flat_v.copy_(sd["adam_v"]); self.t = int(sd["step"])
+            if self.flat_vmax is not None:
+                self.flat_vmax.copy_(sd["adam_vmax"])
+            return
+        if "layout" in sd:
+            raise ValueError("this checkpoint was written by a step with optimizer groups; this step was built without optimizer=")
         assert sd["adam_m"].numel() == self.flat_m.numel(), "checkpoint was written for a different set of trainable parameters"
         self.flat_m.copy_(sd["adam_m"]); self.flat_v.copy_(sd["adam_v"]); self.t = int(sd["step"])
         self.lr, self.eps = float(sd["lr"]), float(sd["eps"])
         self.betas = tuple(float(b) for b in sd["betas"])
+
+    @staticmethod
+    def _check_optimizer(optimizer):
+        """The live ``param_groups`` list of a torch Adam / AdamW the grouped HIP step can stand in for."""
+        if not isinstance(optimizer, torch.optim.Adam):                    # AdamW is a subclass
+            raise TypeError("the HIP step implements torch.optim.Adam and AdamW, not %s" % type(optimizer).__name__)
+        if len(optimizer.param_groups) > 64:
+            raise NotImplementedError("the grouped HIP Adam step takes up to 64 parameter groups, not %d" % len(optimizer.param_groups))
+        for g in optimizer.param_groups:
+            for key in ("maximize", "capturable", "differentiable"):
+                if g.get(key, False):
+                    raise NotImplementedError("%s=True is not implemented by the HIP Adam step" % key)
+        return optimizer.param_groups
+
+    def _group_scalars(self):
+        """What each group asks for right now, as host numbers (read at every step: schedulers write ``lr`` between steps)."""
+        out = []
+        for i, g in enumerate(self.groups):
+            if isinstance(g["lr"], torch.Tensor) or any(isinstance(b, torch.Tensor) for b in g["betas"]):
+                raise NotImplementedError("a tensor lr / betas (group %d) is not implemented by the HIP Adam step: it would cost a "
+                                          "device synchronisation per step" % i)
+            for key in ("maximize", "capturable", "differentiable"):
+                if g.get(key, False):
+                    raise NotImplementedError("%s=True is not implemented by the HIP Adam step" % key)
+            out.append({"lr": float(g["lr"]), "betas": (float(g["betas"][0]), float(g["betas"][1])), "eps": float(g["eps"]),
+                        "weight_decay": float(g.get("weight_decay", 0.0)), "decoupled": bool(g.get("decoupled_weight_decay", False)),
+                        "amsgrad": bool(g.get("amsgrad", False))})
+        return out
+
+    def _prepare_groups(self, t):
+        """Enqueue the per-group rows of step t (in front of the eager step or the graph replay)."""
+        scal = self._group_scalars()
+        if self.flat_vmax is None and any(g["amsgrad"] for g in scal):
+            raise RuntimeError("amsgrad was turned on after this TrainStep was built (it keeps no vmax buffer): build a new TrainStep")
+        ops.adam_groups_prepare(self.group_rows, scal, t)
 
     def __call__(self, inputs, labels):
         """inputs (B, T, 1, 96, 64) (or whatever ``clf.input`` reshapes), labels (B,) int64.
@@ -286,7 +388,10 @@ class TrainStep:
         else:
             g["x"].copy_(inputs, non_blocking=True)
             g["y"].copy_(labels.to(dev, non_blocking=True).long(), non_blocking=True)
-        ops.adam_prepare(self.adam_scal, self.lr, self.betas[0], self.betas[1], self.t + 1)
+        if self.groups is not None:
+            self._prepare_groups(self.t + 1)
+        else:
+            ops.adam_prepare(self.adam_scal, self.lr, self.betas[0], self.betas[1], self.t + 1)
         g["graph"].replay()
         self.t += 1
         self._dev_t = self.t
@@ -370,18 +475,35 @@ class TrainStep:
                 self.dist.all_reduce_sum(self.flat_g, "grad:flat")
             self.dist.all_reduce_sum(loss, "loss")
             self.dist.all_reduce_sum(hits, "hits")             # [running_corrects (train.py:142), #bad labels] over the global batch
-        if captured:
+        if self.groups is not None:
+            # clip_grad_norm_ on the (all-reduced: the waits above are behind us) flat gradient, then every group in one launch.
+            # One form, eager or captured: the rows and the coefficient are device memory either way.
+            coef = None
+            if self.max_grad_norm is not None:
+                ops.grad_norm(self.flat_g, self.max_grad_norm, out=self._clip, workspace=self._norm_ws)
+                coef = self.clip_coef
+            if not captured:
+                self.t += 1
+                self._prepare_groups(self.t)
+            ops.adam_grouped_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.flat_vmax, self._table, self._n_runs,
+                                  self._n_pads, self.group_rows, len(self.groups), coef, self.step_dev if captured else None)
+            if not captured:
+                self._invalidate_weight_copies()
+        elif captured:
             ops.adam_step_dev(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.betas[0], self.betas[1], self.eps, self.adam_scal, self.step_dev)
         else:
             self.t += 1
             ops.adam_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.lr, self.betas[0], self.betas[1], self.eps, self.t)
-            if self.finetune:                      # derived (repacked / bf16) weight copies are stale now
-                for m in clf.cnn.modules():
-                    if hasattr(m, "_cache"):
-                        m._cache.key = None
-            if self.rn_trunk:                      # so are the ResNet trunk's repacked weights (Adam writes behind the version counters)
-                clf.cnn._rn_cache["w"].key = None
+            self._invalidate_weight_copies()
         return loss, hits, out
+
+    def _invalidate_weight_copies(self):
+        if self.finetune:                          # derived (repacked / bf16) weight copies are stale now
+            for m in self.clf.cnn.modules():
+                if hasattr(m, "_cache"):
+                    m._cache.key = None
+        if self.rn_trunk:                          # so are the ResNet trunk's repacked weights (Adam writes behind the version counters)
+            self.clf.cnn._rn_cache["w"].key = None
 
 
 def _evaluate(clf, loader, device, collect=False):
@@ -483,7 +605,7 @@ def load_model(model_args, path):
 
 
 def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=10, save_model_path=None, resume=False,
-                finetune=False):
+                finetune=False, extended_optimizer=False, scheduler=None, max_grad_norm=None):
     """Epoch loop with the reference's signature and return value (train.py:53-179):
     (model with the best-validation weights, validation accuracy history, test_model's result).
     ``criterion`` must be nn.CrossEntropyLoss and ``optimizer`` a one-group torch.optim.Adam without weight decay /
@@ -491,21 +613,33 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
     optimizer holds (and that require grad), as ``optimizer.step()`` does; the torch optimizer object itself is not
     stepped (its ``state`` stays empty; the moments live in the checkpoint written here). Checkpoints hold tensors only
     (``_save_checkpoint``); ``resume=True`` continues from ``save_model_path`` (epoch, best accuracy, history,
-    weights and Adam moments), as train.py:80-94 does from its pickled objects."""
+    weights and Adam moments), as train.py:80-94 does from its pickled objects.
+    ``extended_optimizer=True`` lifts the one-group rule: ``optimizer`` is a torch Adam or AdamW with any parameter groups (per-group
+    lr / betas / eps / weight_decay / amsgrad), stepped by the grouped HIP step; ``scheduler`` (any torch LR scheduler over that
+    optimizer) is stepped once per epoch after validation, a ``ReduceLROnPlateau`` with the validation loss; ``max_grad_norm``
+    clips the gradient's L2 norm before each update. The last two need ``extended_optimizer=True``."""
     if not isinstance(criterion, nn.CrossEntropyLoss) or not isinstance(optimizer, torch.optim.Adam):
         raise TypeError("the HIP training step implements CrossEntropyLoss + Adam (train.py:369-372)")
-    if len(optimizer.param_groups) != 1:
-        raise NotImplementedError("the HIP Adam step takes ONE parameter group (train.py:369-370 builds one)")
-    g = optimizer.param_groups[0]
-    if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
-        raise NotImplementedError("weight_decay / amsgrad / maximize are not implemented by the HIP Adam step (train.py:369 uses none)")
+    if not extended_optimizer:
+        if scheduler is not None or max_grad_norm is not None:
+            raise ValueError("scheduler= and max_grad_norm= belong to the grouped HIP step: pass extended_optimizer=True")
+        if len(optimizer.param_groups) != 1:
+            raise NotImplementedError("the HIP Adam step takes ONE parameter group (train.py:369-370 builds one); "
+                                      "extended_optimizer=True steps several")
+        g = optimizer.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+            raise NotImplementedError("weight_decay / amsgrad / maximize are not implemented by the HIP Adam step (train.py:369 uses "
+                                      "none); extended_optimizer=True implements weight_decay and amsgrad")
     if finetune:
         from .model import set_requires_grad
         set_requires_grad(clf, True)                       # train.py:96-97 (AFTER the caller built the optimizer)
     import copy
     device = torch.device("cuda", torch.cuda.current_device())
     clf.to(device)                                         # train.py:101
-    step = TrainStep(clf, lr=g["lr"], betas=g["betas"], eps=g["eps"], params=g["params"])     # steps what the optimizer holds
+    if extended_optimizer:
+        step = TrainStep(clf, optimizer=optimizer, max_grad_norm=max_grad_norm)               # reads the groups at every step
+    else:
+        step = TrainStep(clf, lr=g["lr"], betas=g["betas"], eps=g["eps"], params=g["params"])     # steps what the optimizer holds
     since, val_acc_history, best_acc, best_epoch, first_epoch = time.time(), [], 0.0, 0, 0
     if resume:
         assert save_model_path is not None
@@ -532,6 +666,14 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
             if save_model_path:
                 _save_checkpoint(clf, step, epoch, v_loss, best_acc, val_acc_history, save_model_path)
                 print("Model checkpoint saved successfully in the given path!")
+        if scheduler is not None:                          # after the checkpoint: a resumed run steps the scheduler at the same point
+            import warnings
+            with warnings.catch_warnings():                # torch warns that optimizer.step() was never called: the HIP step stands in for it
+                warnings.filterwarnings("ignore", message=r"Detected call of `lr_scheduler\.step\(\)` before")
+                if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
+                    scheduler.step(v_loss)
+                else:
+                    scheduler.step()
         if patience is not None and epoch - best_epoch >= patience:
             break
     print("Training complete in {:.0f}s; best val Acc: {:4f}".format(time.time() - since, best_acc))

@@ -598,6 +598,42 @@ int mla_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
 int mla_adam_prepare(float* scal2_dev, float lr, float beta1, float beta2, int64_t step, mla_stream_t stream);
 int mla_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
                       const float* scal2_dev, mla_stream_t stream);
+
+/* torch.optim.Adam / AdamW WITH parameter groups over the same flat buffers (the reference builds `optimizer` at 1e-3 and
+ * `optimizer_ft` at 1e-4, train.py:369-371, and stops there; the finetuning recipe needs a learning rate per group, weight decay
+ * on weights only, amsgrad, gradient clipping). One launch for all groups.
+ *
+ * The flat buffers hold the tensors in named_parameters() order, each padded to a multiple of 4 floats. mla_adam_groups_table
+ * (host only, no device) turns the tensors' sizes and group indices into the int64 table the kernel reads: maximal runs of
+ * adjacent tensors of one group, the run each chunk of the buffer starts in, and the padding quads. Call it with table = NULL
+ * for the sizes: counts5 = [padded total, runs, padding entries, chunks, table words]; then with room for the words, and copy
+ * them to the device once. More than 64 groups (or none): MLA_E_SHAPE. */
+typedef struct {
+    float lr, beta1, beta2, eps, weight_decay;
+    int decoupled;                      /* AdamW: p <- p (1 - lr wd) before the update; 0: L2, g <- g + wd p */
+    int amsgrad;                        /* denominator from the running maximum of v (needs the vmax buffer)  */
+} mla_adam_group_t;
+int mla_adam_groups_table(const int64_t* numel, const int32_t* group, int64_t n_tensors, int n_groups, int64_t* table,
+                          int64_t capacity, int64_t* counts5);
+/* Writes the n_groups x 8 float rows the grouped step reads (lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), beta1, beta2, eps, the
+ * decay coefficient, flags) for step t. `groups` is HOST memory, read during the call; the values are computed on the host in
+ * double, exactly as mla_adam_prepare computes its pair, and travel as a kernel argument: an ordinary launch, no copy, no
+ * synchronisation -- enqueue it in front of every step or graph replay, so a changed lr takes effect without a re-capture.
+ * groups_dev: 16-byte aligned. More than 64 groups: MLA_E_SHAPE. */
+int mla_adam_groups_prepare(float* groups_dev, const mla_adam_group_t* groups, int n_groups, int64_t step, mla_stream_t stream);
+/* The step (train.py:138 with torch's options). n = padded total, a multiple of 4; all buffers 16-byte aligned. vmax: the amsgrad
+ * maximum, touched by amsgrad groups only (NULL when no group asks for it). coef_dev: NULL, or mla_grad_norm's coefficient: the
+ * update then uses coef * g; g itself is only read. Padding elements are never written. With one group, no decay, no amsgrad and
+ * coef_dev = NULL the result equals mla_adam_step bit for bit. Graph-capturable: everything step-dependent is device memory. */
+int mla_adam_grouped_step(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, const int64_t* table_dev,
+                          int64_t table_words, int64_t n_runs, int64_t n_pads, const float* groups_dev, int n_groups,
+                          const float* coef_dev, mla_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_'s two numbers for the flat gradient: norm_coef_dev[0] = ||g||_2, [1] = min(1, max_norm /
+ * (norm + 1e-6)) (NaN for a NaN norm, as torch.clamp gives). Deterministic: sums of squares in double, per block and then over
+ * the blocks, in an order that depends on n only; no float atomics. g: 16-byte aligned, read once. workspace:
+ * mla_grad_norm_workspace_bytes() bytes. Graph-capturable. */
+int64_t mla_grad_norm_workspace_bytes(void);
+int mla_grad_norm(const float* g, int64_t n, float max_norm, void* workspace, float* norm_coef_dev, mla_stream_t stream);
 /* *counter_dev += delta: the call counter mla_dropout_mask_dev reads, advanced once per step from inside the graph */
 int mla_counter_add(int64_t* counter_dev, int64_t delta, mla_stream_t stream);
 
