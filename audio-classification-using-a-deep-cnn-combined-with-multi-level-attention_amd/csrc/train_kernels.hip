@@ -5,6 +5,7 @@
 // update (train.py:369 optim.Adam: betas 0.9/0.999, eps 1e-8, no weight decay, no amsgrad) over
 // one flat parameter buffer. The helpers come in f32 and bf16 (the bf16 finetune step's Linear layers).
 #include "adam_groups.h"
+#include "ce_core.h"
 #include "common.h"
 #include "mma_core.h"
 
@@ -93,6 +94,102 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
     if (threadIdx.x == 0) {
         *loss = bads[0] ? __builtin_nanf("") : float(part[0] * inv_total);
         if (n_correct) { n_correct[0] = hits[0]; n_correct[1] = bads[0]; }
+    }
+}
+
+// ---- nn.CrossEntropyLoss with class weights, label smoothing and ignore_index (formulas and lane layout: ce_core.h) ----
+// Three launches, no floating-point atomics and none on integers either: the denominator of the mean (labels and weights only, so
+// a data-parallel step can all-reduce it in front of the loss), one wavefront per row, and one workgroup that adds the row terms
+// and the row flags in a fixed order. The scale 1 / den is read from device memory: the sequence replays in a HIP graph.
+template <typename T>
+__device__ __forceinline__ T block_tree_256(T v, T* part) {
+    part[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    const T r = part[0];
+    __syncthreads();                                        // part is used again
+    return r;
+}
+
+__global__ __launch_bounds__(ce::kThreads) void cross_entropy_den_kernel(const int64_t* __restrict__ labels, int64_t rows, int K,
+                                                                         const float* __restrict__ w, int64_t ignore_index,
+                                                                         float* __restrict__ den) {
+    __shared__ double part[ce::kThreads];
+    const double s = block_tree_256(ce::den_thread(labels, rows, K, w, ignore_index, threadIdx.x), part);
+    if (threadIdx.x == 0) den[0] = float(s);
+}
+
+__device__ __forceinline__ ce::MaxAt wave_max_at(ce::MaxAt v) {
+    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) v = ce::max_combine(v, ce::MaxAt{__shfl_xor(v.m, o), __shfl_xor(v.i, o)});
+    return v;
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v) {
+    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void cross_entropy_opts_kernel(const float* __restrict__ x, int64_t ldx, const int64_t* __restrict__ labels,
+                                                                 int64_t rows, int K, const float* __restrict__ w, int64_t ignore_index,
+                                                                 float smoothing, const float* __restrict__ den, float* __restrict__ dx,
+                                                                 int64_t ld_dx, double* __restrict__ term, int32_t* __restrict__ flags) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = int64_t(blockIdx.x) * ce::kRowsPerWg + (threadIdx.x >> 6);
+    if (b >= rows) return;                                  // the whole wave; no barrier below
+    const int64_t y64 = labels[b];
+    const int cls = ce::classify(y64, K, ignore_index);
+    if (cls != ce::kCounted) {                              // ignored, or a label that must not be used as an index: zeros, no loss
+        if (dx)
+            for (int k = lane; k < K; k += ce::kLanes) dx[b * ld_dx + k] = 0.f;
+        if (lane == 0) { term[b] = 0.0; flags[b] = cls; }
+        return;
+    }
+    const float* row = x + b * ldx;
+    float xv[ce::kPerLane];
+    _Pragma("unroll") for (int j = 0; j < ce::kPerLane; ++j) {
+        const int k = lane + ce::kLanes * j;
+        xv[j] = k < K ? row[k] : 0.f;
+    }
+    const ce::MaxAt top = wave_max_at(ce::lane_max(xv, K, lane));
+    ce::Row r;
+    r.y = int(y64);
+    r.lse = top.m + ce::fast_log(wave_sum_f32(ce::lane_sum_exp(xv, K, lane, top.m)));
+    r.c = (1.f - smoothing) * (w ? w[r.y] : 1.f);
+    r.ek = smoothing / float(K);
+    r.wsum = 0.f;
+    r.s = den ? 1.f / den[0] : 1.f;
+    float t = 0.f;
+    if (r.ek > 0.f) {
+        ce::lane_smooth(xv, w, K, lane, r.lse, &t, &r.wsum);
+        t = wave_sum_f32(t);
+        r.wsum = wave_sum_f32(r.wsum);
+    }
+    if (dx) {
+        _Pragma("unroll") for (int j = 0; j < ce::kPerLane; ++j) {
+            const int k = lane + ce::kLanes * j;
+            if (k < K) dx[b * ld_dx + k] = ce::dx_elem(r, xv[j], k, (w && r.ek > 0.f) ? w[k] : 1.f);
+        }
+    }
+    if (lane == 0) {
+        term[b] = ce::row_loss(r, row[r.y], t);
+        flags[b] = ce::kCounted | (top.i == r.y ? ce::kHit : 0);
+    }
+}
+
+__global__ __launch_bounds__(ce::kThreads) void cross_entropy_finish_kernel(const double* __restrict__ term, const int32_t* __restrict__ flags,
+                                                                            int64_t rows, int reduction, const float* __restrict__ den,
+                                                                            float* __restrict__ loss, int* __restrict__ counts) {
+    __shared__ double part[ce::kThreads];
+    __shared__ int ipart[ce::kThreads];
+    int n3[3];
+    const double s = block_tree_256(ce::finish_thread(term, flags, rows, threadIdx.x, n3), part);
+    _Pragma("unroll") for (int i = 0; i < 3; ++i) n3[i] = block_tree_256(n3[i], ipart);
+    if (threadIdx.x == 0) {
+        *loss = ce::finish_loss(s, n3[1], reduction, den);
+        counts[0] = n3[0]; counts[1] = n3[1]; counts[2] = n3[2];
     }
 }
 
@@ -404,6 +501,44 @@ extern "C" int mla_cross_entropy(const float* x, int64_t ldx, const int64_t* lab
     hipLaunchKernelGGL(cross_entropy_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), x, ldx, labels, rows, K,
                        inv_total, loss, dx, ld_dx, n_correct);
     MLA_LAUNCH_OK("cross_entropy");
+    return MLA_OK;
+}
+
+extern "C" int mla_cross_entropy_den(const int64_t* labels, int64_t rows, int K, const float* weight, int64_t ignore_index, float* den,
+                                     mla_stream_t stream) {
+    MLA_REQUIRE(labels && den, MLA_E_ARG, "cross_entropy_den: null labels or den");
+    MLA_REQUIRE(rows > 0, MLA_E_ARG, "cross_entropy_den: rows = %lld", (long long)rows);
+    MLA_REQUIRE(K >= 1 && K <= ce::kMaxK, MLA_E_SHAPE, "cross_entropy_den: K = %d, built for 1 to %d classes", K, ce::kMaxK);
+    hipLaunchKernelGGL(cross_entropy_den_kernel, dim3(1), dim3(ce::kThreads), 0, static_cast<hipStream_t>(stream), labels, rows, K, weight,
+                       ignore_index, den);
+    MLA_LAUNCH_OK("cross_entropy_den");
+    return MLA_OK;
+}
+
+extern "C" int64_t mla_cross_entropy_opts_workspace_bytes(int64_t rows) { return ce::workspace_bytes(rows); }
+
+extern "C" int mla_cross_entropy_opts(const float* x, int64_t ldx, const int64_t* labels, int64_t rows, int K, const float* weight,
+                                      int64_t ignore_index, float label_smoothing, int reduction, const float* den, float* loss, float* dx,
+                                      int64_t ld_dx, int* counts, void* workspace, mla_stream_t stream) {
+    MLA_REQUIRE(x && labels && loss && counts && workspace, MLA_E_ARG, "cross_entropy_opts: null x, labels, loss, counts or workspace");
+    MLA_REQUIRE(rows > 0, MLA_E_ARG, "cross_entropy_opts: rows = %lld", (long long)rows);
+    MLA_REQUIRE(K >= 1 && K <= ce::kMaxK, MLA_E_SHAPE, "cross_entropy_opts: K = %d, built for 1 to %d classes (16 per lane of a wavefront)", K,
+                ce::kMaxK);
+    MLA_REQUIRE(ldx >= K && (!dx || ld_dx >= K), MLA_E_ARG, "cross_entropy_opts: a row pitch below K = %d", K);
+    MLA_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, MLA_E_ARG, "cross_entropy_opts: label_smoothing %g outside [0, 1]",
+                double(label_smoothing));
+    MLA_REQUIRE(reduction == ce::kMean || reduction == ce::kSum, MLA_E_ARG, "cross_entropy_opts: reduction code %d (0 = mean, 1 = sum)", reduction);
+    MLA_REQUIRE(reduction != ce::kMean || den, MLA_E_ARG, "cross_entropy_opts: the mean needs den (mla_cross_entropy_den)");
+    MLA_REQUIRE(mla::aligned(workspace, 8), MLA_E_ARG, "cross_entropy_opts: the workspace must be 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* term = static_cast<double*>(workspace);
+    int32_t* flags = reinterpret_cast<int32_t*>(term + rows);
+    const float* scale = reduction == ce::kMean ? den : nullptr;
+    hipLaunchKernelGGL(cross_entropy_opts_kernel, dim3(unsigned((rows + ce::kRowsPerWg - 1) / ce::kRowsPerWg)), dim3(256), 0, s, x, ldx, labels,
+                       rows, K, weight, ignore_index, label_smoothing, scale, dx, ld_dx, term, flags);
+    MLA_LAUNCH_OK("cross_entropy_opts");
+    hipLaunchKernelGGL(cross_entropy_finish_kernel, dim3(1), dim3(ce::kThreads), 0, s, term, flags, rows, reduction, scale, loss, counts);
+    MLA_LAUNCH_OK("cross_entropy_opts finish");
     return MLA_OK;
 }
 

@@ -622,6 +622,53 @@ def cross_entropy(scores, labels, inv_total, want_grad=True):
     return loss, d, hits
 
 
+def check_labels_ignoring(labels, K, ignore_index):
+    """check_labels for a criterion that honours ``ignore_index``: host labels equal to it pass (also when it is a class index),
+    every other label outside [0, K) raises before the upload. Device labels are left to the kernel's counter, as there."""
+    if not labels.is_cuda and labels.numel():
+        kept = labels[labels != ignore_index]
+        if kept.numel():
+            lo, hi = int(kept.min()), int(kept.max())
+            if lo < 0 or hi >= K:
+                raise IndexError("Target %d is out of bounds." % (lo if lo < 0 else hi))
+
+
+REDUCTIONS = {"mean": 0, "sum": 1}
+
+
+def cross_entropy_opts(scores, labels, weight=None, ignore_index=-100, label_smoothing=0.0, reduction="mean", dist=None, want_grad=True):
+    """nn.CrossEntropyLoss(weight, ignore_index=, label_smoothing=, reduction="mean" | "sum") on (B, K <= 1024) scores:
+    (loss, dscores, hits, counted). hits = int32 [n_correct, n_bad] as cross_entropy's (raise_on_bad_labels reads it), counted =
+    int32 [rows whose label is not ignore_index]; both are views of one 3-element tensor. Ignored rows add no loss, get exact zeros
+    in dscores and are neither hits nor bad labels. The mean divides by the sum of weight[y] over the counted rows of the GLOBAL
+    batch: with an active `dist` the denominator is all-reduced (on the current stream) in front of the main launch, so each
+    rank's loss is its share of the global mean (sum the losses) and dscores is scaled for a summed gradient. With no counted
+    row the mean is NaN, as torch's, and dscores all zero. Three launches (two for "sum"), graph-capturable, bit-reproducible."""
+    _chk_rows(scores, torch.float32); _chk(labels, torch.int64)
+    if reduction not in REDUCTIONS:
+        raise ValueError("reduction must be 'mean' or 'sum' (the HIP loss returns a scalar), not %r" % (reduction,))
+    B, K = scores.shape
+    dev = scores.device
+    if weight is not None:
+        _chk(weight, torch.float32)
+        assert weight.numel() == K, "weight holds %d elements for %d classes" % (weight.numel(), K)
+    L = _lib.lib()
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    d = torch.empty((B, K), dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty(int(L.mla_cross_entropy_opts_workspace_bytes(B)) // 8, dtype=torch.float64, device=dev)
+    den = None
+    if reduction == "mean":
+        den = torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.check(L.mla_cross_entropy_den(_p(labels), B, K, _p(weight), int(ignore_index), _p(den), _lib.stream_ptr()))
+        if dist is not None:
+            dist.all_reduce_sum(den, "loss:den")
+    _lib.check(_timed("cross_entropy_opts", L.mla_cross_entropy_opts, _p(scores), scores.stride(0), _p(labels), B, K, _p(weight),
+                      int(ignore_index), float(label_smoothing), REDUCTIONS[reduction], _p(den), _p(loss), _p(d), K, _p(counts), _p(ws),
+                      _lib.stream_ptr()))
+    return loss, d, counts[0:2], counts[2:3]
+
+
 def dropout_mask_dev(n, seed, stream_base, counter, offset, p_drop, device, out=None):
     """dropout_mask with stream_id = stream_base + counter[0] + 1 read on the device (graph-captured training step)."""
     assert counter.dtype == torch.int64 and counter.is_cuda

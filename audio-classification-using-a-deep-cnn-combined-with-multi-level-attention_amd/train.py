@@ -54,6 +54,35 @@ def trainable_params(model, feature_extract):
     return params_to_update
 
 
+def parse_criterion(criterion, classes):
+    """What the HIP loss with options (``ops.cross_entropy_opts``) needs of an ``nn.CrossEntropyLoss``, checked on the host without a
+    device: {"weight": float32 CPU tensor of ``classes`` elements or None, "ignore_index", "label_smoothing", "reduction"}.
+    Refused: another loss (TypeError); ``reduction="none"`` (the step returns a scalar), ``label_smoothing`` outside [0, 1], a
+    weight that is not a finite, non-negative float tensor of ``classes`` elements with a positive entry (ValueError); more than
+    1024 classes (NotImplementedError)."""
+    if not isinstance(criterion, nn.CrossEntropyLoss):
+        raise TypeError("the HIP training step implements nn.CrossEntropyLoss, not %s" % type(criterion).__name__)
+    if criterion.reduction not in ("mean", "sum"):
+        raise ValueError("reduction=%r: the HIP step returns a scalar loss, 'mean' or 'sum'" % (criterion.reduction,))
+    eps = float(criterion.label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError("label_smoothing must lie in [0, 1], not %r" % (criterion.label_smoothing,))
+    if classes > 1024:
+        raise NotImplementedError("the HIP loss with options is built for up to 1024 classes, not %d" % classes)
+    weight = criterion.weight
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or not weight.is_floating_point():
+            raise ValueError("the class weights must be a float tensor")
+        if weight.dim() != 1 or weight.numel() != classes:
+            raise ValueError("the class weights have shape %s; the head has %d classes" % (tuple(weight.shape), classes))
+        weight = weight.detach().to("cpu", torch.float32).contiguous()
+        if not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+            raise ValueError("the class weights must be finite and non-negative")
+        if not bool((weight > 0).any()):
+            raise ValueError("the class weights are all zero")
+    return {"weight": weight, "ignore_index": int(criterion.ignore_index), "label_smoothing": eps, "reduction": criterion.reduction}
+
+
 class TrainStep:
     """One fused training step of an ``Ensemble``: frozen CNN (the reference default
     ``cnn_trainable=False``; model.py:159-160) or finetune (every parameter trainable, train.py:96-97;
@@ -66,7 +95,7 @@ class TrainStep:
     """
 
     def __init__(self, clf, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, params=None, sync_bn=True, graph=None,
-                 optimizer=None, max_grad_norm=None, trunk_data_parallel=False):
+                 optimizer=None, max_grad_norm=None, criterion=None, trunk_data_parallel=False):
         """``params``: the parameters the caller's optimizer holds (``optimizer.param_groups[...]["params"]``); None =
         every parameter that requires grad. Exactly the tensors in ``params`` that require grad are updated, as
         ``optimizer.step()`` does in the reference (train.py:138; torch's Adam skips parameters whose ``.grad`` is None,
@@ -81,8 +110,16 @@ class TrainStep:
         groups are read again at every call, so an LR scheduler or ``group["lr"] = ...`` acts on the next step, graph replays
         included; the torch optimizer itself is never stepped. All groups are stepped by ONE launch (``ops.adam_grouped_step``).
         ``max_grad_norm`` (needs ``optimizer``): ``clip_grad_norm_`` on the all-reduced flat gradient before the update;
-        ``grad_norm`` / ``clip_coef`` are the device values of the last step, ``grads`` keep the unclipped gradients."""
+        ``grad_norm`` / ``clip_coef`` are the device values of the last step, ``grads`` keep the unclipped gradients.
+        ``criterion``: None = the plain mean cross-entropy (``ops.cross_entropy``), or an ``nn.CrossEntropyLoss`` whose ``weight``,
+        ``ignore_index``, ``label_smoothing`` and ``reduction`` ("mean" | "sum") the step honours (``ops.cross_entropy_opts``). The
+        weight is copied to the device once, here; the other three are read here and must not change afterwards. Under a process
+        group the mean's denominator is the global batch's; ``last_counted`` holds the (global) number of rows whose label is not
+        ``ignore_index``, a 1-element device tensor, after each step."""
         self.clf, self.lr, self.betas, self.eps, self.t = clf, lr, betas, eps, 0
+        self.criterion = criterion
+        self._crit = None if criterion is None else parse_criterion(criterion, clf.mla.classes)
+        self._crit_weight, self._counted, self.last_counted = None, None, None
         self.groups = None                                  # the optimizer's param_groups (the live list): the grouped step
         if optimizer is not None:
             if params is not None:
@@ -145,6 +182,8 @@ class TrainStep:
                                       "master weights), not %r" % clf.cnn.precision)
         dev = named[0][1].device
         assert dev.type == "cuda", "TrainStep needs the model on the GPU (train_model moves it there, train.py:101)"
+        if self._crit is not None and self._crit["weight"] is not None:
+            self._crit_weight = self._crit["weight"].to(dev)
         pad4 = lambda k: (k + 3) // 4 * 4                 # every tensor starts 16-byte aligned (GEMM operand rule)
         total = sum(pad4(p.numel()) for _, p in named)
         self.n_params = sum(p.numel() for _, p in named)
@@ -301,6 +340,14 @@ class TrainStep:
             raise RuntimeError("amsgrad was turned on after this TrainStep was built (it keeps no vmax buffer): build a new TrainStep")
         ops.adam_groups_prepare(self.group_rows, scal, t)
 
+    def _check_criterion(self):
+        """The criterion's scalars as they were when the step was built (a graph holds them as launch arguments)."""
+        c, live = self._crit, self.criterion
+        now = (float(live.label_smoothing), int(live.ignore_index), live.reduction)
+        if now != (c["label_smoothing"], c["ignore_index"], c["reduction"]):
+            raise RuntimeError("the criterion changed after this TrainStep was built (label_smoothing, ignore_index, reduction: %r, was "
+                               "%r): build a new TrainStep" % (now, (c["label_smoothing"], c["ignore_index"], c["reduction"])))
+
     def __call__(self, inputs, labels):
         """inputs (B, T, 1, 96, 64) (or whatever ``clf.input`` reshapes), labels (B,) int64.
         Returns (loss, hits) as device tensors (no host sync; train.py:141-142 syncs via .item()): hits = int32
@@ -313,13 +360,18 @@ class TrainStep:
                 raise RuntimeError("parameter %s no longer lives in the flat buffer of this TrainStep (the model was moved or "
                                    "cast after the step was built): build a new TrainStep" % n)
         clf.train()
-        ops.check_labels(labels, clf.mla.classes)
+        if self._crit is None:
+            ops.check_labels(labels, clf.mla.classes)
+        else:
+            self._check_criterion()
+            ops.check_labels_ignoring(labels, clf.mla.classes, self._crit["ignore_index"])
         if self._graph_usable(inputs) and not self._graph_disturbed():
             return self._graphed(inputs, labels)
         with torch.no_grad():
             loss, hits, out = self._body(inputs, labels.to(inputs.device).long().contiguous(), captured=False)
         self._eager_shape = tuple(inputs.shape)
         self.last_out = out
+        self.last_counted = self._counted
         return loss, hits
 
     # ---- the step as ONE HIP graph (no data-parallel group): ~130 small launches of the head's forward / backward / Adam and the
@@ -378,11 +430,14 @@ class TrainStep:
             g["graph"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g["graph"], capture_error_mode="relaxed"), torch.no_grad():
                 g["loss"], g["hits"], g["out"] = self._body(g["x"], g["y"], captured=True, bases=g["bases"])
+            g["counted"] = self._counted
             # what the recorded kernels address without having allocated it during the capture: compared before every replay
             # (_graph_disturbed) and kept alive for as long as this graph is
             scratch = ops.scratch(dev)
             g["stamp"], g["scratch"] = self._stamp(), {k: t.data_ptr() for k, t in scratch.items()}
             g["held"] = [t for c in weight_caches(self.clf.cnn) for t in c.tensors()] + list(scratch.values())
+            if self._crit_weight is not None:
+                g["held"].append(self._crit_weight)
             self._graph = g
             self.captures += 1
         else:
@@ -407,6 +462,7 @@ class TrainStep:
                 if hasattr(m, "_cache"):
                     m._cache.key = None
         self.last_out = g["out"]
+        self.last_counted = g["counted"]
         return g["loss"], g["hits"]
 
     def _body(self, inputs, labels, captured, bases=None):
@@ -431,7 +487,13 @@ class TrainStep:
             feats = clf.cnn(x)
         ctx = mla_train.Ctx(tape=True, dist=self.dist, counter=self.step_dev if captured else None, bases=bases)
         out = mla_train.mla_forward(clf.mla, feats.reshape(-1, clf.mla.slots, clf.emb_input_size), ctx)
-        loss, dout, hits = ops.cross_entropy(out, labels, 1.0 / B_global)
+        if self._crit is None:
+            loss, dout, hits = ops.cross_entropy(out, labels, 1.0 / B_global)
+        else:
+            # the mean's denominator is all-reduced inside, on this (the compute) stream like the SyncBN sums, in front of the loss
+            c = self._crit
+            loss, dout, hits, self._counted = ops.cross_entropy_opts(out, labels, self._crit_weight, c["ignore_index"], c["label_smoothing"],
+                                                                     c["reduction"], dist=self.dist)
         d_feats = mla_train.mla_backward(clf.mla, ctx, dout, self.mla_grads,
                                          need_input_grad=self.finetune or self.rn_fc or bool(self.rn_trunk))
         if self.rn_fc:
@@ -475,6 +537,8 @@ class TrainStep:
                 self.dist.all_reduce_sum(self.flat_g, "grad:flat")
             self.dist.all_reduce_sum(loss, "loss")
             self.dist.all_reduce_sum(hits, "hits")             # [running_corrects (train.py:142), #bad labels] over the global batch
+            if self._crit is not None:
+                self.dist.all_reduce_sum(self._counted, "counted")
         if self.groups is not None:
             # clip_grad_norm_ on the (all-reduced: the waits above are behind us) flat gradient, then every group in one launch.
             # One form, eager or captured: the rows and the coefficient are device memory either way.
@@ -506,16 +570,27 @@ class TrainStep:
             self.clf.cnn._rn_cache["w"].key = None
 
 
-def _evaluate(clf, loader, device, collect=False):
+def _evaluate(clf, loader, device, collect=False, criterion=None):
+    """criterion: None = the plain mean cross-entropy, or the nn.CrossEntropyLoss to evaluate with (ops.cross_entropy_opts), as the
+    reference calls ``criterion(outputs, labels)`` in every phase; the accuracy divides by all rows seen (train.py:145) either way."""
     clf.eval()
     tot_loss, tot_hits, n, preds, trues = 0.0, 0, 0, [], []
+    crit, crit_weight = None, None
     with torch.no_grad():
         for inputs, labels in loader:
             host_labels = labels
             inputs, labels = inputs.to(device).float(), labels.to(device).long()
             out = clf(inputs)
-            ops.check_labels(host_labels, out.shape[1])
-            loss, _, hits = ops.cross_entropy(out, labels.contiguous(), 1.0 / inputs.shape[0], want_grad=False)
+            if criterion is None:
+                ops.check_labels(host_labels, out.shape[1])
+                loss, _, hits = ops.cross_entropy(out, labels.contiguous(), 1.0 / inputs.shape[0], want_grad=False)
+            else:
+                if crit is None:
+                    crit = parse_criterion(criterion, out.shape[1])
+                    crit_weight = None if crit["weight"] is None else crit["weight"].to(device)
+                ops.check_labels_ignoring(host_labels, out.shape[1], crit["ignore_index"])
+                loss, _, hits, _ = ops.cross_entropy_opts(out, labels.contiguous(), crit_weight, crit["ignore_index"], crit["label_smoothing"],
+                                                          crit["reduction"], want_grad=False)
             tot_loss += float(loss) * inputs.shape[0]
             tot_hits += ops.raise_on_bad_labels(hits)
             n += inputs.shape[0]
@@ -559,13 +634,23 @@ def default_target_names(classes):
 def test_model(model, dataloader, criterion=None, optimizer=None, target_names=None):
     """train.py:182-247: final test pass -> (test accuracy, classification summary dict). The confusion-matrix
     plot of the reference is not reproduced; the matrix itself is returned under ``results["confusion_matrix_pct"]``.
-    target_names: one name per class of the head; None = TARGET_NAMES for a 10-class head, else class_0, class_1, ..."""
+    target_names: one name per class of the head; None = TARGET_NAMES for a 10-class head, else class_0, class_1, ...
+    ``criterion`` is not read here: the test loss is the plain mean (``train_model(extended_criterion=True)`` tests with its criterion)."""
+    return _test_model(model, dataloader, target_names, None)
+
+
+def _test_model(model, dataloader, target_names, criterion):
+    """test_model's body. criterion: None = the plain mean, or the nn.CrossEntropyLoss the test loss is taken with; rows whose label it
+    ignores stay in the accuracy's denominator and are left out of the classification summary."""
     if dataloader is None:
         return None
     device = next(model.parameters()).device
     since = time.time()
     print("Testing"); print("-" * 10)
-    loss, acc, preds, trues = _evaluate(model, dataloader, device, collect=True)
+    loss, acc, preds, trues = _evaluate(model, dataloader, device, collect=True, criterion=criterion)
+    if criterion is not None:
+        keep = trues != int(criterion.ignore_index)
+        preds, trues = preds[keep], trues[keep]
     print("{} Loss: {:.4f}, Acc: {:.4f}".format("test", loss, acc))
     print("Testing complete in {:.0f}s".format(time.time() - since))
     if target_names is None:
@@ -605,7 +690,7 @@ def load_model(model_args, path):
 
 
 def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=10, save_model_path=None, resume=False,
-                finetune=False, extended_optimizer=False, scheduler=None, max_grad_norm=None):
+                finetune=False, extended_optimizer=False, scheduler=None, max_grad_norm=None, extended_criterion=False):
     """Epoch loop with the reference's signature and return value (train.py:53-179):
     (model with the best-validation weights, validation accuracy history, test_model's result).
     ``criterion`` must be nn.CrossEntropyLoss and ``optimizer`` a one-group torch.optim.Adam without weight decay /
@@ -617,7 +702,10 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
     ``extended_optimizer=True`` lifts the one-group rule: ``optimizer`` is a torch Adam or AdamW with any parameter groups (per-group
     lr / betas / eps / weight_decay / amsgrad), stepped by the grouped HIP step; ``scheduler`` (any torch LR scheduler over that
     optimizer) is stepped once per epoch after validation, a ``ReduceLROnPlateau`` with the validation loss; ``max_grad_norm``
-    clips the gradient's L2 norm before each update. The last two need ``extended_optimizer=True``."""
+    clips the gradient's L2 norm before each update. The last two need ``extended_optimizer=True``.
+    ``extended_criterion=True``: ``criterion``'s ``weight``, ``ignore_index``, ``label_smoothing`` and ``reduction`` ("mean" | "sum") are
+    honoured by the step (``TrainStep(criterion=)``) and by the validation and test loss; off, the criterion is the plain mean and
+    a label of -100 is refused like any other label outside the classes."""
     if not isinstance(criterion, nn.CrossEntropyLoss) or not isinstance(optimizer, torch.optim.Adam):
         raise TypeError("the HIP training step implements CrossEntropyLoss + Adam (train.py:369-372)")
     if not extended_optimizer:
@@ -636,10 +724,11 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
     import copy
     device = torch.device("cuda", torch.cuda.current_device())
     clf.to(device)                                         # train.py:101
+    crit = criterion if extended_criterion else None
     if extended_optimizer:
-        step = TrainStep(clf, optimizer=optimizer, max_grad_norm=max_grad_norm)               # reads the groups at every step
+        step = TrainStep(clf, optimizer=optimizer, max_grad_norm=max_grad_norm, criterion=crit)   # reads the groups at every step
     else:
-        step = TrainStep(clf, lr=g["lr"], betas=g["betas"], eps=g["eps"], params=g["params"])     # steps what the optimizer holds
+        step = TrainStep(clf, lr=g["lr"], betas=g["betas"], eps=g["eps"], params=g["params"], criterion=crit)     # steps what the optimizer holds
     since, val_acc_history, best_acc, best_epoch, first_epoch = time.time(), [], 0.0, 0, 0
     if resume:
         assert save_model_path is not None
@@ -658,7 +747,7 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
             seen = inputs.shape[0] * (step.dist.world if step.dist.active else 1)
             run_loss += float(loss) * seen; run_hits += ops.raise_on_bad_labels(hits); n += seen
         print("train Loss: {:.4f}, Acc: {:.4f}".format(run_loss / max(n, 1), run_hits / max(n, 1)))
-        v_loss, v_acc = _evaluate(clf, dataloaders["val"], device)
+        v_loss, v_acc = _evaluate(clf, dataloaders["val"], device, criterion=crit)
         print("val Loss: {:.4f}, Acc: {:.4f}".format(v_loss, v_acc))
         val_acc_history.append(v_acc)
         if v_acc > best_acc:
@@ -678,7 +767,7 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
             break
     print("Training complete in {:.0f}s; best val Acc: {:4f}".format(time.time() - since, best_acc))
     clf.load_state_dict(best_wts)
-    tested = test_model(clf, test_loader)
+    tested = test_model(clf, test_loader) if crit is None else _test_model(clf, test_loader, None, crit)
     final = save_model_path or "best_weights.h5"
     root, ext = os.path.splitext(final)
     save_model(clf, root + ("_final_finetuned" if finetune else "_final") + ext)       # train.py:173-177

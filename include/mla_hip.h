@@ -513,6 +513,25 @@ int mla_axpy(float a, const float* x, float* y, int64_t n, mla_stream_t stream);
 int mla_cross_entropy(const float* x, int64_t ldx, const int64_t* labels, int64_t rows, int K, float inv_total,
                       float* loss, float* dx, int64_t ld_dx, int* n_correct, mla_stream_t stream);
 
+/* nn.CrossEntropyLoss with its options, beside mla_cross_entropy (which stays the plain criterion's kernel): class weights
+ * (weight: K floats on the device, NULL = all ones), label_smoothing in [0, 1], ignore_index, reduction 0 = mean | 1 = sum.
+ * A row whose label equals ignore_index adds nothing: no loss, exact zeros in dx, neither a hit nor a bad label. K <= 1024.
+ *   mla_cross_entropy_den : den[0] = sum of weight[y_b] over the rows with an in-range label other than ignore_index (one
+ *     workgroup, double precision, fixed order). Labels and weights only: a data-parallel step sums den over its ranks before
+ *     the main call, so that the mean is the global batch's.
+ *   mla_cross_entropy_opts: one wavefront per row; the row terms go to `workspace` (mla_cross_entropy_opts_workspace_bytes(rows)
+ *     bytes, 8-byte aligned) and one workgroup adds them in double in a fixed order: no atomics, bit-reproducible. The mean's
+ *     scale 1 / den[0] is read from DEVICE memory (den: NULL for the sum), so the sequence replays in a HIP graph. dx may be
+ *     NULL. counts = THREE ints [#argmax hits, #labels outside [0, K) other than ignore_index, #labels other than
+ *     ignore_index]; a label outside [0, K) is never used as an index, its dx row is zero and the loss is NaN. With no
+ *     counted row the mean is NaN (0 / 0, as torch) and the sum 0. */
+int mla_cross_entropy_den(const int64_t* labels, int64_t rows, int K, const float* weight, int64_t ignore_index, float* den,
+                          mla_stream_t stream);
+int64_t mla_cross_entropy_opts_workspace_bytes(int64_t rows);
+int mla_cross_entropy_opts(const float* x, int64_t ldx, const int64_t* labels, int64_t rows, int K, const float* weight,
+                           int64_t ignore_index, float label_smoothing, int reduction, const float* den, float* loss, float* dx,
+                           int64_t ld_dx, int* counts, void* workspace, mla_stream_t stream);
+
 /* --- finetune: gradients of the VGGish feature stack (train.py:96-97, :137), f32, NHWC ------ */
 
 /* Generic 3x3/pad-1 convolution entry over the compiled shape set (VGGish forward with or

@@ -1,0 +1,63 @@
+"""Worker of the 2-rank test of the criterion options in the training step (tests/test_ce_opts_gpu.py): each rank runs
+TrainStep(criterion=CrossEntropyLoss(weight, label_smoothing)) on ITS half of every global batch (gloo, two ranks on one GPU, as
+tests/_dp_worker.py). The ignored labels are split unevenly: rank 0's half holds three of them, rank 1's one, so the mean's
+denominator must be the global one. ``run`` is also what the test calls in its own process for the one-process twin."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+PKG = "audio-classification-using-a-deep-cnn-combined-with-multi-level-attention_amd"
+
+IGNORED = (0, 1, 3, 6)          # rows of the global batch of 8 whose label is -100
+
+
+def criterion():
+    return torch.nn.CrossEntropyLoss(weight=torch.linspace(0.5, 2.0, 10), label_smoothing=0.1)
+
+
+def run(steps, B, lo, hi, process_group):
+    mk = importlib.import_module("make_golden")
+    W = importlib.import_module(PKG + ".weights")
+    M = importlib.import_module(PKG + ".model")
+    TR = importlib.import_module(PKG + ".train")
+    ens = M.Ensemble("repeat", dict(mk.CNN_CONF), [2, 1], torch.device("cuda"), precision="f32")
+    ens.load_state_dict({k: torch.as_tensor(v) for k, v in W.make_state_dict(7, W.ensemble_shapes((2, 1), False)).items()})
+    ens.cuda()
+    step = TR.TrainStep(ens, lr=1e-3, criterion=criterion(), process_group=process_group)
+    out = {"losses": [], "counted": [], "hits": []}
+    for s in range(steps):
+        x, y = mk.synth_bags(100 + s, B)
+        y = y.clone()
+        y[list(IGNORED)] = -100
+        masks = mk.make_masks(200 + s, [2, 1], B)
+        for lvl, em in enumerate(ens.mla.embedded_mappings):
+            for j, d in enumerate(em.dropouts):
+                d.mask = masks["mla.embedded_mappings.%d.dropouts.%d" % (lvl, j)][lo:hi]
+        loss, hits = step(x[lo:hi].cuda(), y[lo:hi].cuda())
+        out["losses"].append(float(loss))
+        out["counted"].append(int(step.last_counted))
+        out["hits"].append(hits.tolist())
+    res = {k: np.array(v) for k, v in out.items()}
+    res.update({k: v.detach().cpu().numpy() for k, v in ens.state_dict().items() if k.startswith("mla.")})
+    return res
+
+
+def main():
+    import torch.distributed as dist
+    out_path, steps, B = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    res = run(steps, B, rank * B // world, (rank + 1) * B // world, None)
+    np.savez(out_path + ".rank%d.npz" % rank, **res)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
