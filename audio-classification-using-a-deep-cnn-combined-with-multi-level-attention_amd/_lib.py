@@ -134,6 +134,9 @@ def lib():
         L.mla_cross_entropy_opts_workspace_bytes.restype = i64
         L.mla_cross_entropy_opts_workspace_bytes.argtypes = [i64]
         L.mla_cross_entropy_opts.argtypes = [vp, i64, vp, i64, ci, vp, i64, cf, ci, vp, vp, vp, i64, vp, vp, vp]
+        L.mla_bce_workspace_bytes.restype = i64
+        L.mla_bce_workspace_bytes.argtypes = [i64]
+        L.mla_bce.argtypes = [vp, i64, vp, i64, i64, ci, vp, ci, cf, vp, vp, i64, vp, vp, vp]
         L.mla_conv3x3.argtypes = [vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, ci, ci, vp]
         L.mla_conv3x3_train.argtypes = [vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, vp]
         L.mla_conv_repack_dgrad.argtypes = [vp, i64, i64, vp, vp]

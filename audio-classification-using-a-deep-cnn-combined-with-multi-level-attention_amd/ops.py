@@ -669,6 +669,58 @@ def cross_entropy_opts(scores, labels, weight=None, ignore_index=-100, label_smo
     return loss, d, counts[0:2], counts[2:3]
 
 
+def check_targets(targets, K):
+    """nn.BCELoss raises on a target outside [0, 1] (a NaN included) and on a shape other than its input's. Host tensors are
+    checked here before the upload (no device sync); for device tensors the kernel takes no logarithm of such a cell and reports
+    it through its second counter (`hits[1]` = number of bad cells) + a NaN loss, which `raise_on_bad_targets` turns into the
+    same exception -- as check_labels does for class indices."""
+    if targets.dim() != 2 or targets.shape[1] != K:
+        raise ValueError("multi-label targets must have shape (batch, %d), one column per class, not %s" % (K, tuple(targets.shape)))
+    if not targets.is_cuda and targets.numel():
+        t = targets.detach().float()
+        if bool(torch.isnan(t).any()):
+            raise ValueError("a target is NaN; BCELoss targets lie in [0, 1]")
+        lo, hi = float(t.min()), float(t.max())
+        if lo < 0.0 or hi > 1.0:
+            raise ValueError("target %g lies outside [0, 1]" % (lo if lo < 0.0 else hi))
+
+
+def raise_on_bad_targets(hits):
+    """Call where the step's result is read on the host anyway: `hits` is bce_loss's pair [n_exact, n_bad_cells] (summed over the
+    ranks by a data-parallel step). Returns n_exact, the rows in which every class lies on the right side of 0.5."""
+    n, bad = (int(v) for v in hits.tolist())
+    if bad > 0:
+        raise ValueError("%d bad cell(s): a target that is NaN or outside [0, 1], or a probability outside [0, 1]" % bad)
+    return n
+
+
+def bce_loss(probs, targets, weight=None, reduction="mean", inv_total=None, want_grad=True):
+    """nn.BCELoss(weight, reduction="mean" | "sum") on (B, K <= 1024) probabilities with float32 targets (B, K) in [0, 1], soft
+    ones included: (loss, dprobs, hits, cell_hits). hits = int32 [rows with every class on the right side of 0.5 (subset accuracy),
+    bad cells] (raise_on_bad_targets reads it), cell_hits = int32 [cells on the right side]; both are views of one 3-element
+    tensor. ``inv_total``: the mean's scale, None = 1 / (B K); a data-parallel step passes 1 / (GLOBAL B * K), so that each rank's
+    loss is its share of the global mean (sum the losses) and dprobs is scaled for a summed gradient. Both operands may be column
+    slices with a pitch. Two launches, graph-capturable, bit-reproducible; see mla_bce for bad cells and NaN."""
+    _chk_rows(probs, torch.float32); _chk_rows(targets, torch.float32)
+    if reduction not in REDUCTIONS:
+        raise ValueError("reduction must be 'mean' or 'sum' (the HIP loss returns a scalar), not %r" % (reduction,))
+    B, K = probs.shape
+    assert tuple(targets.shape) == (B, K), "targets %s for probabilities %s" % (tuple(targets.shape), (B, K))
+    dev = probs.device
+    if weight is not None:
+        _chk(weight, torch.float32)
+        assert weight.numel() == K, "weight holds %d elements for %d classes" % (weight.numel(), K)
+    L = _lib.lib()
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    d = torch.empty((B, K), dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty(int(L.mla_bce_workspace_bytes(B)) // 8, dtype=torch.float64, device=dev)
+    scale = 1.0 / (B * K) if inv_total is None else float(inv_total)
+    _lib.check(_timed("bce", L.mla_bce, _p(probs), probs.stride(0), _p(targets), targets.stride(0), B, K, _p(weight), REDUCTIONS[reduction],
+                      scale, _p(loss), _p(d), K, _p(counts), _p(ws), _lib.stream_ptr()))
+    return loss, d, counts[0:2], counts[2:3]
+
+
 def dropout_mask_dev(n, seed, stream_base, counter, offset, p_drop, device, out=None):
     """dropout_mask with stream_id = stream_base + counter[0] + 1 read on the device (graph-captured training step)."""
     assert counter.dtype == torch.int64 and counter.is_cuda

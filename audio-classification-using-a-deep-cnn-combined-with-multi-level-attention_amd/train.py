@@ -83,6 +83,33 @@ def parse_criterion(criterion, classes):
     return {"weight": weight, "ignore_index": int(criterion.ignore_index), "label_smoothing": eps, "reduction": criterion.reduction}
 
 
+def parse_bce_criterion(criterion, classes):
+    """What the HIP binary cross-entropy (``ops.bce_loss``) needs of an ``nn.BCELoss``, checked on the host without a device:
+    {"weight": float32 CPU tensor of ``classes`` elements or None, "reduction"}. The weight is the per-class rescaling of
+    ``nn.BCELoss(weight=)``, one entry per column. Refused as ``parse_criterion`` refuses: another loss (TypeError;
+    ``nn.BCEWithLogitsLoss`` among them, the head's outputs are probabilities, not logits); ``reduction="none"``, a weight that is
+    not a finite, non-negative float tensor of ``classes`` elements with a positive entry (ValueError); more than 1024 classes
+    (NotImplementedError)."""
+    if not isinstance(criterion, nn.BCELoss):
+        raise TypeError("the HIP multi-label step implements nn.BCELoss, not %s" % type(criterion).__name__)
+    if criterion.reduction not in ("mean", "sum"):
+        raise ValueError("reduction=%r: the HIP step returns a scalar loss, 'mean' or 'sum'" % (criterion.reduction,))
+    if classes > 1024:
+        raise NotImplementedError("the HIP binary cross-entropy is built for up to 1024 classes, not %d" % classes)
+    weight = criterion.weight
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or not weight.is_floating_point():
+            raise ValueError("the class weights must be a float tensor")
+        if weight.dim() != 1 or weight.numel() != classes:
+            raise ValueError("the class weights have shape %s; the head has %d classes" % (tuple(weight.shape), classes))
+        weight = weight.detach().to("cpu", torch.float32).contiguous()
+        if not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+            raise ValueError("the class weights must be finite and non-negative")
+        if not bool((weight > 0).any()):
+            raise ValueError("the class weights are all zero")
+    return {"weight": weight, "reduction": criterion.reduction}
+
+
 class TrainStep:
     """One fused training step of an ``Ensemble``: frozen CNN (the reference default
     ``cnn_trainable=False``; model.py:159-160) or finetune (every parameter trainable, train.py:96-97;
@@ -115,11 +142,18 @@ class TrainStep:
         ``ignore_index``, ``label_smoothing`` and ``reduction`` ("mean" | "sum") the step honours (``ops.cross_entropy_opts``). The
         weight is copied to the device once, here; the other three are read here and must not change afterwards. Under a process
         group the mean's denominator is the global batch's; ``last_counted`` holds the (global) number of rows whose label is not
-        ``ignore_index``, a 1-element device tensor, after each step."""
+        ``ignore_index``, a 1-element device tensor, after each step.
+        An ``nn.BCELoss`` (``weight``, ``reduction`` "mean" | "sum") makes it a multi-label step (``ops.bce_loss``): labels are
+        (B, classes) multi-hot or soft targets in [0, 1], the mean divides by global batch x classes, ``hits`` counts the rows
+        with every class on the right side of 0.5, and ``last_cell_hits`` holds the (global) number of such cells, a 1-element
+        device tensor, after each step; ``last_counted`` stays None."""
         self.clf, self.lr, self.betas, self.eps, self.t = clf, lr, betas, eps, 0
         self.criterion = criterion
-        self._crit = None if criterion is None else parse_criterion(criterion, clf.mla.classes)
+        self._bce = isinstance(criterion, nn.BCELoss)
+        parse = parse_bce_criterion if self._bce else parse_criterion
+        self._crit = None if criterion is None else parse(criterion, clf.mla.classes)
         self._crit_weight, self._counted, self.last_counted = None, None, None
+        self._cell_hits, self.last_cell_hits = None, None
         self.groups = None                                  # the optimizer's param_groups (the live list): the grouped step
         if optimizer is not None:
             if params is not None:
@@ -343,6 +377,11 @@ class TrainStep:
     def _check_criterion(self):
         """The criterion's scalars as they were when the step was built (a graph holds them as launch arguments)."""
         c, live = self._crit, self.criterion
+        if self._bce:
+            if live.reduction != c["reduction"]:
+                raise RuntimeError("the criterion changed after this TrainStep was built (reduction: %r, was %r): build a new TrainStep"
+                                   % (live.reduction, c["reduction"]))
+            return
         now = (float(live.label_smoothing), int(live.ignore_index), live.reduction)
         if now != (c["label_smoothing"], c["ignore_index"], c["reduction"]):
             raise RuntimeError("the criterion changed after this TrainStep was built (label_smoothing, ignore_index, reduction: %r, was "
@@ -353,7 +392,10 @@ class TrainStep:
         Returns (loss, hits) as device tensors (no host sync; train.py:141-142 syncs via .item()): hits = int32
         [n_correct, n_labels_out_of_range] over the global batch (``ops.raise_on_bad_labels(hits)`` -> n_correct or IndexError).
         With the HIP graph in use the two tensors (and ``last_out``) are the graph's own buffers: valid until the next step.
-        ``inputs`` and ``labels`` are only read, and not kept: the graph works on private copies (one device copy per step)."""
+        ``inputs`` and ``labels`` are only read, and not kept: the graph works on private copies (one device copy per step).
+        With an ``nn.BCELoss``: labels (B, classes) of a bool, integer or float dtype, values in [0, 1]; hits = int32 [rows in which
+        every class lies on the right side of 0.5 (subset accuracy), bad cells] over the global batch
+        (``ops.raise_on_bad_targets(hits)`` -> the row count or ValueError)."""
         clf = self.clf
         for n, p, ptr in self._seated:
             if p.data_ptr() != ptr:
@@ -362,17 +404,26 @@ class TrainStep:
         clf.train()
         if self._crit is None:
             ops.check_labels(labels, clf.mla.classes)
+        elif self._bce:
+            self._check_criterion()
+            ops.check_targets(labels, clf.mla.classes)
         else:
             self._check_criterion()
             ops.check_labels_ignoring(labels, clf.mla.classes, self._crit["ignore_index"])
         if self._graph_usable(inputs) and not self._graph_disturbed():
             return self._graphed(inputs, labels)
         with torch.no_grad():
-            loss, hits, out = self._body(inputs, labels.to(inputs.device).long().contiguous(), captured=False)
+            loss, hits, out = self._body(inputs, self._device_labels(labels, inputs.device), captured=False)
         self._eager_shape = tuple(inputs.shape)
         self.last_out = out
         self.last_counted = self._counted
+        self.last_cell_hits = self._cell_hits
         return loss, hits
+
+    def _device_labels(self, labels, dev):
+        """Class indices as int64, multi-label targets as float32: what the loss kernels read."""
+        labels = labels.to(dev)
+        return (labels.float() if self._bce else labels.long()).contiguous()
 
     # ---- the step as ONE HIP graph (no data-parallel group): ~130 small launches of the head's forward / backward / Adam and the
     # CNN's kernels become one graph launch; what the host used to pass per step -- Adam's step count, the dropout call number --
@@ -424,13 +475,13 @@ class TrainStep:
             self._dev_t = self.t
         if g is None:
             # the static input and labels are the graph's own: the caller's tensors are never written and never kept
-            g = {"shape": tuple(inputs.shape), "x": inputs.clone(), "y": labels.to(dev).long().contiguous().clone(),
+            g = {"shape": tuple(inputs.shape), "x": inputs.clone(), "y": self._device_labels(labels, dev).clone(),
                  "bases": {id(d): d.calls - self.t for d in drops}}
             torch.cuda.synchronize()
             g["graph"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g["graph"], capture_error_mode="relaxed"), torch.no_grad():
                 g["loss"], g["hits"], g["out"] = self._body(g["x"], g["y"], captured=True, bases=g["bases"])
-            g["counted"] = self._counted
+            g["counted"], g["cell_hits"] = self._counted, self._cell_hits
             # what the recorded kernels address without having allocated it during the capture: compared before every replay
             # (_graph_disturbed) and kept alive for as long as this graph is
             scratch = ops.scratch(dev)
@@ -442,7 +493,8 @@ class TrainStep:
             self.captures += 1
         else:
             g["x"].copy_(inputs, non_blocking=True)
-            g["y"].copy_(labels.to(dev, non_blocking=True).long(), non_blocking=True)
+            on_dev = labels.to(dev, non_blocking=True)
+            g["y"].copy_(on_dev if self._bce else on_dev.long(), non_blocking=True)       # copy_ casts to the buffer's float32
         if self.groups is not None:
             self._prepare_groups(self.t + 1)
         else:
@@ -462,7 +514,7 @@ class TrainStep:
                 if hasattr(m, "_cache"):
                     m._cache.key = None
         self.last_out = g["out"]
-        self.last_counted = g["counted"]
+        self.last_counted, self.last_cell_hits = g["counted"], g["cell_hits"]
         return g["loss"], g["hits"]
 
     def _body(self, inputs, labels, captured, bases=None):
@@ -489,6 +541,10 @@ class TrainStep:
         out = mla_train.mla_forward(clf.mla, feats.reshape(-1, clf.mla.slots, clf.emb_input_size), ctx)
         if self._crit is None:
             loss, dout, hits = ops.cross_entropy(out, labels, 1.0 / B_global)
+        elif self._bce:
+            # every scalar of the loss is a launch argument: the mean's scale is the global batch's, known on the host
+            loss, dout, hits, self._cell_hits = ops.bce_loss(out, labels, self._crit_weight, self._crit["reduction"],
+                                                             inv_total=1.0 / (B_global * out.shape[1]))
         else:
             # the mean's denominator is all-reduced inside, on this (the compute) stream like the SyncBN sums, in front of the loss
             c = self._crit
@@ -537,7 +593,9 @@ class TrainStep:
                 self.dist.all_reduce_sum(self.flat_g, "grad:flat")
             self.dist.all_reduce_sum(loss, "loss")
             self.dist.all_reduce_sum(hits, "hits")             # [running_corrects (train.py:142), #bad labels] over the global batch
-            if self._crit is not None:
+            if self._bce:
+                self.dist.all_reduce_sum(self._cell_hits, "cell_hits")
+            elif self._crit is not None:
                 self.dist.all_reduce_sum(self._counted, "counted")
         if self.groups is not None:
             # clip_grad_norm_ on the (all-reduced: the waits above are behind us) flat gradient, then every group in one launch.
@@ -572,7 +630,11 @@ class TrainStep:
 
 def _evaluate(clf, loader, device, collect=False, criterion=None):
     """criterion: None = the plain mean cross-entropy, or the nn.CrossEntropyLoss to evaluate with (ops.cross_entropy_opts), as the
-    reference calls ``criterion(outputs, labels)`` in every phase; the accuracy divides by all rows seen (train.py:145) either way."""
+    reference calls ``criterion(outputs, labels)`` in every phase; the accuracy divides by all rows seen (train.py:145) either way.
+    An nn.BCELoss: labels are (B, classes) targets, the loss is ops.bce_loss's, the accuracy is the subset accuracy (rows with every
+    class on the right side of 0.5), and collect=True returns the outputs (N, K) and the targets (N, K) instead of predictions."""
+    if isinstance(criterion, nn.BCELoss):
+        return _evaluate_multilabel(clf, loader, device, collect, criterion)
     clf.eval()
     tot_loss, tot_hits, n, preds, trues = 0.0, 0, 0, [], []
     crit, crit_weight = None, None
@@ -599,6 +661,80 @@ def _evaluate(clf, loader, device, collect=False, criterion=None):
     if collect:
         return tot_loss / max(n, 1), tot_hits / max(n, 1), torch.cat(preds), torch.cat(trues)
     return tot_loss / max(n, 1), tot_hits / max(n, 1)
+
+
+def _evaluate_multilabel(clf, loader, device, collect, criterion):
+    """_evaluate under an nn.BCELoss."""
+    clf.eval()
+    tot_loss, tot_hits, n, outs, trues = 0.0, 0, 0, [], []
+    crit, crit_weight = None, None
+    with torch.no_grad():
+        for inputs, labels in loader:
+            inputs = inputs.to(device).float()
+            out = clf(inputs)
+            if crit is None:
+                crit = parse_bce_criterion(criterion, out.shape[1])
+                crit_weight = None if crit["weight"] is None else crit["weight"].to(device)
+            ops.check_targets(labels, out.shape[1])
+            targets = labels.to(device).float().contiguous()
+            loss, _, hits, _ = ops.bce_loss(out, targets, crit_weight, crit["reduction"], want_grad=False)
+            tot_loss += float(loss) * inputs.shape[0]
+            tot_hits += ops.raise_on_bad_targets(hits)
+            n += inputs.shape[0]
+            if collect:
+                outs.append(out.cpu()); trues.append(targets.cpu())
+    if collect:
+        return tot_loss / max(n, 1), tot_hits / max(n, 1), torch.cat(outs), torch.cat(trues)
+    return tot_loss / max(n, 1), tot_hits / max(n, 1)
+
+
+def multilabel_summary(y_true, y_score, target_names=None):
+    """The report of a multi-label run, from targets (N, K) (a cell is positive at >= 0.5) and scores (N, K). Per class: average
+    precision = sum_n (R_n - R_{n-1}) P_n over the DISTINCT score thresholds in descending order (tied scores form one threshold),
+    ROC AUC = the Mann-Whitney statistic with ties counted one half, and the support (positives). A class without a positive has
+    AP = NaN; one without a positive or without a negative has AUC = NaN. "mAP", "mAUC" and "d_prime" = sqrt(2) ndtri(mAUC)
+    average over the defined classes only; "classes_without_positives" and "classes_undefined_auc" say how many were left out.
+    "subset_accuracy" (all K cells of a row right) and "micro avg" precision / recall / f1-score threshold the scores at 0.5.
+    Plain numpy in float64: nothing here is on the GPU path."""
+    y_true = np.asarray(y_true, dtype=np.float64) >= 0.5
+    y_score = np.asarray(y_score, dtype=np.float64)
+    if y_true.ndim != 2 or y_true.shape != y_score.shape:
+        raise ValueError("targets %s and scores %s must both be (N, K)" % (y_true.shape, y_score.shape))
+    n, k = y_true.shape
+    if target_names is None:
+        target_names = default_target_names(k)
+    if len(target_names) != k:
+        raise ValueError("%d target names for %d classes" % (len(target_names), k))
+    ap, auc = np.full(k, np.nan), np.full(k, np.nan)
+    for c in range(k):
+        pos_total = int(y_true[:, c].sum())
+        neg_total = n - pos_total
+        order = np.argsort(-y_score[:, c], kind="stable")
+        s, t = y_score[order, c], y_true[order, c]
+        last = np.flatnonzero(np.append(s[1:] != s[:-1], True)) if n else np.zeros(0, dtype=np.int64)    # last row of each threshold
+        tp = np.cumsum(t)[last].astype(np.float64)                 # positives at or above the threshold
+        fp = (last + 1) - tp
+        if pos_total > 0:
+            recall = tp / pos_total
+            ap[c] = float(np.sum(np.diff(np.append(0.0, recall)) * (tp / (tp + fp))))
+        if pos_total > 0 and neg_total > 0:
+            pos_g, neg_g = np.diff(np.append(0.0, tp)), np.diff(np.append(0.0, fp))
+            auc[c] = float(np.sum(pos_g * ((neg_total - fp) + 0.5 * neg_g)) / (float(pos_total) * float(neg_total)))
+    res = {name: {"average_precision": float(ap[i]), "roc_auc": float(auc[i]), "support": int(y_true[:, i].sum())}
+           for i, name in enumerate(target_names)}
+    res["mAP"] = float(np.mean(ap[~np.isnan(ap)])) if (~np.isnan(ap)).any() else float("nan")
+    res["mAUC"] = float(np.mean(auc[~np.isnan(auc)])) if (~np.isnan(auc)).any() else float("nan")
+    res["d_prime"] = float(np.sqrt(2.0) * torch.special.ndtri(torch.tensor(res["mAUC"], dtype=torch.float64)))
+    res["classes_without_positives"] = int(np.isnan(ap).sum())
+    res["classes_undefined_auc"] = int(np.isnan(auc).sum())
+    pred = y_score >= 0.5
+    res["subset_accuracy"] = float((pred == y_true).all(axis=1).mean()) if n else 0.0
+    tp_all, n_pred, n_pos = float((pred & y_true).sum()), float(pred.sum()), float(y_true.sum())
+    prec = tp_all / n_pred if n_pred else 0.0
+    rec = tp_all / n_pos if n_pos else 0.0
+    res["micro avg"] = {"precision": prec, "recall": rec, "f1-score": 2 * prec * rec / (prec + rec) if prec + rec else 0.0,
+                        "support": int(n_pos)}
+    return res
 
 
 def classification_summary(y_true, y_pred, target_names=TARGET_NAMES):
@@ -648,6 +784,11 @@ def _test_model(model, dataloader, target_names, criterion):
     since = time.time()
     print("Testing"); print("-" * 10)
     loss, acc, preds, trues = _evaluate(model, dataloader, device, collect=True, criterion=criterion)
+    if isinstance(criterion, nn.BCELoss):                  # preds: the outputs (N, K); the report is mAP / AUC, not a confusion matrix
+        results = multilabel_summary(trues.numpy(), preds.numpy(), target_names)
+        print("{} Loss: {:.4f}, subset Acc: {:.4f}, mAP: {:.4f}, mAUC: {:.4f}".format("test", loss, acc, results["mAP"], results["mAUC"]))
+        print("Testing complete in {:.0f}s".format(time.time() - since))
+        return results["mAP"], results
     if criterion is not None:
         keep = trues != int(criterion.ignore_index)
         preds, trues = preds[keep], trues[keep]
@@ -705,9 +846,15 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
     clips the gradient's L2 norm before each update. The last two need ``extended_optimizer=True``.
     ``extended_criterion=True``: ``criterion``'s ``weight``, ``ignore_index``, ``label_smoothing`` and ``reduction`` ("mean" | "sum") are
     honoured by the step (``TrainStep(criterion=)``) and by the validation and test loss; off, the criterion is the plain mean and
-    a label of -100 is refused like any other label outside the classes."""
-    if not isinstance(criterion, nn.CrossEntropyLoss) or not isinstance(optimizer, torch.optim.Adam):
-        raise TypeError("the HIP training step implements CrossEntropyLoss + Adam (train.py:369-372)")
+    a label of -100 is refused like any other label outside the classes.
+    ``criterion=nn.BCELoss(weight, reduction)`` with ``extended_criterion=True`` trains a multi-label head: labels are (B, classes)
+    targets in [0, 1], "train Acc" is the subset accuracy, validation computes ``multilabel_summary`` and its **mAP** is the number
+    that enters the history, selects the best weights, is stored as the checkpoint's ``accuracy`` and drives ``patience``;
+    ``scheduler`` still gets the validation loss, and the test phase returns ``(mAP, summary)``."""
+    multilabel = extended_criterion and isinstance(criterion, nn.BCELoss)
+    if not (isinstance(criterion, nn.CrossEntropyLoss) or multilabel) or not isinstance(optimizer, torch.optim.Adam):
+        raise TypeError("the HIP training step implements CrossEntropyLoss + Adam (train.py:369-372), and with extended_criterion=True "
+                        "BCELoss + Adam")
     if not extended_optimizer:
         if scheduler is not None or max_grad_norm is not None:
             raise ValueError("scheduler= and max_grad_norm= belong to the grouped HIP step: pass extended_optimizer=True")
@@ -745,10 +892,17 @@ def train_model(clf, dataloaders, criterion, optimizer, num_epochs=25, patience=
             loss, hits = step(inputs.to(device).float(), labels)
             # under data parallelism the step returns the GLOBAL mean loss and the GLOBAL hit count (train.py:141-142 on the whole batch)
             seen = inputs.shape[0] * (step.dist.world if step.dist.active else 1)
-            run_loss += float(loss) * seen; run_hits += ops.raise_on_bad_labels(hits); n += seen
+            run_loss += float(loss) * seen; n += seen
+            run_hits += ops.raise_on_bad_targets(hits) if multilabel else ops.raise_on_bad_labels(hits)
         print("train Loss: {:.4f}, Acc: {:.4f}".format(run_loss / max(n, 1), run_hits / max(n, 1)))
-        v_loss, v_acc = _evaluate(clf, dataloaders["val"], device, criterion=crit)
-        print("val Loss: {:.4f}, Acc: {:.4f}".format(v_loss, v_acc))
+        if multilabel:                                     # the model-selection metric is the validation mAP
+            v_loss, v_subset, v_out, v_true = _evaluate(clf, dataloaders["val"], device, collect=True, criterion=crit)
+            v_sum = multilabel_summary(v_true.numpy(), v_out.numpy())
+            v_acc = v_sum["mAP"]
+            print("val Loss: {:.4f}, subset Acc: {:.4f}, mAP: {:.4f}, mAUC: {:.4f}".format(v_loss, v_subset, v_acc, v_sum["mAUC"]))
+        else:
+            v_loss, v_acc = _evaluate(clf, dataloaders["val"], device, criterion=crit)
+            print("val Loss: {:.4f}, Acc: {:.4f}".format(v_loss, v_acc))
         val_acc_history.append(v_acc)
         if v_acc > best_acc:
             best_acc, best_epoch, best_wts = v_acc, epoch, copy.deepcopy(clf.state_dict())

@@ -532,6 +532,21 @@ int mla_cross_entropy_opts(const float* x, int64_t ldx, const int64_t* labels, i
                            int64_t ignore_index, float label_smoothing, int reduction, const float* den, float* loss, float* dx,
                            int64_t ld_dx, int* counts, void* workspace, mla_stream_t stream);
 
+/* nn.BCELoss(weight, reduction) on probabilities p (rows, K <= 1024; the head's sigmoid outputs) with float32 targets (rows, K) in
+ * [0, 1], soft targets included: the criterion of a multi-label step.
+ *   term = w_k ((y - 1) max(log(1 - p), -100) - y max(log p, -100)),  loss = s * sum term,
+ *   dp = s w_k (p - y) / max((1 - p) p, 1e-12),  s = scale under reduction 0 (mean; pass 1 / (GLOBAL rows * K)), 1 under 1 (sum).
+ * weight: K floats on the device, NULL = all ones. dp may be NULL (loss and counters only, the same loss bits). One wavefront
+ * per row, the row terms go to `workspace` (mla_bce_workspace_bytes(rows) bytes, 8-byte aligned) and one workgroup adds them in
+ * double in a fixed order: no atomics, bit-reproducible; every scalar is a launch argument, so the pair replays in a HIP graph.
+ * A cell whose target is NaN or outside [0, 1], or whose p lies outside [0, 1], is BAD (torch raises): no logarithm is taken,
+ * its dp is an exact zero and the loss is NaN. A NaN in p travels into the loss and into its own cell of dp.
+ * counts = THREE ints, both sides thresholded at 0.5: [rows with every class on the right side (subset accuracy), bad cells,
+ * cells on the right side]; a bad cell is never right. */
+int64_t mla_bce_workspace_bytes(int64_t rows);
+int mla_bce(const float* p, int64_t ldp, const float* target, int64_t ldt, int64_t rows, int K, const float* weight, int reduction,
+            float scale, float* loss, float* dp, int64_t ld_dp, int* counts, void* workspace, mla_stream_t stream);
+
 /* --- finetune: gradients of the VGGish feature stack (train.py:96-97, :137), f32, NHWC ------ */
 
 /* Generic 3x3/pad-1 convolution entry over the compiled shape set (VGGish forward with or
